@@ -15,7 +15,14 @@ blocks; a step = every rank passes once over ITS contigs; the total work per ste
 scaling), no collective on the data path (regions shard embarrassingly).  `--weak` gives every rank one
 contig of its own instead.
 
+A plain run does what the headline needs: set-up, warmup, ONE timed region of exactly --steps steps, the result line
+(`value`, `ms_per_step`, ...).  `--full` adds everything else, outside that region: the median of 5 regions (--repeat), the
+HBM-resident and pipelined passes, the stage breakdown and roofline, the CPU baseline, configs[2], the whole-genome pass and
+the extra configurations (N > 1: the indel leg and the sharded whole-genome pass).  `--dump-outputs DIR` writes the arrays
+the last timed step returned as DIR/<name>.npy (inputs are seeded: two builds can be compared array for array).
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 3 --warmup 1
 """
@@ -71,12 +78,57 @@ def parse():
     ap.add_argument("--indel-passes", type=int, default=3)
     ap.add_argument("--configs2-length", type=int, default=CHR1_LEN)
     ap.add_argument("--no-overlap", action="store_true", help="collect every step's results before the next step is enqueued")
-    ap.add_argument("--repeat", type=int, default=5, help="timed regions of --steps steps each; value = the median, min / max reported")
+    ap.add_argument("--repeat", type=int, default=None,
+                    help="timed regions of --steps steps each; value = the median, min / max reported (default 1, or 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: HBM-resident and pipelined passes, stage breakdown, roofline, CPU baseline, "
+                         "configs[2], whole-genome pass, extra configurations (N>1: the indel leg and the sharded whole-genome pass)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-sample-chunks", type=int, default=0,
                     help="chunks of contig 0 the CPU baseline runs; 0 = the whole contig (SURVEY 8d: one OS process per usable core pulling chunks from a queue)")
     ap.add_argument("--cnn-precision", default="default", choices=["default", "fp32", "fp16x3"],
                     help="trunk kernel: exact fp32 MFMA (k4_conv12) or fp16x3 split precision (k5_trunk_p3)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(res, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write the array fields of one call_chunks result as out_dir/<name>.npy: floats as they are (float32 / float64), integers as float32
+    where that is exact (|v| < 2^24) and float64 otherwise.  If the whole exceeds `limit` bytes, the per-site arrays keep a fixed seeded
+    sample of their rows (the same rows in every array), and sample_rows.npy says which."""
+    arrs = {}
+    for k, v in res.items():
+        if isinstance(v, torch.Tensor):
+            v = v.cpu().numpy()
+        if not isinstance(v, np.ndarray):
+            continue
+        if v.dtype.kind == "f":
+            v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+        else:
+            exact = v.size == 0 or int(np.abs(v.astype(np.int64)).max()) < (1 << 24)
+            v = v.astype(np.float32 if exact else np.float64)
+        arrs[k] = v
+    n = int(res.get("n", 0))
+    per_site = [k for k, v in arrs.items() if v.ndim and v.shape[0] == n]
+    total = sum(v.nbytes for v in arrs.values())
+    if total > limit and n:
+        row_bytes = sum(arrs[k].nbytes // n for k in per_site) + 8                # + the row's entry in sample_rows
+        other = total - sum(arrs[k].nbytes for k in per_site)
+        keep = max(1, min(n, (limit - other) // row_bytes))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        for k in per_site:
+            arrs[k] = arrs[k][rows]
+        arrs["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrs)
 
 
 def usable_cpus():
@@ -1260,8 +1312,8 @@ def main():
     import gc
     gc.collect()
     gc.disable()                                                  # a collector pause is tens of ms: 2-3 steps
-    # --repeat R: R timed regions of K steps each, every one bracketed by barrier + synchronize; the line reports the MEDIAN region
-    # (value, ms_per_step) and the spread
+    # --repeat R (default 1; 5 with --full): R timed regions of K steps each, every one bracketed by barrier + synchronize; the line
+    # reports the MEDIAN region (value, ms_per_step) and the spread
     dts, n_sites_rank, r = [], 0, None
     trunk_ms = trunk_launches = 0.0
     for _ in range(max(1, args.repeat)):
@@ -1283,6 +1335,8 @@ def main():
     dt = dts[order[len(dts) // 2]]
     gc.enable()
     eng.enable_timing(False)                                      # (trunk_ms / trunk_launches: HIP-event totals over ALL the timed regions)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(r, args.dump_outputs)                        # what the last timed step returned (rank 0's last unit)
     h2d_gbs, h2d_ms, h2d_bytes = uploader.h2d_rate()
     from nanocaller_amd.shard import dist_max, dist_sum
     total_sites = dist_sum(n_sites_rank)                # whole-job aggregate over the K steps of one region
@@ -1297,7 +1351,7 @@ def main():
     # ---- N > 1: the indel half over the same sharded contig list (configs[3] is SNP + indel): every rank runs the indel pass over ITS contigs,
     # `--indel-passes` times, from pinned host memory, between barriers; no collective on the data path
     indel_leg = None
-    if world > 1 and not args.no_indel_leg:
+    if args.full and world > 1 and not args.no_indel_leg:
         try:
             jobs = [IndelJob(eng, L, seed=4813 + k) for k in mine]
             for j in jobs:
@@ -1343,7 +1397,7 @@ def main():
             indel_leg = {"error": "%s: %s" % (type(e).__name__, e)}
     # ---- N > 1: BASELINE.json configs[3], the whole-genome mix sharded by shard_plan (every rank takes part; rank 0 reports it)
     wgs_sharded = None
-    if world > 1 and not args.no_wgs:
+    if args.full and world > 1 and not args.no_wgs:
         try:
             wgs_sharded = wgs_sharded_block(eng, uploader, local, args.model, rank, world, barrier, args.wgs_scale)
         except Exception as e:                                      # never take the headline down
@@ -1356,109 +1410,8 @@ def main():
         n_units = args.steps * per_step
         c0 = contigs[0]
         pack = c0.pack
-        # ---- the same units from HBM-resident packs (round 1's definition of the timed region), contig 0
-        rs_sites, rs_dt, r0 = measure(eng, uploader, contigs[:1], n_units, 1, params, chunks, local, lambda: None, not args.no_overlap, True)
-        n_sites = int(r0["n"])                          # sites of contig 0: the stage numbers below are per pass over it
-
-        def step():
-            return snpCaller.call_chunks(params, chunks, device=local, dpk=pack)
-        # stage breakdown (scan / featurize / CNN stage): event pairs around each stage put barrier packets on the stream,
-        # so they are taken in their own short loop after the timed region
-        eng.enable_timing(True)
-        for _ in range(min(3, args.steps)):
-            step()
-        s2, cnt = eng.timing_sums()
-        eng.enable_timing(False)
-        stage_ms = np.array([s2[0] / max(1, cnt[0]), s2[1] / max(1, cnt[1]), s2[2] / max(1, cnt[2])])
-        # expansion kernel alone
-        t = uploader.submit(c0.wire)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(3):
-            uploader.expand(t)
-        e1.record()
-        torch.cuda.synchronize()
-        uploader.release(t)
-        expand_ms = e0.elapsed_time(e1) / 3
-        # host genotype rules + VCF record text for one pass' results (native formatter), untimed above: the third number
-        # SURVEY.md 8(d) asks for (kernels only / + H2D + D2H / end to end incl. host K6 + VCF text)
-        tv = time.perf_counter()
-        vcf = snpCaller.snp_vcf_text("chr20", r0["pos"], r0["ref"], r0["probs"], r0["dp"], r0["freq"], r0["fwd_dp"], r0["rev_dp"],
-                                     haploid=(args.ploidy == "haploid"), as_array=True)
-        vcf_ms = (time.perf_counter() - tv) * 1e3
-        # the production loop (snpCaller.caller) formats contig i on a worker thread while the GPU runs contig i+1: measure
-        # that pipeline with the uploads inside
-        from concurrent.futures import ThreadPoolExecutor
-
-        scratch = np.empty((400 + 5) * max(n_sites, 1) * 5 // 4 + 65536, np.uint8)
-
-        def fmt(res):
-            return len(snpCaller.snp_vcf_text("chr20", res["pos"], res["ref"], res["probs"], res["dp"], res["freq"], res["fwd_dp"],
-                                              res["rev_dp"], haploid=(args.ploidy == "haploid"), as_array=True, out=scratch))
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            torch.cuda.synchronize()
-            tp = time.perf_counter()
-            pend, prev, pipe_sites = None, None, 0
-            nxt = uploader.submit(contigs[0].wire)
-            for i in range(n_units + 1):
-                cur = None
-                if i < n_units:
-                    tk = nxt
-                    dpk_i = uploader.expand(tk)
-                    nxt = uploader.submit(contigs[(i + 1) % len(contigs)].wire) if i + 1 < n_units else None
-                    cur = snpCaller.call_chunks(params, chunks, device=local, dpk=dpk_i, defer=True)
-                    uploader.release(tk)
-                if prev is not None:
-                    res = prev.result()
-                    pipe_sites += int(res["n"])
-                    if pend is not None:
-                        pend.result()
-                    pend = pool.submit(fmt, res)
-                prev = cur
-            pend.result()
-            pipelined_dt = time.perf_counter() - tp
         ms_per_step = dt / args.steps * 1e3
         value = total_sites / dt
-        sites_timed = n_sites_rank * len(dts)                          # this rank's sites inside ALL the timed regions (the trunk events span them)
-        cnn_tflops = SNP_FLOP_PER_SITE * n_sites / (stage_ms[2] * 1e-3) / 1e12 if stage_ms[2] > 0 else 0.0
-        # dominant kernel = fused conv1+conv2+conv3 trunk: algorithmic FLOP of its launches in the timed region / their
-        # summed HIP-event durations == FLOP per launch / average launch duration
-        n_launch = max(1.0, trunk_launches)
-        trunk_tflops = TRUNK_FLOP_PER_SITE * sites_timed / (trunk_ms * 1e-3) / 1e12 if trunk_ms > 0 else 0.0
-        scan_bytes = c0.entries + L                            # (d+1) B/column, SURVEY.md 8d
-        feat_bytes = (5403 - 2050) * n_sites                  # SURVEY.md 8d's 5,403 B/site with the tensor written as int16 (2,050 B) instead of fp32
-        tt = trunk_traffic_from_profiles()
-        traffic, stale_note = None, None
-        eng.set_tensor_format(int16=not exact_fp32)                # (as the timed region ran: which trunk kernel does this context launch?)
-        mfma_per_site, trunk_kernel = eng.trunk_info()
-        eng.set_tensor_format(int16=False)
-        if tt and tt.get("kernel") == trunk_kernel:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from build_tag import TRUNK_SOURCES
-            tag_ok, stale_note = traffic_build_check(tt, TRUNK_SOURCES)
-            if tag_ok:
-                traffic = tt["bytes_per_site"] * sites_timed / n_launch
-        common = {"achieved": trunk_tflops, "unit": "TFLOP/s", "traffic": traffic,
-                  "traffic_note": ("HBM bytes per launch = bytes per site from the committed PMC passes (%s) x sites per launch of this run"
-                                   % tt.get("source", "profiles/trunk_traffic.json")) if traffic else (stale_note or "no PMC pass committed for this kernel build"),
-                  "launches_in_timed_region": n_launch, "avg_launch_ms": float(trunk_ms / n_launch),
-                  "flop_per_launch": TRUNK_FLOP_PER_SITE * sites_timed / n_launch,
-                  "cnn_stage_tflops": cnn_tflops, "cnn_stage_ms": float(stage_ms[2])}
-        if exact_fp32:
-            roofline = {"bound": "mfma", "kernel": "k4_conv12: fused conv1+conv2+conv3 of the SNP CNN, fp32 MFMA 16x16x4",
-                        "peak": FP32_MFMA_PEAK_TFLOPS, "frac": trunk_tflops / FP32_MFMA_PEAK_TFLOPS, **common}
-        else:
-            peak = F16_MFMA_PEAK_TFLOPS / 3.0
-            exec_tflops = mfma_per_site * 16384.0 * sites_timed / (trunk_ms * 1e-3) / 1e12 if trunk_ms > 0 else 0.0
-            roofline = {"bound": "mfma", "kernel": "%s: fused conv1+conv2+conv3 of the SNP CNN, three roles on three sites; f16 MFMA 16x16x32, f32 accumulate" % trunk_kernel,
-                        "kernel_note": "fp32-equivalent products as hi*hi + hi*lo + lo*hi (3 f16 products); k5_trunk_lin runs conv1 on the integer tensor entries "
-                                       "(exact in f16) with the coverage scale on the accumulators: 2 products there",
-                        "peak": peak, "peak_note": "dense f16 MFMA peak 2500 TF / 3 products per fp32-equivalent product",
-                        "frac": trunk_tflops / peak, "executed_mfma_per_site": mfma_per_site, "executed_f16_mfma_tflops": exec_tflops,
-                        "executed_frac_of_f16_peak": exec_tflops / F16_MFMA_PEAK_TFLOPS,
-                        "vs_fp32_mfma_peak": trunk_tflops / FP32_MFMA_PEAK_TFLOPS, **common}
-        wire_b = c0.wire.nbytes
         out = {
             "metric": "candidate sites/sec (pileup+CNN)", "value": value, "unit": "sites/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
@@ -1471,40 +1424,146 @@ def main():
                                     if scaling == "strong" else "1 contig per GPU per step"),
                        "timed_region": "HBM-resident packs (--resident)" if args.resident else
                        "pinned host wire -> H2D (own stream, 3-slot ring) -> expand -> scan -> tensors -> CNN -> results in pinned host memory",
-                       "contigs_per_step": job_contigs if world > 1 else 1, "sites_per_contig": n_sites,
+                       "contigs_per_step": job_contigs if world > 1 else 1, "sites_per_step": total_sites // max(1, args.steps),
                        "pileup_entries_per_contig": c0.entries, "snp_weights": args.model,
                        "tensor_format": "int16 between featuriser and CNN (exact; fp32 with --cnn-precision fp32)", "generator": "synth_v1 seed 812+contig",
                        "setup_s": round(t_setup, 2), "data_gen_s": round(sum(c.gen_s for c in contigs), 2),
-                       "host_wire_build_s": round(sum(c.wire_s for c in contigs), 2)},
-            "roofline": roofline,
-            "h2d": {"wire_bytes_per_contig": wire_b, "bytes_per_pileup_entry": wire_b / c0.entries,
-                    "uncompressed_pack_bytes": c0.entries + L, "achieved_GBs": h2d_gbs, "pcie_peak_GBs": PCIE_PEAK_GBS,
-                    "copy_ms_per_contig": h2d_ms / max(1, len(uploader.h2d_events)), "copies_timed": len(uploader.h2d_events),
-                    "expand_ms": expand_ms, "expand_GBs_written": c0.wire.codes_len / (expand_ms * 1e-3) / 1e9,
-                    "note": "copies run on their own stream under the previous contig's compute; expansion is on the compute stream",
-                    "per_rank_achieved_GBs": [round(v[0], 2) for v in per_rank_h2d] if per_rank_h2d else None,
-                    "host_dram_read_GBs_all_ranks": (sum(v[1] for v in per_rank_h2d) / sum(dts)) / 1e9 if per_rank_h2d else None},
-            "three_numbers": {"kernels_only_sites_s": n_sites / ((stage_ms[0] + stage_ms[1] + stage_ms[2] + expand_ms) * 1e-3),
-                              "with_h2d_d2h_sites_s": value if not args.resident else None,
-                              "hbm_resident_with_d2h_sites_s": rs_sites / rs_dt,
-                              "end_to_end_incl_vcf_text_serial_sites_s": n_sites / ((dt / max(1, n_units) * 1e3 + vcf_ms) * 1e-3),
-                              "end_to_end_incl_vcf_text_pipelined_sites_s": pipe_sites / pipelined_dt,
-                              "vcf_text_ms": vcf_ms, "vcf_bytes": len(vcf),
-                              "note": "rank 0, per GPU; with_h2d_d2h = the timed region (= value at N=1); hbm_resident = the same passes over a pack "
-                                      "already in HBM (round 1's headline); pipelined = + VCF text of pass i formatted on a host thread while the "
-                                      "GPU runs pass i+1 (snpCaller.caller), uploads included"},
-            "indel_leg": indel_leg, "wgs_sharded": wgs_sharded,
+                       "host_wire_build_s": round(sum(c.wire_s for c in contigs), 2), "full": bool(args.full)},
             "numa": ({"rank0_bound": numa["bound"], "node": numa["node"], "cpus": len(numa["cpus"]) if numa["cpus"] else None, "note": numa["note"]} if numa else None),
             "range_guard": {"x_limit": eng.x_limit(_lib_kind(args.ploidy)), "sites_rerun_on_exact_trunk": int(r.get("range_reruns", 0)) if r else None,
                             "note": "fp16x3 trunk: sites whose scaled tensor exceeds the model's proven-safe input bound are re-run on the exact fp32 trunk "
                                     "(nc_cnn_range_watch); 0 = every result of the timed region is proven inside the fp16 range"},
-            "stages": {"expand_ms": expand_ms, "scan_ms": float(stage_ms[0]), "scan_GBs": scan_bytes / (stage_ms[0] * 1e-3) / 1e9 if stage_ms[0] else 0,
-                       "scan_frac_hbm": scan_bytes / (stage_ms[0] * 1e-3) / 1e9 / HBM_PEAK_GBS if stage_ms[0] else 0,
-                       "featurize_ms": float(stage_ms[1]),
-                       "featurize_GBs": feat_bytes / (stage_ms[1] * 1e-3) / 1e9 if stage_ms[1] else 0,
-                       "featurize_frac_hbm": feat_bytes / (stage_ms[1] * 1e-3) / 1e9 / HBM_PEAK_GBS if stage_ms[1] else 0,
-                       "cnn_ms": float(stage_ms[2]), "trunk_ms_per_contig": float(trunk_ms / max(1, n_units * len(dts)))},
         }
+        # ---- --full: everything beyond the headline, outside its timed region
+        if args.full:
+            # ---- the same units from HBM-resident packs (round 1's definition of the timed region), contig 0
+            rs_sites, rs_dt, r0 = measure(eng, uploader, contigs[:1], n_units, 1, params, chunks, local, lambda: None, not args.no_overlap, True)
+            n_sites = int(r0["n"])                          # sites of contig 0: the stage numbers below are per pass over it
+
+            def step():
+                return snpCaller.call_chunks(params, chunks, device=local, dpk=pack)
+            # stage breakdown (scan / featurize / CNN stage): event pairs around each stage put barrier packets on the stream,
+            # so they are taken in their own short loop after the timed region
+            eng.enable_timing(True)
+            for _ in range(min(3, args.steps)):
+                step()
+            s2, cnt = eng.timing_sums()
+            eng.enable_timing(False)
+            stage_ms = np.array([s2[0] / max(1, cnt[0]), s2[1] / max(1, cnt[1]), s2[2] / max(1, cnt[2])])
+            # expansion kernel alone
+            t = uploader.submit(c0.wire)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(3):
+                uploader.expand(t)
+            e1.record()
+            torch.cuda.synchronize()
+            uploader.release(t)
+            expand_ms = e0.elapsed_time(e1) / 3
+            # host genotype rules + VCF record text for one pass' results (native formatter), untimed above: the third number
+            # SURVEY.md 8(d) asks for (kernels only / + H2D + D2H / end to end incl. host K6 + VCF text)
+            tv = time.perf_counter()
+            vcf = snpCaller.snp_vcf_text("chr20", r0["pos"], r0["ref"], r0["probs"], r0["dp"], r0["freq"], r0["fwd_dp"], r0["rev_dp"],
+                                         haploid=(args.ploidy == "haploid"), as_array=True)
+            vcf_ms = (time.perf_counter() - tv) * 1e3
+            # the production loop (snpCaller.caller) formats contig i on a worker thread while the GPU runs contig i+1: measure
+            # that pipeline with the uploads inside
+            from concurrent.futures import ThreadPoolExecutor
+
+            scratch = np.empty((400 + 5) * max(n_sites, 1) * 5 // 4 + 65536, np.uint8)
+
+            def fmt(res):
+                return len(snpCaller.snp_vcf_text("chr20", res["pos"], res["ref"], res["probs"], res["dp"], res["freq"], res["fwd_dp"],
+                                                  res["rev_dp"], haploid=(args.ploidy == "haploid"), as_array=True, out=scratch))
+            with ThreadPoolExecutor(max_workers=1) as pool:
+                torch.cuda.synchronize()
+                tp = time.perf_counter()
+                pend, prev, pipe_sites = None, None, 0
+                nxt = uploader.submit(contigs[0].wire)
+                for i in range(n_units + 1):
+                    cur = None
+                    if i < n_units:
+                        tk = nxt
+                        dpk_i = uploader.expand(tk)
+                        nxt = uploader.submit(contigs[(i + 1) % len(contigs)].wire) if i + 1 < n_units else None
+                        cur = snpCaller.call_chunks(params, chunks, device=local, dpk=dpk_i, defer=True)
+                        uploader.release(tk)
+                    if prev is not None:
+                        res = prev.result()
+                        pipe_sites += int(res["n"])
+                        if pend is not None:
+                            pend.result()
+                        pend = pool.submit(fmt, res)
+                    prev = cur
+                pend.result()
+                pipelined_dt = time.perf_counter() - tp
+            sites_timed = n_sites_rank * len(dts)                          # this rank's sites inside ALL the timed regions (the trunk events span them)
+            cnn_tflops = SNP_FLOP_PER_SITE * n_sites / (stage_ms[2] * 1e-3) / 1e12 if stage_ms[2] > 0 else 0.0
+            # dominant kernel = fused conv1+conv2+conv3 trunk: algorithmic FLOP of its launches in the timed region / their
+            # summed HIP-event durations == FLOP per launch / average launch duration
+            n_launch = max(1.0, trunk_launches)
+            trunk_tflops = TRUNK_FLOP_PER_SITE * sites_timed / (trunk_ms * 1e-3) / 1e12 if trunk_ms > 0 else 0.0
+            scan_bytes = c0.entries + L                            # (d+1) B/column, SURVEY.md 8d
+            feat_bytes = (5403 - 2050) * n_sites                  # SURVEY.md 8d's 5,403 B/site with the tensor written as int16 (2,050 B) instead of fp32
+            tt = trunk_traffic_from_profiles()
+            traffic, stale_note = None, None
+            eng.set_tensor_format(int16=not exact_fp32)                # (as the timed region ran: which trunk kernel does this context launch?)
+            mfma_per_site, trunk_kernel = eng.trunk_info()
+            eng.set_tensor_format(int16=False)
+            if tt and tt.get("kernel") == trunk_kernel:
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                from build_tag import TRUNK_SOURCES
+                tag_ok, stale_note = traffic_build_check(tt, TRUNK_SOURCES)
+                if tag_ok:
+                    traffic = tt["bytes_per_site"] * sites_timed / n_launch
+            common = {"achieved": trunk_tflops, "unit": "TFLOP/s", "traffic": traffic,
+                      "traffic_note": ("HBM bytes per launch = bytes per site from the committed PMC passes (%s) x sites per launch of this run"
+                                       % tt.get("source", "profiles/trunk_traffic.json")) if traffic else (stale_note or "no PMC pass committed for this kernel build"),
+                      "launches_in_timed_region": n_launch, "avg_launch_ms": float(trunk_ms / n_launch),
+                      "flop_per_launch": TRUNK_FLOP_PER_SITE * sites_timed / n_launch,
+                      "cnn_stage_tflops": cnn_tflops, "cnn_stage_ms": float(stage_ms[2])}
+            if exact_fp32:
+                roofline = {"bound": "mfma", "kernel": "k4_conv12: fused conv1+conv2+conv3 of the SNP CNN, fp32 MFMA 16x16x4",
+                            "peak": FP32_MFMA_PEAK_TFLOPS, "frac": trunk_tflops / FP32_MFMA_PEAK_TFLOPS, **common}
+            else:
+                peak = F16_MFMA_PEAK_TFLOPS / 3.0
+                exec_tflops = mfma_per_site * 16384.0 * sites_timed / (trunk_ms * 1e-3) / 1e12 if trunk_ms > 0 else 0.0
+                roofline = {"bound": "mfma", "kernel": "%s: fused conv1+conv2+conv3 of the SNP CNN, three roles on three sites; f16 MFMA 16x16x32, f32 accumulate" % trunk_kernel,
+                            "kernel_note": "fp32-equivalent products as hi*hi + hi*lo + lo*hi (3 f16 products); k5_trunk_lin runs conv1 on the integer tensor entries "
+                                           "(exact in f16) with the coverage scale on the accumulators: 2 products there",
+                            "peak": peak, "peak_note": "dense f16 MFMA peak 2500 TF / 3 products per fp32-equivalent product",
+                            "frac": trunk_tflops / peak, "executed_mfma_per_site": mfma_per_site, "executed_f16_mfma_tflops": exec_tflops,
+                            "executed_frac_of_f16_peak": exec_tflops / F16_MFMA_PEAK_TFLOPS,
+                            "vs_fp32_mfma_peak": trunk_tflops / FP32_MFMA_PEAK_TFLOPS, **common}
+            wire_b = c0.wire.nbytes
+            out["config"]["sites_per_contig"] = n_sites              # sites of contig 0 (the HBM-resident pass)
+            out.update({
+                "roofline": roofline,
+                "h2d": {"wire_bytes_per_contig": wire_b, "bytes_per_pileup_entry": wire_b / c0.entries,
+                        "uncompressed_pack_bytes": c0.entries + L, "achieved_GBs": h2d_gbs, "pcie_peak_GBs": PCIE_PEAK_GBS,
+                        "copy_ms_per_contig": h2d_ms / max(1, len(uploader.h2d_events)), "copies_timed": len(uploader.h2d_events),
+                        "expand_ms": expand_ms, "expand_GBs_written": c0.wire.codes_len / (expand_ms * 1e-3) / 1e9,
+                        "note": "copies run on their own stream under the previous contig's compute; expansion is on the compute stream",
+                        "per_rank_achieved_GBs": [round(v[0], 2) for v in per_rank_h2d] if per_rank_h2d else None,
+                        "host_dram_read_GBs_all_ranks": (sum(v[1] for v in per_rank_h2d) / sum(dts)) / 1e9 if per_rank_h2d else None},
+                "three_numbers": {"kernels_only_sites_s": n_sites / ((stage_ms[0] + stage_ms[1] + stage_ms[2] + expand_ms) * 1e-3),
+                                  "with_h2d_d2h_sites_s": value if not args.resident else None,
+                                  "hbm_resident_with_d2h_sites_s": rs_sites / rs_dt,
+                                  "end_to_end_incl_vcf_text_serial_sites_s": n_sites / ((dt / max(1, n_units) * 1e3 + vcf_ms) * 1e-3),
+                                  "end_to_end_incl_vcf_text_pipelined_sites_s": pipe_sites / pipelined_dt,
+                                  "vcf_text_ms": vcf_ms, "vcf_bytes": len(vcf),
+                                  "note": "rank 0, per GPU; with_h2d_d2h = the timed region (= value at N=1); hbm_resident = the same passes over a pack "
+                                          "already in HBM (round 1's headline); pipelined = + VCF text of pass i formatted on a host thread while the "
+                                          "GPU runs pass i+1 (snpCaller.caller), uploads included"},
+                "indel_leg": indel_leg, "wgs_sharded": wgs_sharded,
+                "stages": {"expand_ms": expand_ms, "scan_ms": float(stage_ms[0]), "scan_GBs": scan_bytes / (stage_ms[0] * 1e-3) / 1e9 if stage_ms[0] else 0,
+                           "scan_frac_hbm": scan_bytes / (stage_ms[0] * 1e-3) / 1e9 / HBM_PEAK_GBS if stage_ms[0] else 0,
+                           "featurize_ms": float(stage_ms[1]),
+                           "featurize_GBs": feat_bytes / (stage_ms[1] * 1e-3) / 1e9 if stage_ms[1] else 0,
+                           "featurize_frac_hbm": feat_bytes / (stage_ms[1] * 1e-3) / 1e9 / HBM_PEAK_GBS if stage_ms[1] else 0,
+                           "cnn_ms": float(stage_ms[2]), "trunk_ms_per_contig": float(trunk_ms / max(1, n_units * len(dts)))},
+            })
         if wgs_sharded is not None:
             cfg = out["config"]
             if "error" in wgs_sharded:
@@ -1514,14 +1573,14 @@ def main():
                             "wgs_sharded_rank_imbalance": wgs_sharded["rank_imbalance_max_over_mean"], "wgs_sharded_scale": args.wgs_scale,
                             "wgs_sharded_h2d_GBs_min": min(wgs_sharded["rank_h2d_GBs"]), "wgs_sharded_h2d_GBs_max": max(wgs_sharded["rank_h2d_GBs"]),
                             "wgs_sharded_host_read_GBs": wgs_sharded["host_pinned_read_GBs_all_ranks"]})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_cpu = args.cpu_sample_chunks or len(chunks)
             cb, parity = cpu_baseline_processes(pack, c0.info, chunks, params, args.model, r0, n_cpu)
             out["cpu_baseline"] = cb
             out["parity"] = parity
             cbt, _ = cpu_baseline(pack, c0.info, chunks, params, args.model, r0, min(len(chunks), max(1, usable_cpus())))
             out["cpu_baseline"]["thread_variant"] = {"value": cbt["value"], "cores": cbt["cores"], "sample": cbt["sample"]}
-        if world == 1 and not args.no_configs2:
+        if args.full and world == 1 and not args.no_configs2:
             # BASELINE.json configs[2] as a first-class block of the line: chr1-sized SNP + indel, one timed region
             contigs.clear()
             c0 = pack = None
@@ -1544,7 +1603,7 @@ def main():
                             "configs2_frac_trunk": c2["snp_half"]["roofline"]["frac"], "configs2_frac_k9": c2["indel_half"]["roofline"]["frac"],
                             "configs2_frac_fill_issue_model": c2["indel_half"]["roofline_alignment"]["frac"],
                             "configs2_h2d_GBs": c2["h2d"]["achieved_GBs"], "configs2_wire_bytes": c2["h2d"]["bytes_per_step"]})
-        if world == 1 and not args.no_wgs:
+        if args.full and world == 1 and not args.no_wgs:
             # the metric's own configuration at N = 1: one pass over 24 contigs at GRCh38 lengths, both halves (scalars in `config` as well)
             contigs.clear()
             c0 = pack = None
@@ -1560,7 +1619,7 @@ def main():
             except Exception as e:
                 out["wgs_n1"] = {"error": "%s: %s" % (type(e).__name__, e)}
                 cfg["wgs_error"] = ("%s: %s" % (type(e).__name__, e))[:120]
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             # other configurations, outside the headline's timed region (BASELINE.json configs[4], the exact-fp32 trunk,
             # and the indel half of configs[2]); each with its own workload and roofline
             contigs.clear()

@@ -1,8 +1,9 @@
 """the drop-in boundary.  CPU-only: the reference's module / function / class names under `nanocaller_src`,
-`utils.get_regions_list`, the job structure and merges of `indelCaller.call_manager`, the reference's own `run(args)`
-(NanoCaller:12-56, executed from /root/reference when present -- build container only) against this package, the
+`utils.get_regions_list`, the job structure and merges of `indelCaller.call_manager`, what the reference's own `run(args)`
+(NanoCaller:12-56) handed this package (tests/golden/reference_run.json), the
 contig-keyed pack cache, and the rank -> GPU mapping of `snpCaller.call_manager` under a world_size-2 gloo run."""
 import gzip
+import json
 import os
 import queue
 import socket
@@ -16,7 +17,6 @@ import torch.multiprocessing as mp
 from tests import bamio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
 
 
 def test_reference_module_names_resolve_to_this_package():
@@ -58,7 +58,11 @@ def test_model_classes_accept_the_reference_weight_paths():
 @pytest.fixture(scope="module")
 def two_contig_files(tmp_path_factory):
     """one BAM with two contigs (different reads on each) + its FASTA"""
-    d = tmp_path_factory.mktemp("two")
+    return write_two_contig_files(tmp_path_factory.mktemp("two"))
+
+
+def write_two_contig_files(d):
+    """the two_contig_files fixture's files under directory `d` (also used by oracle/tools/make_run_golden.py)"""
     w1 = bamio.make_pass2_world(seed=3, length=30_000, depth=16)
     w2 = bamio.make_pass2_world(seed=4, length=22_000, depth=20)
     w1.chrom, w2.chrom = "chr1", "chrX"
@@ -68,7 +72,7 @@ def two_contig_files(tmp_path_factory):
             r["tid"] = tid
             r["name"] = "%s_%s" % (w.chrom, r["name"])
             recs.append(r)
-    bam, fa = str(d / "t.bam"), str(d / "t.fa")
+    bam, fa = os.path.join(str(d), "t.bam"), os.path.join(str(d), "t.fa")
     bamio.write_bam(bam, w1.chrom, w1.length, recs, other_refs=[(w2.chrom, w2.length)])
     bamio.write_fasta(fa, w1.chrom, w1.ref, extra=[(w2.chrom, w2.ref)])
     return w1, w2, bam, fa
@@ -212,35 +216,32 @@ def test_indel_call_manager_job_structure_and_merges(tmp_path, monkeypatch, mode
 
 
 # ------------------------------------------------------------------------------------------------- the reference's run(args)
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "NanoCaller")), reason="build container only (/root/reference)")
-def test_reference_run_function_drives_this_package(two_contig_files, tmp_path, monkeypatch):
-    """Load `run` from the reference's own NanoCaller script (its top-level imports of pysam / intervaltree satisfied by empty
-    stand-ins, `nanocaller_src` = this repo's alias package) and execute it: regions and chunks come from THIS package's
-    utils, and the dicts it hands to snpCaller.call_manager / indelCaller.call_manager carry every key this package reads."""
+def test_reference_run_function_drives_this_package(two_contig_files, tmp_path):
+    """What the reference's own `run` (NanoCaller:12-56, executed against this package on these files by
+    oracle/tools/make_run_golden.py) handed to snpCaller.call_manager / indelCaller.call_manager, kept as data in
+    tests/golden/reference_run.json: its regions and chunks are what THIS package's utils give for the same arguments, and
+    the dicts carry every key this package reads."""
     w1, w2, bam, fa = two_contig_files
     import nanocaller_src
     from nanocaller_src import indelCaller, snpCaller
-    for name in ("pysam", "intervaltree"):
-        if name not in sys.modules:
-            m = types.ModuleType(name)
-            m.Interval = m.IntervalTree = object
-            monkeypatch.setitem(sys.modules, name, m)
     assert sys.modules["nanocaller_src"] is nanocaller_src and nanocaller_src.__file__.startswith(ROOT)
-    src = open(os.path.join(REFERENCE, "NanoCaller")).read()
-    head = src[:src.index("if __name__ == '__main__':")]
-    ns = {"__file__": os.path.join(ROOT, "NanoCaller"), "__name__": "nanocaller_script"}
-    sys.dont_write_bytecode = True
-    exec(compile(head, "NanoCaller", "exec"), ns)
-    got = {}
-    monkeypatch.setattr(snpCaller, "call_manager", lambda p: got.setdefault("snp", p) and os.path.join(p["vcf_path"], "t.snps.vcf.gz"))
-    monkeypatch.setattr(indelCaller, "call_manager", lambda p: got.setdefault("indel", p) and {"snps": None, "indels": None, "final": None})
-    ns["run"](_args(bam, fa, str(tmp_path), mode="all", haploid_X=True))
+    text = open(os.path.join(ROOT, "tests", "golden", "reference_run.json")).read()
+    for ph, path in (("<bam>", bam), ("<ref>", fa), ("<output>", str(tmp_path))):
+        text = text.replace(ph, path)
+    got = json.loads(text)
     sp, ip = got["snp"], got["indel"]
-    assert sp["regions_list"] == (("chr1", 1, w1.length, "diploid"), ("chrX", 1, w2.length, "haploid"))
-    assert sp["chunks_list"] == nanocaller_src.utils.get_chunks(sp["regions_list"], 2)
-    assert ip["chunks_list"] == nanocaller_src.utils.get_chunks(sp["regions_list"], 2, max_chunk_size=100000)
+    a = _args(bam, fa, str(tmp_path), mode="all", haploid_X=True)
+    regions = nanocaller_src.utils.get_regions_list(a)
+    assert regions == (("chr1", 1, w1.length, "diploid"), ("chrX", 1, w2.length, "haploid"))
+
+    def as_json(v):
+        return json.loads(json.dumps(v))
+    assert sp["regions_list"] == ip["regions_list"] == as_json(regions)
+    assert sp["chunks_list"] == as_json(nanocaller_src.utils.get_chunks(regions, 2))
+    assert ip["chunks_list"] == as_json(nanocaller_src.utils.get_chunks(regions, 2, max_chunk_size=100000))
     assert snpCaller.PARAM_KEYS <= set(sp) and indelCaller.PARAM_KEYS <= set(ip)
-    assert ip["snp_vcf"].endswith("t.snps.vcf.gz") and ip["mode"] == "all"
+    assert sp["sam_path"] == ip["sam_path"] == bam and sp["fasta_path"] == ip["fasta_path"] == fa
+    assert ip["snp_vcf"] == os.path.join(str(tmp_path), "t.snps.vcf.gz") and ip["mode"] == "all"
 
 
 # ------------------------------------------------------------------------------------------------- rank -> GPU under gloo

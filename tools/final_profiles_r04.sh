@@ -5,7 +5,7 @@ set -x
 TAG=${1:-r04b}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profi_$TAG -o p -- python tools/bench_indel_pipe.py 64444167 4 > $O/${TAG}_indel_pipe.txt 2>/dev/null
 python tools/trim_rocprof.py $O/profi_$TAG/p_kernel_stats.csv $O/${TAG}_indel_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

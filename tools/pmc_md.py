@@ -48,7 +48,7 @@ out += table("pmci", it["passes"], "## Indel pipeline: `python tools/bench_indel
 out += ["", "Per stage (`profiles/indel_traffic.json`, bytes per candidate site: what `bench.py` reports as `traffic` of the indel stages):", ""]
 for s, v in sorted(it["stages"].items(), key=lambda kv: -kv[1]["bytes_per_site"]):
     out.append("* %s: %.1f KB read + %.1f KB written" % (s, v["read_bytes_per_site_corrected"] / 1e3, v["write_bytes_per_site"] / 1e3))
-out += table("pmc", snp_passes, "## SNP path: `python bench.py --no-extra --no-configs2 --no-cpu-baseline --steps 4 --warmup 1 --repeat 1` (%d contig passes of %d sites)"
+out += table("pmc", snp_passes, "## SNP path: `python bench.py --full --no-extra --no-configs2 --no-cpu-baseline --steps 4 --warmup 1 --repeat 1` (%d contig passes of %d sites)"
              % (snp_passes, tt["sites_per_pass"]), "contig pass")
 out += ["", "Dominant kernel `%s`: %.0f B/site read + %.0f B/site written = **%.0f B per site** (`profiles/trunk_traffic.json`; algorithmic 2,050 B int16 tensor in + 6,912 B of conv3 "
         "activations out)." % (tt["kernel"], tt["read_bytes_per_site_corrected"], tt["write_bytes_per_site"], tt["bytes_per_site"]),
