@@ -795,6 +795,49 @@ int nc_synth_indel_reads(nc_ctx *ctx, int64_t L, uint64_t seed, double p_sub, do
                          const int32_t *ev_off_dev, const int32_t *ins_off_read_dev, uint8_t *codes_dev, int32_t *ev_pos_dev,
                          int32_t *ev_len_dev, int32_t *ins_off_dev, uint8_t *ins_bases_dev);
 
+/* ------------------------------------------------------------------ read-based SNP phasing and haplotagging (csrc/nc_happhase.hip)
+ * Replaces the `whatshap phase` + `whatshap haplotag` steps of phase_run (nanocaller_src/indelCaller.py:192-262) with an exact
+ * minimum-error-correction phaser over the contig's resident pack (DESIGN.md "Read-based phasing": every step and tie-break).
+ * Sites: the het SNP calls of one contig, positions ascending strictly; site_alleles [n_sites][2] = base codes of the first and second
+ * allele (REF, ALT for 0/1; ALT1, ALT2 for 1/2).  A read's allele at a site: 0 / 1 when its code there is the first / second allele,
+ * none otherwise.
+ * nc_snp_phase_gather: the alleles of the kept reads of a resident pack (codes dev; rd_start / rd_end (exclusive) / slot_off dev, the
+ *   pack's read table: read r's code at position p is codes[slot_off[r] + (rd_start[r] & 15) + p - rd_start[r]]) -> a phasing handle
+ *   holding the read -> (site, allele) CSR, on the device and on the host.  Site arrays are host.
+ * nc_snp_phase_load: the same handle from a host CSR (entry_off [n_reads + 1], entry_site ascending per read, entry_allele 0 / 1).
+ * nc_snp_phase_solve: read selection (max_cov in [1, 15]), blocks, slots (host) and the DP (one workgroup per block).  NC_ERR_CAPACITY
+ *   when a partition cost exceeds the DP's 16-bit relative range.
+ * nc_haplotag_run: read_group [n_reads] (host) = name group 0 .. n_groups-1 of every read; scores of one name are summed -> HP / PS.
+ * nc_snp_phase_view: host views of the handle's arrays (valid until the next call on the handle or nc_snp_phase_free).
+ *   read_side: -1 not accepted, else the read's part (0 = HP 1); site_block: -1 outside blocks; site_h: allele carried by HP 1;
+ *   site_ps: 0 when unphased; group_hp 0 (untagged) / 1 / 2, group_ps 0 when untagged; ms: gather, selection, DP, haplotag wall times. */
+typedef struct nc_phase nc_phase;
+typedef struct {
+    int32_t n_reads, n_sites, n_blocks, n_groups;
+    int64_t n_entries;
+    const int64_t *entry_off;
+    const int32_t *entry_site;
+    const uint8_t *entry_allele;
+    const int8_t *read_side;
+    const int32_t *site_block;
+    const uint8_t *site_h;
+    const uint8_t *site_phased;
+    const int32_t *site_ps;
+    const int32_t *block_first, *block_last, *block_ps;
+    const int64_t *block_cost;
+    const uint8_t *group_hp;
+    const int32_t *group_ps;
+    float ms[4];
+} nc_phase_arrays;
+int nc_snp_phase_gather(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, int32_t n_reads, const int32_t *rd_start, const int32_t *rd_end,
+                        const int64_t *slot_off, int32_t n_sites, const int32_t *site_pos, const uint8_t *site_alleles, nc_phase **out);
+int nc_snp_phase_load(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32_t *site_pos, const int64_t *entry_off, const int32_t *entry_site,
+                      const uint8_t *entry_allele, nc_phase **out);
+int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov);
+int nc_haplotag_run(nc_ctx *ctx, nc_phase *ph, int32_t n_groups, const int32_t *read_group);
+int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out);
+int nc_snp_phase_free(nc_phase *ph);
+
 #ifdef __cplusplus
 }
 #endif

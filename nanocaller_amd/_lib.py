@@ -43,6 +43,7 @@ EXPORTS = [
     "nc_indel_pass2_sets", "nc_pass2_view", "nc_pass2_free",
     "nc_decoded_check", "nc_indel_pack_build", "nc_indel_pack_view", "nc_indel_pack_free", "nc_indel_sites_plan", "nc_indel_sites_run",
     "nc_indel_sites_fetch", "nc_indel_sites_fetch_alt", "nc_indel_sites_stage_ms", "nc_indel_sites_band_stats", "nc_indel_sites_band", "nc_indel_events_pack", "nc_indel_events_expand", "nc_inflate_device", "nc_inflate_device_phase", "nc_bgzf_crc_device", "nc_bgzf_members", "nc_bgzf_scan", "nc_bam_walk", "nc_bam_meta", "nc_bam_codes", "nc_bam_indel_reads", "nc_indel_sites_scoring", "nc_indel_vcf_format", "nc_synth_indel_truth", "nc_synth_indel_reads", "nc_cnn_x_limit", "nc_cnn_range_watch", "nc_snp_trunk_info",
+    "nc_snp_phase_gather", "nc_snp_phase_load", "nc_snp_phase_solve", "nc_haplotag_run", "nc_snp_phase_view", "nc_snp_phase_free",
 ]
 
 
@@ -110,6 +111,14 @@ class WireArraysC(C.Structure):
     _fields_ = [("n_reads", C.c_int32), ("rd_start", C.c_void_p), ("rd_end", C.c_void_p), ("slot_off", C.c_void_p),
                 ("codes_len", C.c_int64), ("n_blocks", C.c_int64), ("blk_off", C.c_void_p), ("blk_read", C.c_void_p), ("events", C.c_void_p),
                 ("n_events", C.c_int64), ("blk_ev", C.c_void_p), ("ev_bytes", C.c_void_p), ("n_ev_bytes", C.c_int64)]
+
+
+class PhaseArraysC(C.Structure):
+    _fields_ = [("n_reads", C.c_int32), ("n_sites", C.c_int32), ("n_blocks", C.c_int32), ("n_groups", C.c_int32), ("n_entries", C.c_int64),
+                ("entry_off", C.c_void_p), ("entry_site", C.c_void_p), ("entry_allele", C.c_void_p), ("read_side", C.c_void_p),
+                ("site_block", C.c_void_p), ("site_h", C.c_void_p), ("site_phased", C.c_void_p), ("site_ps", C.c_void_p),
+                ("block_first", C.c_void_p), ("block_last", C.c_void_p), ("block_ps", C.c_void_p), ("block_cost", C.c_void_p),
+                ("group_hp", C.c_void_p), ("group_ps", C.c_void_p), ("ms", C.c_float * 4)]
 
 
 _lib = None
@@ -245,6 +254,12 @@ def lib():
         L.nc_snp_trunk_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.nc_cnn_range_watch.argtypes = [vp, vp]
         L.nc_argsort4.argtypes = [vp, i64, vp, C.POINTER(i64), vp, i64]
+        L.nc_snp_phase_gather.argtypes = [vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, C.POINTER(vp)]
+        L.nc_snp_phase_load.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]
+        L.nc_snp_phase_solve.argtypes = [vp, vp, i32]
+        L.nc_haplotag_run.argtypes = [vp, vp, i32, vp]
+        L.nc_snp_phase_view.argtypes = [vp, C.POINTER(PhaseArraysC)]
+        L.nc_snp_phase_free.argtypes = [vp]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

@@ -1,0 +1,705 @@
+// Read-based SNP phasing (exact minimum-error-correction DP over at most 15 reads per column, WhatsHap's model) and read
+// haplotagging, on the contig's resident read pack.  DESIGN.md "Read-based phasing" states the algorithm; every tie-break below
+// is part of it (tests/phase_ref.py restates it in numpy and the GPU tests compare bit for bit).
+//
+//   k_hp_gather<false>  per read: the number of its alleles at the het sites (code == first / second allele)
+//   k_hp_scan           one workgroup: exclusive prefix of those counts (nc_wave_incl_scan) -> read -> entry offsets
+//   k_hp_gather<true>   per read: the (site, allele) CSR entries
+//   host                read selection (max_cov), blocks, slot assignment, per-column masks, backtrace offsets
+//   k_hp_dp             one workgroup per block: the 2^15 partition costs in LDS (uint16, relative to the column minimum),
+//                       leaving slots minimised out, backtrace in HBM, traceback by the same workgroup
+//   k_hp_tag            one thread per read-name group: per-block scores -> HP / PS
+#include "nc_common.h"
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <vector>
+
+namespace {
+
+constexpr int HP_SLOTS = 15;
+constexpr int HP_STATES = 1 << HP_SLOTS;
+constexpr int HP_THREADS = 1024;
+
+struct HpCol {            // one column of a block: the active slots, those continuing from the previous column, the allele masks
+    uint16_t act, keep, m0, m1;
+};
+
+__device__ __forceinline__ uint32_t hp_pdep(uint32_t t, uint32_t mask)
+{
+    uint32_t r = 0;
+    for (uint32_t m = mask; m; m &= m - 1) {
+        if (t & 1) r |= m & (0u - m);
+        t >>= 1;
+    }
+    return r;
+}
+
+__device__ __forceinline__ uint32_t hp_pext(uint32_t x, uint32_t mask)
+{
+    uint32_t r = 0;
+    int k = 0;
+    for (uint32_t m = mask; m; m &= m - 1, k++)
+        if (x & m & (0u - m)) r |= 1u << k;
+    return r;
+}
+
+__device__ __forceinline__ uint32_t hp_wave_min(uint32_t v)
+{
+    for (int o = 32; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+
+__device__ __forceinline__ int32_t hp_lower_bound(const int32_t *a, int32_t lo, int32_t hi, int32_t v)
+{
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one thread per kept read; codes of read r at position p: codes[slot_off[r] + (start & 15) + p - start]
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_hp_gather(const uint8_t *__restrict__ codes, int32_t n_reads, const int32_t *__restrict__ rs,
+                                                   const int32_t *__restrict__ re, const int64_t *__restrict__ slot_off, int32_t n_sites,
+                                                   const int32_t *__restrict__ spos, const uint8_t *__restrict__ sal, int32_t *__restrict__ cnt,
+                                                   const int64_t *__restrict__ off, int32_t *__restrict__ esite, uint8_t *__restrict__ eal)
+{
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const int32_t s0 = rs[r], s1 = re[r];
+    const int64_t base = slot_off[r] + (s0 & 15);
+    int32_t n = 0;
+    int64_t o = FILL ? off[r] : 0;
+    for (int32_t s = hp_lower_bound(spos, 0, n_sites, s0); s < n_sites && spos[s] < s1; s++) {
+        const uint8_t c = codes[base + (spos[s] - s0)];
+        const int a = c == sal[2 * s] ? 0 : (c == sal[2 * s + 1] ? 1 : -1);
+        if (a < 0) continue;
+        if (FILL) {
+            esite[o] = s;
+            eal[o] = (uint8_t)a;
+            o++;
+        } else {
+            n++;
+        }
+    }
+    if (!FILL) cnt[r] = n;
+}
+
+__global__ __launch_bounds__(HP_THREADS) void k_hp_scan(const int32_t *__restrict__ cnt, int32_t n, int64_t *__restrict__ off)
+{
+    __shared__ int32_t wsum[HP_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int64_t carry = 0;
+    if (tid == 0) off[0] = 0;
+    for (int32_t base = 0; base < n; base += HP_THREADS) {
+        const int32_t i = base + tid;
+        const int32_t inc = nc_wave_incl_scan(i < n ? cnt[i] : 0);
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        int32_t pre = 0, tot = 0;
+        for (int k = 0; k < HP_THREADS / 64; k++) {
+            const int32_t s = wsum[k];
+            pre += k < w ? s : 0;
+            tot += s;
+        }
+        if (i < n) off[i + 1] = carry + pre + inc;
+        carry += tot;
+        __syncthreads();
+    }
+}
+
+// One workgroup per block [bfirst, blast] of columns (= sites).  D(j, B) for the subsets B of the active slots lives in LDS as
+// uint16 relative to the column minimum (the minima are summed into the block's cost); P(b) for the subsets of the continuing
+// slots, the backtrace (smallest minimising bits of the leaving slots) per (column, continuing subset) in HBM at bt_off[column].
+__global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ cols, const int32_t *__restrict__ bfirst,
+                                                       const int32_t *__restrict__ blast, const int64_t *__restrict__ bt_off, uint16_t *__restrict__ bt,
+                                                       uint16_t *__restrict__ colB, uint8_t *__restrict__ colh, int64_t *__restrict__ bcost,
+                                                       int32_t *__restrict__ overflow)
+{
+    __shared__ uint16_t D[HP_STATES];
+    __shared__ uint16_t P[HP_STATES];
+    __shared__ uint32_t red[HP_THREADS];
+    __shared__ uint32_t smin;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int32_t c0 = bfirst[blockIdx.x], c1 = blast[blockIdx.x];
+    int64_t total = 0;
+    uint32_t prevA = 0;
+    for (int32_t j = c0; j <= c1; j++) {
+        const HpCol c = cols[j];
+        const uint32_t A = c.act, K = c.keep, m0 = c.m0, m1 = c.m1;
+        if (j > c0) {
+            const uint32_t Lm = prevA & ~K;
+            const int nk = __popc(K), nl = __popc(Lm);
+            const int32_t NT = 1 << nk, NU = 1 << nl;
+            uint16_t *btj = bt + bt_off[j];
+            if (NT >= HP_THREADS) {
+                for (int32_t t = tid; t < NT; t += HP_THREADS) {
+                    const uint32_t b = hp_pdep(t, K);
+                    uint32_t best = ~0u;
+                    for (int32_t u = 0; u < NU; u++) {
+                        const uint32_t x = hp_pdep(u, Lm);
+                        best = min(best, ((uint32_t)D[b | x] << 16) | x);
+                    }
+                    P[b] = (uint16_t)(best >> 16);
+                    btj[t] = (uint16_t)(best & 0xFFFF);
+                }
+            } else {
+                // fewer continuing subsets than threads: G = 1024 / NT threads share one subset's leaving-slot loop
+                const int32_t t = tid & (NT - 1), g = tid >> nk, G = HP_THREADS >> nk;
+                if (tid < NT) red[tid] = ~0u;
+                __syncthreads();
+                const uint32_t b = hp_pdep(t, K);
+                uint32_t best = ~0u;
+                for (int32_t u = g; u < NU; u += G) {
+                    const uint32_t x = hp_pdep(u, Lm);
+                    best = min(best, ((uint32_t)D[b | x] << 16) | x);
+                }
+                if (best != ~0u) atomicMin(&red[t], best);
+                __syncthreads();
+                if (tid < NT) {
+                    P[hp_pdep(tid, K)] = (uint16_t)(red[tid] >> 16);
+                    btj[tid] = (uint16_t)(red[tid] & 0xFFFF);
+                }
+            }
+        }
+        if (tid == 0) smin = ~0u;
+        __syncthreads();
+        const int32_t NA = 1 << __popc(A);
+        const bool first = j == c0;
+        uint32_t mn = ~0u;
+        for (int32_t t = tid; t < NA; t += HP_THREADS) {
+            const uint32_t B = hp_pdep(t, A);
+            const uint32_t e0 = __popc(m1 & ~B) + __popc(m0 & B), e1 = __popc(m0 & ~B) + __popc(m1 & B);
+            mn = min(mn, (first ? 0u : (uint32_t)P[B & K]) + min(e0, e1));
+        }
+        mn = hp_wave_min(mn);
+        if (lane == 0 && mn != ~0u) atomicMin(&smin, mn);
+        __syncthreads();
+        const uint32_t cmin = smin;
+        for (int32_t t = tid; t < NA; t += HP_THREADS) {
+            const uint32_t B = hp_pdep(t, A);
+            const uint32_t e0 = __popc(m1 & ~B) + __popc(m0 & B), e1 = __popc(m0 & ~B) + __popc(m1 & B);
+            const uint32_t v = (first ? 0u : (uint32_t)P[B & K]) + min(e0, e1) - cmin;
+            if (v > 0xFFFFu) atomicOr(overflow, 1);
+            D[B] = (uint16_t)min(v, 0xFFFFu);
+        }
+        total += cmin;
+        prevA = A;
+        __syncthreads();
+    }
+    // the smallest B among the minima of the last column (its minimum is 0 after the shift)
+    if (tid == 0) smin = ~0u;
+    __syncthreads();
+    {
+        const uint32_t A = cols[c1].act;
+        const int32_t NA = 1 << __popc(A);
+        uint32_t mn = ~0u;
+        for (int32_t t = tid; t < NA; t += HP_THREADS) {
+            const uint32_t B = hp_pdep(t, A);
+            mn = min(mn, ((uint32_t)D[B] << 16) | B);
+        }
+        mn = hp_wave_min(mn);
+        if (lane == 0 && mn != ~0u) atomicMin(&smin, mn);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t B = smin & 0xFFFF;
+        for (int32_t j = c1; j >= c0; j--) {
+            const HpCol c = cols[j];
+            const uint32_t e0 = __popc(c.m1 & ~B) + __popc(c.m0 & B), e1 = __popc(c.m0 & ~B) + __popc(c.m1 & B);
+            colB[j] = (uint16_t)B;
+            colh[j] = e0 <= e1 ? 0 : 1;
+            if (j > c0) {
+                const uint32_t bk = B & c.keep;
+                B = bk | bt[bt_off[j] + hp_pext(bk, c.keep)];
+            }
+        }
+        bcost[blockIdx.x] = total;
+    }
+}
+
+// sblk: block of a PHASED site, -1 otherwise (sites are contiguous per block: a read's entries of one block form one run)
+__device__ void hp_block_score(int32_t r, int32_t b, const int64_t *off, const int32_t *esite, const uint8_t *eal, const int32_t *sblk,
+                               const uint8_t *sh, const int32_t *bfirst, const int32_t *blast, int32_t &n, int32_t &s)
+{
+    const int64_t e0 = off[r], e1 = off[r + 1];
+    int64_t lo = e0, hi = e1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (esite[mid] < bfirst[b]) lo = mid + 1;
+        else hi = mid;
+    }
+    for (int64_t e = lo; e < e1 && esite[e] <= blast[b]; e++) {
+        const int32_t site = esite[e];
+        if (sblk[site] != b) continue;
+        n++;
+        s += eal[e] == sh[site] ? 1 : -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hp_tag(int32_t n_groups, const int32_t *__restrict__ goff, const int32_t *__restrict__ greads,
+                                                const int64_t *__restrict__ off, const int32_t *__restrict__ esite, const uint8_t *__restrict__ eal,
+                                                const int32_t *__restrict__ sblk, const uint8_t *__restrict__ sh, const int32_t *__restrict__ bfirst,
+                                                const int32_t *__restrict__ blast, const int32_t *__restrict__ bps, uint8_t *__restrict__ ghp,
+                                                int32_t *__restrict__ gps)
+{
+    const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    int32_t best_n = 0, best_s = 0, best_ps = INT_MAX;
+    for (int32_t ia = goff[g]; ia < goff[g + 1]; ia++) {
+        const int32_t r = greads[ia];
+        for (int64_t e = off[r]; e < off[r + 1];) {
+            const int32_t b = sblk[esite[e]];
+            if (b < 0) {
+                e++;
+                continue;
+            }
+            while (e < off[r + 1] && esite[e] <= blast[b]) e++;          // the rest of the read's run in block b
+            bool seen = false;                                          // scored already from an earlier alignment of the name
+            for (int32_t ib = goff[g]; ib < ia && !seen; ib++) {
+                int32_t n = 0, s = 0;
+                hp_block_score(greads[ib], b, off, esite, eal, sblk, sh, bfirst, blast, n, s);
+                seen = n > 0;
+            }
+            if (seen) continue;
+            int32_t n = 0, s = 0;
+            for (int32_t ib = goff[g]; ib < goff[g + 1]; ib++) hp_block_score(greads[ib], b, off, esite, eal, sblk, sh, bfirst, blast, n, s);
+            if (n > best_n || (n == best_n && bps[b] < best_ps)) {
+                best_n = n;
+                best_s = s;
+                best_ps = bps[b];
+            }
+        }
+    }
+    const uint8_t hp = best_n == 0 || best_s == 0 ? 0 : (best_s > 0 ? 1 : 2);
+    ghp[g] = hp;
+    gps[g] = hp ? best_ps : 0;
+}
+
+double hp_now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+}  // namespace
+
+struct nc_phase {
+    nc_ctx *ctx = nullptr;
+    int32_t n_reads = 0, n_sites = 0, n_groups = 0;
+    std::vector<int32_t> site_pos;
+    std::vector<int64_t> off;
+    std::vector<int32_t> esite;
+    std::vector<uint8_t> eal;
+    int64_t *d_off = nullptr;
+    int32_t *d_site = nullptr;
+    uint8_t *d_al = nullptr;
+    std::vector<int8_t> side;
+    std::vector<int32_t> site_block, site_ps, block_first, block_last, block_ps;
+    std::vector<uint8_t> site_h, site_phased, group_hp;
+    std::vector<int64_t> block_cost;
+    std::vector<int32_t> group_ps;
+    float ms[4] = {0, 0, 0, 0};
+    bool solved = false;
+};
+
+static void hp_free_dev(nc_phase *ph)
+{
+    if (ph->d_off) (void)hipFree(ph->d_off);
+    if (ph->d_site) (void)hipFree(ph->d_site);
+    if (ph->d_al) (void)hipFree(ph->d_al);
+    ph->d_off = nullptr;
+    ph->d_site = nullptr;
+    ph->d_al = nullptr;
+}
+
+// device scratch of one call, released on every return path
+struct HpScratch {
+    std::vector<void *> p;
+    ~HpScratch()
+    {
+        for (void *q : p) (void)hipFree(q);
+    }
+    template <class T>
+    int get(nc_ctx *ctx, T **out, size_t n)
+    {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, n * sizeof(T) + 16);
+        if (e != hipSuccess) return nc_fail(ctx, NC_ERR_NOMEM, "hipMalloc(%zu) failed: %s", n * sizeof(T), hipGetErrorString(e));
+        p.push_back(q);
+        *out = (T *)q;
+        return NC_OK;
+    }
+};
+
+static int hp_upload_csr(nc_phase *ph)
+{
+    nc_ctx *ctx = ph->ctx;
+    const int64_t ne = ph->off[ph->n_reads];
+    NC_HIP(ctx, hipMalloc(&ph->d_off, (ph->n_reads + 1) * sizeof(int64_t)));
+    NC_HIP(ctx, hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16));
+    NC_HIP(ctx, hipMalloc(&ph->d_al, ne + 16));
+    NC_HIP(ctx, hipMemcpyAsync(ph->d_off, ph->off.data(), (ph->n_reads + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (ne) {
+        NC_HIP(ctx, hipMemcpyAsync(ph->d_site, ph->esite.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(ph->d_al, ph->eal.data(), ne, hipMemcpyHostToDevice, ctx->stream));
+    }
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NC_OK;
+}
+
+static int hp_check_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *pos)
+{
+    for (int32_t s = 1; s < n_sites; s++)
+        if (pos[s] <= pos[s - 1]) return nc_fail(ctx, NC_ERR_ARG, "phasing sites must ascend strictly (site %d)", s);
+    return NC_OK;
+}
+
+extern "C" {
+
+int nc_snp_phase_gather(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, int32_t n_reads, const int32_t *rd_start, const int32_t *rd_end,
+                        const int64_t *slot_off, int32_t n_sites, const int32_t *site_pos, const uint8_t *site_alleles, nc_phase **out)
+{
+    if (!ctx || !out || n_reads < 0 || n_sites < 0 || (n_reads && (!codes || !rd_start || !rd_end || !slot_off)) || (n_sites && (!site_pos || !site_alleles)))
+        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_gather: bad argument");
+    (void)codes_len;
+    *out = nullptr;
+    NC_TRY(hp_check_sites(ctx, n_sites, site_pos));
+    const double t0 = hp_now_ms();
+    nc_phase *ph = new nc_phase();
+    ph->ctx = ctx;
+    ph->n_reads = n_reads;
+    ph->n_sites = n_sites;
+    ph->site_pos.assign(site_pos, site_pos + n_sites);
+    ph->off.assign(n_reads + 1, 0);
+    int rc = NC_OK;
+    {
+        HpScratch sc;
+        int32_t *d_spos = nullptr, *d_cnt = nullptr;
+        uint8_t *d_sal = nullptr;
+        auto hip = [&](hipError_t e, const char *what) {
+            if (e != hipSuccess && rc == NC_OK) rc = nc_fail(ctx, NC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        };
+        if ((rc = sc.get(ctx, &d_spos, n_sites + 1)) || (rc = sc.get(ctx, &d_sal, 2 * (size_t)n_sites + 2)) || (rc = sc.get(ctx, &d_cnt, n_reads + 1))) {
+            nc_snp_phase_free(ph);
+            return rc;
+        }
+        hip(hipMalloc(&ph->d_off, (n_reads + 1) * sizeof(int64_t)), "hipMalloc(offsets)");
+        if (n_sites && rc == NC_OK) {
+            hip(hipMemcpyAsync(d_spos, site_pos, n_sites * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "site upload");
+            hip(hipMemcpyAsync(d_sal, site_alleles, 2 * (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream), "allele upload");
+        }
+        const int nb = (n_reads + 255) / 256;
+        if (n_reads && rc == NC_OK) {
+            k_hp_gather<false><<<nb, 256, 0, ctx->stream>>>(codes, n_reads, rd_start, rd_end, slot_off, n_sites, d_spos, d_sal, d_cnt, nullptr, nullptr, nullptr);
+            hip(hipGetLastError(), "k_hp_gather (count)");
+        }
+        if (rc == NC_OK) {
+            k_hp_scan<<<1, HP_THREADS, 0, ctx->stream>>>(d_cnt, n_reads, ph->d_off);
+            hip(hipGetLastError(), "k_hp_scan");
+            hip(hipMemcpyAsync(ph->off.data(), ph->d_off, (n_reads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream), "offset download");
+            hip(hipStreamSynchronize(ctx->stream), "gather sync");
+        }
+        const int64_t ne = rc == NC_OK ? ph->off[n_reads] : 0;
+        if (rc == NC_OK) {
+            hip(hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16), "hipMalloc(entries)");
+            hip(hipMalloc(&ph->d_al, ne + 16), "hipMalloc(alleles)");
+        }
+        if (rc == NC_OK && n_reads) {
+            k_hp_gather<true><<<nb, 256, 0, ctx->stream>>>(codes, n_reads, rd_start, rd_end, slot_off, n_sites, d_spos, d_sal, nullptr, ph->d_off, ph->d_site, ph->d_al);
+            hip(hipGetLastError(), "k_hp_gather (fill)");
+        }
+        if (rc == NC_OK) {
+            ph->esite.resize(ne);
+            ph->eal.resize(ne);
+            if (ne) {
+                hip(hipMemcpyAsync(ph->esite.data(), ph->d_site, ne * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream), "entry download");
+                hip(hipMemcpyAsync(ph->eal.data(), ph->d_al, ne, hipMemcpyDeviceToHost, ctx->stream), "allele download");
+            }
+            hip(hipStreamSynchronize(ctx->stream), "gather sync");
+        }
+    }
+    if (rc != NC_OK) {
+        nc_snp_phase_free(ph);
+        return rc;
+    }
+    ph->ms[0] = (float)(hp_now_ms() - t0);
+    *out = ph;
+    return NC_OK;
+}
+
+int nc_snp_phase_load(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32_t *site_pos, const int64_t *entry_off, const int32_t *entry_site,
+                      const uint8_t *entry_allele, nc_phase **out)
+{
+    if (!ctx || !out || n_reads < 0 || n_sites < 0 || !entry_off || (n_sites && !site_pos)) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: bad argument");
+    *out = nullptr;
+    NC_TRY(hp_check_sites(ctx, n_sites, site_pos));
+    if (entry_off[0] != 0) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: entry_off[0] != 0");
+    for (int32_t r = 0; r < n_reads; r++) {
+        if (entry_off[r + 1] < entry_off[r]) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: offsets descend at read %d", r);
+        for (int64_t e = entry_off[r]; e < entry_off[r + 1]; e++)
+            if (entry_site[e] < 0 || entry_site[e] >= n_sites || entry_allele[e] > 1 || (e > entry_off[r] && entry_site[e] <= entry_site[e - 1]))
+                return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: read %d: sites must ascend inside [0, n_sites), alleles 0 / 1", r);
+    }
+    nc_phase *ph = new nc_phase();
+    ph->ctx = ctx;
+    ph->n_reads = n_reads;
+    ph->n_sites = n_sites;
+    ph->site_pos.assign(site_pos, site_pos + n_sites);
+    ph->off.assign(entry_off, entry_off + n_reads + 1);
+    ph->esite.assign(entry_site, entry_site + entry_off[n_reads]);
+    ph->eal.assign(entry_allele, entry_allele + entry_off[n_reads]);
+    const int rc = hp_upload_csr(ph);
+    if (rc != NC_OK) {
+        nc_snp_phase_free(ph);
+        return rc;
+    }
+    *out = ph;
+    return NC_OK;
+}
+
+int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
+{
+    if (!ctx || !ph || max_cov < 1 || max_cov > HP_SLOTS) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_solve: max_cov must lie in [1, %d]", HP_SLOTS);
+    const double t0 = hp_now_ms();
+    const int32_t R = ph->n_reads, S = ph->n_sites;
+    const std::vector<int64_t> &off = ph->off;
+    const std::vector<int32_t> &es = ph->esite;
+    // read selection: most informative sites first, then the first site, then the read index
+    std::vector<int32_t> order;
+    for (int32_t r = 0; r < R; r++)
+        if (off[r + 1] - off[r] >= 2) order.push_back(r);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        const int64_t na = off[a + 1] - off[a], nb = off[b + 1] - off[b];
+        if (na != nb) return na > nb;
+        if (es[off[a]] != es[off[b]]) return es[off[a]] < es[off[b]];
+        return a < b;
+    });
+    std::vector<int32_t> cov(S, 0);
+    std::vector<uint8_t> acc(R, 0);
+    for (int32_t r : order) {
+        const int32_t a = es[off[r]], b = es[off[r + 1] - 1];
+        bool ok = true;
+        for (int32_t s = a; s <= b && ok; s++) ok = cov[s] < max_cov;
+        if (!ok) continue;
+        for (int32_t s = a; s <= b; s++) cov[s]++;
+        acc[r] = 1;
+    }
+    // blocks: consecutive sites share a block when an accepted span covers both
+    std::vector<int32_t> link(S + 1, 0);
+    std::vector<int32_t> starts_at(S + 1, 0), ends_at(S + 1, 0);
+    std::vector<std::vector<int32_t>> enter(S);
+    for (int32_t r = 0; r < R; r++) {
+        if (!acc[r]) continue;
+        const int32_t a = es[off[r]], b = es[off[r + 1] - 1];
+        link[a]++;
+        link[b]--;                                   // link[i] > 0 after the prefix: sites i and i + 1 joined
+        enter[a].push_back(r);                       // read-index order (r ascends)
+    }
+    ph->site_block.assign(S, -1);
+    ph->site_h.assign(S, 0);
+    ph->site_phased.assign(S, 0);
+    ph->site_ps.assign(S, 0);
+    ph->side.assign(R, -1);
+    ph->block_first.clear();
+    ph->block_last.clear();
+    ph->block_ps.clear();
+    for (int32_t s = 1; s <= S; s++) link[s] += link[s - 1];
+    for (int32_t s = 0; s < S;) {
+        if (link[s] <= 0) {
+            s++;
+            continue;
+        }
+        int32_t e = s;
+        while (e < S && link[e] > 0) e++;            // sites s .. e form a block
+        ph->block_first.push_back(s);
+        ph->block_last.push_back(e);
+        s = e + 1;
+    }
+    const int32_t nblk = (int32_t)ph->block_first.size();
+    // slots and the per-column masks
+    std::vector<HpCol> cols(S + 1, HpCol{0, 0, 0, 0});
+    std::vector<int8_t> slot(R, -1);
+    std::vector<std::vector<int32_t>> ending(S);
+    for (int32_t bi = 0; bi < nblk; bi++) {
+        uint32_t freem = (1u << HP_SLOTS) - 1, act = 0;
+        for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi]; c++) {
+            ph->site_block[c] = bi;
+            if (c > ph->block_first[bi])
+                for (int32_t r : ending[c - 1]) {
+                    freem |= 1u << slot[r];
+                    act &= ~(1u << slot[r]);
+                }
+            uint32_t entering = 0;
+            for (int32_t r : enter[c]) {
+                if (!freem) return nc_fail(ctx, NC_ERR_STATE, "nc_snp_phase_solve: more than %d reads active", HP_SLOTS);
+                const int sl = __builtin_ctz(freem);
+                freem &= freem - 1;
+                slot[r] = (int8_t)sl;
+                entering |= 1u << sl;
+                ending[es[off[r + 1] - 1]].push_back(r);
+            }
+            act |= entering;
+            cols[c].act = (uint16_t)act;
+            cols[c].keep = (uint16_t)(act & ~entering);
+        }
+    }
+    for (int32_t r = 0; r < R; r++) {
+        if (!acc[r]) continue;
+        for (int64_t e = off[r]; e < off[r + 1]; e++) {
+            const int32_t c = es[e];
+            (ph->eal[e] ? cols[c].m1 : cols[c].m0) |= (uint16_t)(1u << slot[r]);
+            ph->site_phased[c] = 1;
+        }
+    }
+    std::vector<int64_t> bt_off(S + 1, 0);
+    int64_t bt_total = 0;
+    for (int32_t bi = 0; bi < nblk; bi++)
+        for (int32_t c = ph->block_first[bi] + 1; c <= ph->block_last[bi]; c++) {
+            bt_off[c] = bt_total;
+            bt_total += 1ll << __builtin_popcount(cols[c].keep);
+        }
+    ph->ms[1] = (float)(hp_now_ms() - t0);
+    const double t1 = hp_now_ms();
+    std::vector<uint16_t> colB(S + 1, 0);
+    std::vector<uint8_t> colh(S + 1, 0);
+    ph->block_cost.assign(nblk, 0);
+    int32_t overflow = 0;
+    if (nblk) {
+        HpScratch sc;
+        HpCol *d_cols = nullptr;
+        int32_t *d_bf = nullptr, *d_bl = nullptr, *d_ovf = nullptr;
+        int64_t *d_bto = nullptr, *d_cost = nullptr;
+        uint16_t *d_bt = nullptr, *d_colB = nullptr;
+        uint8_t *d_colh = nullptr;
+        NC_TRY(sc.get(ctx, &d_cols, S + 1));
+        NC_TRY(sc.get(ctx, &d_bf, nblk));
+        NC_TRY(sc.get(ctx, &d_bl, nblk));
+        NC_TRY(sc.get(ctx, &d_ovf, 1));
+        NC_TRY(sc.get(ctx, &d_bto, S + 1));
+        NC_TRY(sc.get(ctx, &d_cost, nblk));
+        NC_TRY(sc.get(ctx, &d_bt, bt_total + 1));
+        NC_TRY(sc.get(ctx, &d_colB, S + 1));
+        NC_TRY(sc.get(ctx, &d_colh, S + 1));
+        NC_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (S + 1) * sizeof(HpCol), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_bf, ph->block_first.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_bl, ph->block_last.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_bto, bt_off.data(), (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemsetAsync(d_ovf, 0, sizeof(int32_t), ctx->stream));
+        k_hp_dp<<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf);
+        NC_HIP(ctx, hipGetLastError());
+        NC_HIP(ctx, hipMemcpyAsync(colB.data(), d_colB, (S + 1) * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(colh.data(), d_colh, S + 1, hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(ph->block_cost.data(), d_cost, nblk * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(&overflow, d_ovf, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (overflow) return nc_fail(ctx, NC_ERR_CAPACITY, "nc_snp_phase_solve: a partition cost exceeds 65535 above its column's minimum");
+    for (int32_t s = 0; s < S; s++) ph->site_h[s] = ph->site_block[s] >= 0 ? colh[s] : 0;
+    for (int32_t bi = 0; bi < nblk; bi++) {
+        int32_t ps = 0;
+        for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi] && !ps; c++)
+            if (ph->site_phased[c]) ps = ph->site_pos[c];
+        ph->block_ps.push_back(ps);
+        for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi]; c++)
+            if (ph->site_phased[c]) ph->site_ps[c] = ps;
+    }
+    for (int32_t r = 0; r < R; r++)
+        if (acc[r]) ph->side[r] = (int8_t)((colB[es[off[r]]] >> slot[r]) & 1);
+    ph->ms[2] = (float)(hp_now_ms() - t1);
+    ph->solved = true;
+    return NC_OK;
+}
+
+int nc_haplotag_run(nc_ctx *ctx, nc_phase *ph, int32_t n_groups, const int32_t *read_group)
+{
+    if (!ctx || !ph || n_groups < 0 || (ph->n_reads && !read_group)) return nc_fail(ctx, NC_ERR_ARG, "nc_haplotag_run: bad argument");
+    if (!ph->solved) return nc_fail(ctx, NC_ERR_STATE, "nc_haplotag_run before nc_snp_phase_solve");
+    const double t0 = hp_now_ms();
+    const int32_t R = ph->n_reads, S = ph->n_sites, nblk = (int32_t)ph->block_first.size();
+    std::vector<int32_t> goff(n_groups + 2, 0), greads(R + 1, 0);
+    for (int32_t r = 0; r < R; r++) {
+        if (read_group[r] < 0 || read_group[r] >= n_groups) return nc_fail(ctx, NC_ERR_ARG, "nc_haplotag_run: read %d: group out of range", r);
+        goff[read_group[r] + 1]++;
+    }
+    for (int32_t g = 0; g < n_groups; g++) goff[g + 1] += goff[g];
+    {
+        std::vector<int32_t> fill(goff.begin(), goff.end() - 1);
+        for (int32_t r = 0; r < R; r++) greads[fill[read_group[r]]++] = r;
+    }
+    std::vector<int32_t> sblk(S + 1, -1);
+    for (int32_t s = 0; s < S; s++)
+        if (ph->site_phased[s]) sblk[s] = ph->site_block[s];
+    ph->n_groups = n_groups;
+    ph->group_hp.assign(n_groups, 0);
+    ph->group_ps.assign(n_groups, 0);
+    if (n_groups && nblk) {
+        if (!ph->d_off) NC_TRY(hp_upload_csr(ph));
+        HpScratch sc;
+        int32_t *d_goff = nullptr, *d_gr = nullptr, *d_sblk = nullptr, *d_bf = nullptr, *d_bl = nullptr, *d_bps = nullptr, *d_gps = nullptr;
+        uint8_t *d_sh = nullptr, *d_ghp = nullptr;
+        NC_TRY(sc.get(ctx, &d_goff, n_groups + 1));
+        NC_TRY(sc.get(ctx, &d_gr, R + 1));
+        NC_TRY(sc.get(ctx, &d_sblk, S + 1));
+        NC_TRY(sc.get(ctx, &d_sh, S + 1));
+        NC_TRY(sc.get(ctx, &d_bf, nblk));
+        NC_TRY(sc.get(ctx, &d_bl, nblk));
+        NC_TRY(sc.get(ctx, &d_bps, nblk));
+        NC_TRY(sc.get(ctx, &d_ghp, n_groups));
+        NC_TRY(sc.get(ctx, &d_gps, n_groups));
+        NC_HIP(ctx, hipMemcpyAsync(d_goff, goff.data(), (n_groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_gr, greads.data(), (R + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_sblk, sblk.data(), (S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (S) NC_HIP(ctx, hipMemcpyAsync(d_sh, ph->site_h.data(), S, hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_bf, ph->block_first.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_bl, ph->block_last.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_bps, ph->block_ps.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        k_hp_tag<<<(n_groups + 255) / 256, 256, 0, ctx->stream>>>(n_groups, d_goff, d_gr, ph->d_off, ph->d_site, ph->d_al, d_sblk, d_sh, d_bf, d_bl, d_bps,
+                                                                 d_ghp, d_gps);
+        NC_HIP(ctx, hipGetLastError());
+        NC_HIP(ctx, hipMemcpyAsync(ph->group_hp.data(), d_ghp, n_groups, hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(ph->group_ps.data(), d_gps, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ph->ms[3] = (float)(hp_now_ms() - t0);
+    return NC_OK;
+}
+
+int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out)
+{
+    if (!ph || !out) return NC_ERR_ARG;
+    out->n_reads = ph->n_reads;
+    out->n_sites = ph->n_sites;
+    out->n_blocks = (int32_t)ph->block_first.size();
+    out->n_groups = ph->n_groups;
+    out->n_entries = ph->off.empty() ? 0 : ph->off[ph->n_reads];
+    out->entry_off = ph->off.data();
+    out->entry_site = ph->esite.data();
+    out->entry_allele = ph->eal.data();
+    out->read_side = ph->solved ? ph->side.data() : nullptr;
+    out->site_block = ph->solved ? ph->site_block.data() : nullptr;
+    out->site_h = ph->solved ? ph->site_h.data() : nullptr;
+    out->site_phased = ph->solved ? ph->site_phased.data() : nullptr;
+    out->site_ps = ph->solved ? ph->site_ps.data() : nullptr;
+    out->block_first = ph->block_first.data();
+    out->block_last = ph->block_last.data();
+    out->block_ps = ph->block_ps.data();
+    out->block_cost = ph->block_cost.data();
+    out->group_hp = ph->group_hp.data();
+    out->group_ps = ph->group_ps.data();
+    for (int k = 0; k < 4; k++) out->ms[k] = ph->ms[k];
+    return NC_OK;
+}
+
+int nc_snp_phase_free(nc_phase *ph)
+{
+    if (!ph) return NC_OK;
+    hp_free_dev(ph);
+    delete ph;
+    return NC_OK;
+}
+
+}  // extern "C"

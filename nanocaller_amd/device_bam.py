@@ -488,8 +488,9 @@ class DeviceBam:
         return out
 
     # ------------------------------------------------------------------ one contig: the host's decisions
-    def prepare(self, chrom, ref, supplementary=False, exclude=None, span=None, tile_size=2048):
-        """host half (numpy + native, no GPU call: may run on a worker thread).  ref: the contig's sequence.  -> dict for pack()"""
+    def prepare(self, chrom, ref, supplementary=False, exclude=None, span=None, tile_size=2048, haplotags=None):
+        """host half (numpy + native, no GPU call: may run on a worker thread).  ref: the contig's sequence.  haplotags: path of a haplotag
+        table (phase.save_haplotags) whose HP / PS replace the records' own tags, by read-name hash.  -> dict for pack()"""
         if not self.loaded:
             raise RuntimeError("DeviceBam.load() first")
         if chrom not in self.ref_names:
@@ -525,7 +526,12 @@ class DeviceBam:
             raise err
         filt = FLAG_FILTER_SUPPL if supplementary else FLAG_FILTER_DEFAULT
         keep = pileup_depth_cap(start, end, np.ascontiguousarray((flag & filt) == 0, np.uint8))
-        strand = np.ascontiguousarray(((flag & 0x10) != 0).astype(np.uint8) | ((m[M_HAP][idx].astype(np.uint8) & 3) << 1))
+        if haplotags:
+            from .phase import tags_for_hashes
+            hap, ps = tags_for_hashes(h, haplotags)
+        else:
+            hap, ps = m[M_HAP][idx].astype(np.uint8), m[M_PS][idx]
+        strand = np.ascontiguousarray(((flag & 0x10) != 0).astype(np.uint8) | ((hap & 3) << 1))
         # tile index + slot layout (nc_pack_plan / nc_pack_fill, index only: what wire.build_wire does)
         L = _lib.lib()
         ref_bytes = np.frombuffer(ref.encode("ascii") if isinstance(ref, str) else ref, np.uint8)
@@ -559,8 +565,8 @@ class DeviceBam:
         ga, gb = max(1, tile_pos0.value), min(Lref_b, tile_pos0.value + n_tiles.value * tile_size - 1)
         parts = dict(rec=np.ascontiguousarray(self.rec_off[a + idx[kk]]), slot=slot, cigd=np.ascontiguousarray(mk[M_CIGD]),
                      ncig=ncig.astype(np.uint32).view(np.int32), start=np.ascontiguousarray(ks), rd_end=np.ascontiguousarray(ke),
-                     slot_off=np.concatenate([slot, [int(size.sum())]]).astype(np.int64), read_hap=np.ascontiguousarray(mk[M_HAP].astype(np.uint8)),
-                     read_ps=np.ascontiguousarray(mk[M_PS]), read_flag=np.ascontiguousarray((mk[M_LSEQ] == 0).astype(np.uint8)), tile_off=tile_off,
+                     slot_off=np.concatenate([slot, [int(size.sum())]]).astype(np.int64), read_hap=np.ascontiguousarray(hap[kk]),
+                     read_ps=np.ascontiguousarray(ps[kk], np.int32), read_flag=np.ascontiguousarray((mk[M_LSEQ] == 0).astype(np.uint8)), tile_off=tile_off,
                      tile_ent=tile_ent.view(np.uint8).reshape(-1), ref_letters=ref_bytes[ga - 1:gb] if gb >= ga else ref_bytes[:0])
         sections, total_b = {}, 0
         for k, v in parts.items():

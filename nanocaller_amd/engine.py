@@ -380,6 +380,43 @@ class Engine:
         self._check(self.L.nc_indel_forward(self.ctx, kind, n, _ptr(x), _ptr(probs)), "nc_indel_forward")
         return probs
 
+    def snp_phase(self, site_pos, site_alleles, read_group, n_groups, *, max_cov=15, reads=None, csr=None) -> dict:
+        """Read-based phasing + haplotags (nc_snp_phase_*, nc_haplotag_run) -> dict of host arrays (see nc_phase_arrays).
+        reads: (codes, rd_start, rd_end, slot_off) device tensors of a resident pack's kept reads (alleles gathered on the device);
+        csr: (entry_off int64, entry_site int32, entry_allele uint8) host arrays instead."""
+        L = self.L
+        pos = np.ascontiguousarray(site_pos, np.int32)
+        h = C.c_void_p()
+        if reads is not None:
+            codes, rs, re_, so = reads
+            al = np.ascontiguousarray(site_alleles, np.uint8).reshape(-1, 2)
+            torch.cuda.current_stream(self.device).synchronize()            # (the pack's upload may still be in flight on torch's stream)
+            rc = L.nc_snp_phase_gather(self.ctx, _ptr(codes), codes.numel(), int(rs.numel()), _ptr(rs), _ptr(re_), _ptr(so), pos.size, _lib.npp(pos),
+                                       _lib.npp(al), C.byref(h))
+            self._check(rc, "nc_snp_phase_gather")
+        else:
+            off, site, allele = (np.ascontiguousarray(a, t) for a, t in zip(csr, (np.int64, np.int32, np.uint8)))
+            self._check(L.nc_snp_phase_load(self.ctx, off.size - 1, pos.size, _lib.npp(pos), _lib.npp(off), _lib.npp(site), _lib.npp(allele),
+                                            C.byref(h)), "nc_snp_phase_load")
+        try:
+            self._check(L.nc_snp_phase_solve(self.ctx, h, int(max_cov)), "nc_snp_phase_solve")
+            grp = np.ascontiguousarray(read_group, np.int32)
+            self._check(L.nc_haplotag_run(self.ctx, h, int(n_groups), _lib.npp(grp)), "nc_haplotag_run")
+            v = _lib.PhaseArraysC()
+            L.nc_snp_phase_view(h, C.byref(v))
+
+            def a(ptr, n, dt):
+                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), (n,)).copy() if n and ptr else np.zeros(0, dt)
+            R, S, nb, ng = v.n_reads, v.n_sites, v.n_blocks, v.n_groups
+            return dict(entry_off=a(v.entry_off, R + 1, np.int64), entry_site=a(v.entry_site, v.n_entries, np.int32),
+                        entry_allele=a(v.entry_allele, v.n_entries, np.uint8), side=a(v.read_side, R, np.int8),
+                        site_block=a(v.site_block, S, np.int32), site_h=a(v.site_h, S, np.uint8), site_phased=a(v.site_phased, S, np.uint8).astype(bool),
+                        site_ps=a(v.site_ps, S, np.int32), block_first=a(v.block_first, nb, np.int32), block_last=a(v.block_last, nb, np.int32),
+                        block_ps=a(v.block_ps, nb, np.int32), block_cost=a(v.block_cost, nb, np.int64), group_hp=a(v.group_hp, ng, np.uint8),
+                        group_ps=a(v.group_ps, ng, np.int32), ms=dict(zip(("gather", "select", "dp", "haplotag"), list(v.ms))))
+        finally:
+            L.nc_snp_phase_free(h)
+
     def indel_scan(self, dp: DevicePack, start, end, *, mincov, win_size, small_win_size, ins_t, del_t, excl=None, haploid=False, impute=False):
         """K7 -> int8 [end-start+1] per-column decision (-1 none, 0 long-window rule, 1 small-window rule, 2 impute_indel_phase
         candidate when impute=True)."""

@@ -102,7 +102,11 @@ def _resolve(sam_path, chrom=None, fasta_path=None, span=None) -> World:
 
         def make():
             DECODES.append((sam_path, chrom, span))
-            return read_bam(sam_path, fasta_path, chrom) if span is None else read_bam(sam_path, fasta_path, chrom, span[0], span[1])
+            w = read_bam(sam_path, fasta_path, chrom) if span is None else read_bam(sam_path, fasta_path, chrom, span[0], span[1])
+            if getattr(sam_path, "tags", None):                     # a TaggedBam: HP / PS from the phaser's haplotag table
+                from .phase import tags_for_names
+                w.meta["hap"], w.meta["ps"] = tags_for_names(w.names, sam_path.tags)
+            return w
         return _BAM_WORLDS.get((sam_path, fasta_path, chrom) + ((span,) if span else ()), make)
     raise FileNotFoundError("alignments %r: not a BAM file, a World, or a registered key" % (sam_path,))
 

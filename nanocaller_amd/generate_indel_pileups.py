@@ -29,6 +29,7 @@ from . import _lib
 
 from .engine import get_engine
 from .generate_SNP_pileups import _exclude_rows, _resolve, device_pack
+from .phase import retag_decoded
 
 
 def pick_variants(col_type, start, win_size, groups=None, extra=None):
@@ -362,6 +363,7 @@ def get_indel_testing_candidates(dct, chunk, aligner=None, device=0):
     d = bf.decode(chrom, max(1, start - 100000), end + 1000, anchors=anchors, window_before=window_before,
                   window_after=window_after, keep_mask=flag)
     bf.close()
+    retag_decoded(d, chunk["sam_path"])
     names, hap, ps = d["names"], d["hap"], d["ps"]
     out_pos, x0, x1, x2, alleles, phase = [], [], [], [], [], []
     for v_pos, win in zip(anchors, d["windows"]):
@@ -417,6 +419,7 @@ def decoded_contig(sam_path, chrom, fasta_path):
         from .bam import decode_parallel, name_gids, read_fasta, unsupported_counts
         _CONTIGS.clear()
         dec = decode_parallel(sam_path, chrom, keep_seq=True)
+        retag_decoded(dec, sam_path)                                # (a TaggedBam: HP / PS from the phaser's haplotag table)
         fasta = read_fasta(fasta_path, chrom)
         _CONTIGS[key] = dict(dec=dec, handle=dec["_owner"].handle, fasta=fasta, fasta_b=fasta.encode("ascii"), keep={}, name_idx=None)
         # the same decode serves pass 1 (and the SNP path): register it as the contig's World so that nothing decodes the BAM twice
@@ -674,7 +677,7 @@ def _device_ingest_contig(dct, sam_path, chrom, supp, device):
         except DeviceIngestUnavailable:
             return None
         fasta_b = read_fasta_bytes(dct["fasta_path"], chrom)
-        dp = dbam.pack(dbam.prepare(chrom, fasta_b, supplementary=supp), indel=True, tail_cap=TAIL_CAP)
+        dp = dbam.pack(dbam.prepare(chrom, fasta_b, supplementary=supp, haplotags=getattr(sam_path, "tags", None)), indel=True, tail_cap=TAIL_CAP)
         _DEV_INGEST[key] = (dp, indel_reads_struct(dp), dict(fasta=fasta_b.decode("ascii"), fasta_b=fasta_b, device_ingest=True))
     return _DEV_INGEST[key]
 

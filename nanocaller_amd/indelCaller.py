@@ -8,7 +8,9 @@ tensor K8, allele_prediction), `Indel_model` / `haploid_Indel_model` on the GPU 
 that release that contig's indel chunks, then 'indel' jobs; the merges that the reference delegates to bcftools / bgzip /
 tabix / rtg are done by vcfio (sorted BGZF + CSI).  WhatsHap itself stays an optional external step (out of scope,
 SURVEY.md section 2): when `whatshap` is on PATH the reference's two commands are run, otherwise the contig's SNP records pass
-through unphased and the indel chunks read `params['sam_path']` as it is (a BAM that already carries HP / PS tags works).
+through unphased and the indel chunks read `params['sam_path']` as it is (a BAM that already carries HP / PS tags works).  Opt-in
+alternative: the built-in phaser on the GPU (`params['phaser'] = 'device'` or NC_PHASER=device; phase.py), whose haplotags reach the
+indel chunks as a table (`chunk['haplotags']`) instead of a tagged BAM.
 
 Arithmetic note: in the reference `batch_prob_all` is a float32 TensorFlow tensor, so QUAL/GQ are evaluated in
 float32 (`1e-6 + 1 - p` etc.); that is reproduced with explicit np.float32 operations.
@@ -134,6 +136,7 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
     from .generate_indel_pileups import (default_aligner, device_route_ok, get_indel_testing_candidates, get_indel_testing_candidates_batch,
                                          impute_split_chunks, indel_chunks_vcf_text, star_aligner)
     from .generate_indel_pileups_haploid import get_indel_testing_candidates_haploid
+    from .phase import tagged_source
     from .weights import Weights
     curr_vcf_path = os.path.join(params['intermediate_indel_files_dir'], '%s.%d.indel.vcf' % (params['prefix'], worker_id))
     indel_files_list.append(curr_vcf_path)
@@ -204,6 +207,8 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
                 if len(indel_dict) > 0:
                     continue
                 break
+            # a chunk with `haplotags` (the device phaser's table) reads its BAM through a TaggedBam: HP / PS by read name from the table
+            jobs = [(j[0], dict(j[1], sam_path=tagged_source(j[1]))) if j[1].get('haplotags') else j for j in jobs]
             if not native:
                 for job in jobs:
                     chunk = job[1]
@@ -283,13 +288,17 @@ def _whatshap_available():
     return all(shutil.which(b) for b in ("whatshap", "samtools"))
 
 
-def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_files_list):
+def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_files_list, device=0):
     """indelCaller.py:192-262 for one contig: split the SNP calls of the contig at `phase_qual_score`, phase the confident
     ones and haplotag the reads (WhatsHap: external, optional), write <contig>.snps.phased.vcf.gz (+ the low-quality rest),
-    then release the contig's indel chunks with chunk['sam_path'] = the haplotagged BAM (or params['sam_path'])."""
+    then release the contig's indel chunks with chunk['sam_path'] = the haplotagged BAM (or params['sam_path']).
+    With the built-in phaser selected (params['phaser'] = 'device', or NC_PHASER=device without that key; phase.py) the confident
+    SNPs are phased on `device` from the contig's resident reads, the haplotags go to <contig>.haplotags.npz and the contig's
+    indel chunks carry chunk['haplotags'] = that file beside chunk['sam_path'] = params['sam_path']."""
     import os
 
     from . import vcfio
+    from .phase import device_phaser_selected
     from .utils import run_cmd
     contig = contig_dict['name']
     phase_dir = params['intermediate_phase_files_dir']
@@ -308,7 +317,15 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
         lowq_vcf = os.path.join(phase_dir, '%s.snps.lowq.unphased.vcf.gz' % contig)
         vcfio.write_sorted_vcf(lowq_vcf, header, lo, [contig])
         phased = False
-        if _whatshap_available() and isinstance(sam_path, str):
+        haplotags = None
+        if device_phaser_selected(params):
+            from .phase import phase_contig, save_haplotags
+            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device)
+            vcfio.write_sorted_vcf(out_vcf, _with_phase_format(header), res.records, [contig])
+            haplotags = os.path.join(phase_dir, '%s.haplotags.npz' % contig)
+            save_haplotags(haplotags, res.haplotags)
+            phased = True
+        elif _whatshap_available() and isinstance(sam_path, str):
             unph = os.path.join(phase_dir, '%s.snps.unphased.vcf' % contig)
             raw = os.path.join(phase_dir, '%s.snps.phased.raw.vcf' % contig)
             with open(unph, 'w') as f:
@@ -337,6 +354,8 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
     else:
         for chunk in indel_dict.get(contig, []):
             chunk['sam_path'] = sam_path                                       # :258
+            if contig_dict['ploidy'] != 'haploid' and haplotags:
+                chunk['haplotags'] = haplotags
             job_Q.put(('indel', chunk))
         indel_dict.pop(contig, None)
 
@@ -361,7 +380,7 @@ def caller(params, job_Q, counter_Q, indel_dict, phased_snp_files_list, indel_fi
         except queue.Empty:
             continue
         if job[0] == 'phase':
-            phase_run(job[1], params, indel_dict, job_Q, counter_Q, phased_snp_files_list)
+            phase_run(job[1], params, indel_dict, job_Q, counter_Q, phased_snp_files_list, device=device)
         elif job[0] == 'indel':
             job_Q.put(job)
             indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=device, worker_id=worker_id, aligner=aligner)
@@ -427,12 +446,15 @@ def call_manager(params, devices=None, aligner=None):
         if rank == 0:
             while not job_Q.empty():
                 job = job_Q.get()
-                phase_run(job[1], dict(params, mode='snps'), {}, queue.Queue(), queue.Queue(), phased_snp_files_list)
+                phase_run(job[1], dict(params, mode='snps'), {}, queue.Queue(), queue.Queue(), phased_snp_files_list, device=device)
         shard.barrier()
         for name in list(indel_dict):
             tagged = os.path.join(params['intermediate_phase_files_dir'], '%s.phased.bam' % name)
+            tags = os.path.join(params['intermediate_phase_files_dir'], '%s.haplotags.npz' % name)
             for chunk in indel_dict.pop(name):
                 chunk['sam_path'] = tagged if os.path.exists(tagged) else params['sam_path']
+                if os.path.exists(tags):                                       # the device phaser's haplotags (phase_run)
+                    chunk['haplotags'] = tags
                 job_Q.put(('indel', chunk))
     caller(params, job_Q, counter_Q, indel_dict, phased_snp_files_list, indel_files_list, device=device, worker_id=rank + 1,
            aligner=aligner)

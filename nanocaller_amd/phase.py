@@ -1,0 +1,232 @@
+"""Read-based SNP phasing and read haplotagging on the GPU: the built-in replacement for the `whatshap phase` +
+`whatshap haplotag` steps of phase_run (nanocaller_src/indelCaller.py:192-262).  DESIGN.md "Read-based phasing" states the
+algorithm (an exact minimum-error-correction phaser, WhatsHap's model, every tie-break fixed) and its deviations from WhatsHap.
+
+`phase_contig` phases one contig's het SNP calls from the reads of its resident pack (the SNP pass's `device_pack`: nothing is
+decoded twice) and returns the phased records, the blocks and a haplotag table: per read NAME its 64-bit FNV-1a hash (the hash
+the device ingest's record meta carries), HP and PS.  The indel pass takes HP / PS from such a table instead of the BAM's own tags
+when a chunk carries `haplotags` (`TaggedBam`).  Opt-in: params['phaser'] = 'device', or NC_PHASER=device when params has no
+'phaser' key (`device_phaser_selected`).
+"""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from .synth import FLAG_FILTER_DEFAULT, FLAG_FILTER_SUPPL, World
+
+_CODE = {"A": 0, "G": 1, "T": 2, "C": 3}
+_FNV_OFFSET = np.uint64(1469598103934665603)
+_FNV_PRIME = np.uint64(1099511628211)
+
+
+def device_phaser_selected(params) -> bool:
+    """params['phaser'] == 'device'; without that key, the environment's NC_PHASER == 'device'"""
+    if "phaser" in params:
+        return params["phaser"] == "device"
+    return os.environ.get("NC_PHASER") == "device"
+
+
+def name_hash(names) -> np.ndarray:
+    """FNV-1a (64 bit) of every read name with its terminating NUL: the hash of the BAM record's read_name field, as the device
+    ingest computes it (nc_ingest.hip, meta rows M_HASH_LO / M_HASH_HI)"""
+    n = len(names)
+    if n == 0:
+        return np.zeros(0, np.uint64)
+    enc = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in names]
+    ln = np.fromiter((len(b) for b in enc), np.int64, n)
+    w = int(ln.max()) + 1
+    buf = np.zeros((n, w), np.uint8)
+    flat = np.frombuffer(b"".join(enc), np.uint8)
+    rows = np.repeat(np.arange(n), ln)
+    cols = np.arange(flat.size) - np.repeat(np.cumsum(ln) - ln, ln)
+    buf[rows, cols] = flat
+    h = np.full(n, _FNV_OFFSET, np.uint64)
+    with np.errstate(over="ignore"):
+        for k in range(w):
+            m = k <= ln                                                    # (k == len: the NUL byte)
+            h[m] = (h[m] ^ buf[m, k].astype(np.uint64)) * _FNV_PRIME
+    return h
+
+
+@dataclass
+class PhaseResult:
+    records: list                      # VCF record lines, phased ones rewritten (GT with '|', FORMAT + ':PS')
+    blocks: list                       # (first site position, last site position, PS, MEC cost) per block
+    haplotags: dict                    # hash uint64 [n] ascending, hp uint8 [n], ps int32 [n]: tagged read names only
+    sites: dict = field(default_factory=dict)    # pos, record index, h, phased, ps per het site
+    reads: dict = field(default_factory=dict)    # kept reads: index into the World, name hash, group, side, hp, ps
+    ms: dict = field(default_factory=dict)
+
+
+def het_sites(snp_records, phase_qual_score):
+    """the records the phaser takes: QUAL >= phase_qual_score, GT 0/1 or 1/2, single-base alleles -> (record index, pos, alleles [n, 2], kind)"""
+    q = float(phase_qual_score)
+    idx, pos, al, kind = [], [], [], []
+    last = 0
+    for i, ln in enumerate(snp_records):
+        f = ln.rstrip("\n").split("\t")
+        if len(f) < 10 or not float(f[5]) >= q:
+            continue
+        gt = f[9].split(":", 1)[0]
+        alts = f[4].split(",")
+        if gt == "0/1" and len(alts) == 1:
+            a = (f[3], alts[0])
+        elif gt == "1/2" and len(alts) == 2:
+            a = (alts[0], alts[1])
+        else:
+            continue
+        if a[0] not in _CODE or a[1] not in _CODE or int(f[1]) <= last:
+            continue
+        last = int(f[1])
+        idx.append(i)
+        pos.append(last)
+        al.append((_CODE[a[0]], _CODE[a[1]]))
+        kind.append(gt)
+    return (np.array(idx, np.int64), np.array(pos, np.int32), np.array(al, np.uint8).reshape(-1, 2), kind)
+
+
+def phased_record(line, h, ps):
+    """one record with its GT phased (0/1 -> 0|1 when h = 0, 1|0 when h = 1; 1/2 -> 1|2 / 2|1) and PS appended"""
+    f = line.rstrip("\n").split("\t")
+    smp = f[9].split(":")
+    a, b = smp[0].split("/")
+    smp[0] = ("%s|%s" % (a, b)) if h == 0 else ("%s|%s" % (b, a))
+    f[8] += ":PS"
+    f[9] = ":".join(smp) + ":%d" % ps
+    return "\t".join(f) + "\n"
+
+
+def kept_reads(world: World, supplementary):
+    """the alignments the SNP pileup keeps (flag filter, htslib's depth cap), in pack order -> (World indices, start, end, slot_off)"""
+    from .pack import pileup_depth_cap
+    filt = FLAG_FILTER_SUPPL if supplementary else FLAG_FILTER_DEFAULT
+    keep = pileup_depth_cap(world.read_start, world.read_end, np.ascontiguousarray((np.asarray(world.read_flag) & filt) == 0, np.uint8))
+    kept = np.flatnonzero(keep)
+    rs = np.ascontiguousarray(np.asarray(world.read_start)[kept], np.int32)
+    re_ = np.ascontiguousarray(np.asarray(world.read_end)[kept], np.int32)
+    slot = np.zeros(kept.size + 1, np.int64)
+    np.cumsum(((re_.astype(np.int64) + 15) & ~15) - (rs.astype(np.int64) & ~15), out=slot[1:])     # (nc_pack_fill's slot layout)
+    return kept, rs, re_, slot
+
+
+def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, supplementary=False, max_cov=15, device=0) -> PhaseResult:
+    """Phase the het SNP calls `snp_records` (VCF lines of contig `chrom`) from the reads of `sam_path` (a BAM path, a World or a
+    registered key) and haplotag the reads.  -> PhaseResult"""
+    import torch
+
+    from .engine import get_engine
+    from .generate_SNP_pileups import _resolve, device_pack
+    eng = get_engine(device)
+    eng.use_torch_stream()
+    rec_idx, pos, alleles, _ = het_sites(snp_records, phase_qual_score)
+    world = _resolve(sam_path, chrom, fasta_path)
+    dp = device_pack(sam_path, fasta_path, chrom, bool(supplementary), None, device, by_name=True)[0]
+    kept, rs, re_, slot = kept_reads(world, supplementary)
+    if dp.reads is not None:
+        if dp.reads["n_reads"] != kept.size:
+            raise RuntimeError("phase_contig: the pack holds %d reads, the flag filter keeps %d" % (dp.reads["n_reads"], kept.size))
+        reads = (dp.codes, dp.reads["rd_start"], dp.reads["rd_end"], dp.reads["slot_off"])
+    else:
+        dev = eng.device
+        reads = (dp.codes, torch.from_numpy(rs).to(dev), torch.from_numpy(re_).to(dev), torch.from_numpy(slot).to(dev))
+    if int(slot[-1]) > dp.codes.numel():
+        raise RuntimeError("phase_contig: the read table addresses %d code bytes, the pack holds %d" % (int(slot[-1]), dp.codes.numel()))
+    from .pack import world_names
+    names = world_names(world)
+    if names is not None:
+        hashes = name_hash([names[k] for k in kept.tolist()])
+        uniq, group = np.unique(hashes, return_inverse=True)
+    else:                                                               # no names: every alignment is its own read
+        hashes = np.zeros(kept.size, np.uint64)
+        uniq, group = np.zeros(kept.size, np.uint64), np.arange(kept.size)
+    r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, reads=reads)
+    out = list(snp_records)
+    for k in np.flatnonzero(r["site_phased"]).tolist():
+        out[int(rec_idx[k])] = phased_record(snp_records[int(rec_idx[k])], int(r["site_h"][k]), int(r["site_ps"][k]))
+    blocks = [(int(pos[f]), int(pos[l_]), int(ps), int(c)) for f, l_, ps, c in zip(r["block_first"], r["block_last"], r["block_ps"], r["block_cost"])]
+    tagged = r["group_hp"] != 0
+    tags = dict(hash=np.ascontiguousarray(uniq[tagged] if names is not None else np.zeros(0, np.uint64)),
+                hp=np.ascontiguousarray(r["group_hp"][tagged] if names is not None else np.zeros(0, np.uint8)),
+                ps=np.ascontiguousarray(r["group_ps"][tagged] if names is not None else np.zeros(0, np.int32)))
+    sites = dict(pos=pos, record=rec_idx, h=r["site_h"], phased=r["site_phased"], ps=r["site_ps"], block=r["site_block"])
+    reads_out = dict(index=kept, hash=hashes, group=group, side=r["side"], hp=r["group_hp"][group], ps=r["group_ps"][group],
+                     entry_off=r["entry_off"], entry_site=r["entry_site"], entry_allele=r["entry_allele"])
+    return PhaseResult(records=out, blocks=blocks, haplotags=tags, sites=sites, reads=reads_out, ms=r["ms"])
+
+
+# ------------------------------------------------------------------------------------------- haplotag tables in the indel pass
+def save_haplotags(path, tags):
+    with open(path, "wb") as f:                                          # (an open file: np.savez would append '.npz' to a bare name)
+        np.savez(f, hash=np.asarray(tags["hash"], np.uint64), hp=np.asarray(tags["hp"], np.uint8), ps=np.asarray(tags["ps"], np.int32))
+
+
+_TABLES = {}
+
+
+def load_haplotags(path):
+    st = os.stat(path)
+    key = (os.path.abspath(path), st.st_size, st.st_mtime_ns)
+    if key not in _TABLES:
+        _TABLES.clear()
+        with np.load(path) as z:
+            h, hp, ps = z["hash"].astype(np.uint64), z["hp"].astype(np.uint8), z["ps"].astype(np.int32)
+        o = np.argsort(h, kind="stable")
+        _TABLES[key] = (h[o], hp[o], ps[o])
+    return _TABLES[key]
+
+
+def tags_for_hashes(hashes, path):
+    """(HP uint8, PS int32) per read-name hash from the table at `path`: names the table lacks are untagged (0, 0)"""
+    h, hp, ps = load_haplotags(path)
+    hashes = np.asarray(hashes, np.uint64)
+    i = np.searchsorted(h, hashes)
+    i = np.minimum(i, max(h.size - 1, 0))
+    hit = (h[i] == hashes) if h.size else np.zeros(hashes.size, bool)
+    return np.where(hit, hp[i] if h.size else 0, 0).astype(np.uint8), np.where(hit, ps[i] if h.size else 0, 0).astype(np.int32)
+
+
+def tags_for_names(names, path):
+    return tags_for_hashes(name_hash(names), path)
+
+
+class TaggedBam(str):
+    """The path of a BAM whose alignments take HP / PS from the haplotag table `tags` (by read name) instead of their own tags.
+    It compares and hashes unequal to the bare path and to other tables, so every cache keyed by the source (decoded contig,
+    resident pack, device-ingested contig) keeps the tagged and the untagged variant apart; file access sees the plain path."""
+
+    def __new__(cls, path, tags):
+        s = super().__new__(cls, path)
+        s.tags = str(tags)
+        return s
+
+    def __eq__(self, other):
+        return isinstance(other, TaggedBam) and str.__eq__(self, other) and self.tags == other.tags
+
+    def __ne__(self, other):
+        return not self.__eq__(other)
+
+    def __hash__(self):
+        return hash((str.__str__(self), self.tags))
+
+    def __reduce__(self):
+        return (TaggedBam, (str.__str__(self), self.tags))
+
+
+def tagged_source(chunk):
+    """chunk['sam_path'] as the indel pass reads it: a TaggedBam when the chunk carries `haplotags`"""
+    sp = chunk["sam_path"]
+    if chunk.get("haplotags") and isinstance(sp, str) and not isinstance(sp, TaggedBam):
+        return TaggedBam(sp, chunk["haplotags"])
+    return sp
+
+
+def retag_decoded(d, sam_path):
+    """a host decode (dict with names / hap / ps) of a TaggedBam: HP / PS overwritten in place from the table"""
+    if isinstance(sam_path, TaggedBam):
+        hp, ps = tags_for_names(d["names"], sam_path.tags)
+        d["hap"][:] = hp
+        d["ps"][:] = ps
+    return d

@@ -1,0 +1,59 @@
+"""Wall time of the read-based phaser on a chr20-sized synthetic ONT contig (64.4 Mb, 30x, generated in HBM by nc_synth_indel_*):
+allele gather, read selection + blocks + slots (host), the MEC DP, haplotagging.  The het sites are the generator's own (its truth,
+recomputed from the same seed); every read is its own name.  Prints one JSON line.  Usage: python tools/bench_phase.py [--length L] [--reps N]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from nanocaller_amd.engine import get_engine  # noqa: E402
+from nanocaller_amd.synth_device import make_indel_device_workload  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--length", type=int, default=64_444_167)
+    ap.add_argument("--depth", type=float, default=30.0)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=812)
+    a = ap.parse_args()
+    eng = get_engine(0)
+    eng.use_torch_stream()
+    L = a.length
+    pack, _, info = make_indel_device_workload(eng, L, depth=a.depth, seed=a.seed)
+    # the generator's haplotype bases (make_indel_device_workload's defaults): het SNP sites and their two alleles
+    ref = torch.zeros(L + 1, dtype=torch.uint8, device=eng.device)
+    hapb = torch.zeros(2 * (L + 1), dtype=torch.uint8, device=eng.device)
+    hapi = torch.zeros(2 * (L + 1), dtype=torch.int8, device=eng.device)
+    P = lambda x: C.c_void_p(x.data_ptr())                              # noqa: E731
+    assert eng.L.nc_synth_indel_truth(eng.ctx, L, a.seed, 1 / 1000.0, 1 / 2000.0, 1 / 5000.0, 1 / 15000.0, 50, P(ref), P(hapb), P(hapi)) == 0
+    hb = hapb.view(2, L + 1).cpu().numpy()
+    r = ref.cpu().numpy()
+    het = np.flatnonzero((hb[0] != hb[1]) & (r < 4))
+    het = het[het >= 1].astype(np.int32)
+    alt = np.where(hb[0][het] != r[het], hb[0][het], hb[1][het])
+    alleles = np.stack([r[het], alt], 1).astype(np.uint8)
+    R = info["n_reads"]
+    reads = (pack.codes, pack.reads["rd_start"], pack.reads["rd_end"], pack.reads["slot_off"])
+    group = np.arange(R, dtype=np.int32)
+    runs = []
+    for _ in range(a.reps + 1):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        res = eng.snp_phase(het, alleles, group, R, reads=reads)
+        runs.append((time.perf_counter() - t, res["ms"]))
+    wall, ms = min(runs[1:], key=lambda x: x[0])
+    out = dict(metric="phase_chr20_sized_s", value=round(wall, 4), length=L, depth=a.depth, reads=R, het_sites=int(het.size),
+               phased_sites=int(res["site_phased"].sum()), blocks=int(res["block_first"].size), entries=int(res["entry_site"].size),
+               tagged_reads=int((res["group_hp"] > 0).sum()), stage_ms={k: round(v, 2) for k, v in ms.items()})
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
