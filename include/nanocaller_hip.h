@@ -421,7 +421,7 @@ int nc_snp_forward_drain(nc_ctx *ctx, int32_t model_kind, int64_t n, const float
 int nc_cnn_x_limit(nc_ctx *ctx, int32_t model_kind, float *x_limit);
 int nc_cnn_range_watch(nc_ctx *ctx, uint8_t *site_flags_dev);
 /* The split-precision SNP trunk the next nc_snp_forward[_drain] of this context launches (it depends on the tensor format and the precision
- * mode): kernel_id 0 = k4_conv12 (exact fp32), 1 = k5_trunk_h3, 2 = k5_trunk_p3, 3 = k5_trunk_lin (int16 tensors: conv1 by linearity, two f16
+ * mode): kernel_id 0 = k4_conv12 (exact fp32), 2 = k5_trunk_p3, 3 = k5_trunk_lin (int16 tensors: conv1 by linearity, two f16
  * products on the integer entries instead of three); mfma_per_site = v_mfma_f32_16x16x32_f16 instructions it executes per site (bench.py's
  * executed-vs-algorithmic figure).  No reference counterpart (measurement support for model_architect.py:36-64's conv1-3). */
 int nc_snp_trunk_info(nc_ctx *ctx, int32_t *mfma_per_site, int32_t *kernel_id);

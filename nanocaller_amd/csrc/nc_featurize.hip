@@ -35,10 +35,7 @@ __constant__ ModeTab MODES[5] = {
     {4, 20000, {{0, 2000, 4, 1}, {2000, 5000, 5, 0}, {5000, 10000, 5, 0}, {10000, 20000, 6, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}},
 };
 
-#ifndef NC_NBR_IDX_SHIFT
-#define NC_NBR_IDX_SHIFT 10
-#endif
-constexpr int NBR_IDX_SHIFT = NC_NBR_IDX_SHIFT;   // coarse index granularity: first neighbour site >= every 2^shift-th position
+constexpr int NBR_IDX_SHIFT = 10;   // coarse index granularity: first neighbour site >= every 2^shift-th position
 
 __device__ __forceinline__ int lower_bound_i32(const int32_t *a, int n, int64_t key, const int32_t *cidx, int32_t cidx_pos0, int n_cidx)
 {
@@ -502,10 +499,7 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
         typedef const uint8_t __attribute__((address_space(1))) *gbyte_ptr;
         const int P = nsel * ncols;
         const float inv = 1.0f / (float)ncols;
-#ifndef NC_FEAT_U
-#define NC_FEAT_U 8
-#endif
-        constexpr int U = NC_FEAT_U;                                   // steps whose gathers are in flight together
+        constexpr int U = 8;                                           // steps whose gathers are in flight together
         for (int p0 = 0; p0 < P; p0 += 64 * U) {
             int jk[U];
             uint32_t bc[U];

@@ -438,12 +438,8 @@ __global__ __launch_bounds__(256) void k_event_intervals_w(int32_t n_reads, cons
                     if (k2 - k > w - 1) break;
                     if (qualifies(ev_len[e2], cls)) { has_next = true; break; }
                 }
-#ifdef NC_ABL_EV_NOATOMIC
-                if (!has_prev && !has_next && k == -12345) diff[0] = 1;
-#else
                 if (!has_prev) atomicAdd(&diff[(int64_t)(cls * 2 + h) * c.nd + k], 1);
                 if (!has_next) atomicAdd(&diff[(int64_t)(cls * 2 + h) * c.nd + k + w], -1);
-#endif
             }
         }
     }
@@ -457,9 +453,6 @@ __global__ __launch_bounds__(256) void k_event_intervals_w(int32_t n_reads, cons
 // columns' decisions from them: k_prefix_rows_b and k_indel_decide_b have nothing left to do, the counts never reach HBM (2 GB
 // written and 2 GB read per chr20-sized contig) and the workspace needs no zeroing.  Needs the map tile entry -> read (slot_off of the wire pack): the device pipeline has
 // it (nc_indel_sites_plan); the host-route API keeps k_event_intervals_w.
-#ifndef NC_EV_NT
-#define NC_EV_NT 512
-#endif
 // per-column decision of :252-275 (float64 divide-and-compare, as in the reference) from the depths n0 / n1 of the two haplotypes (haploid:
 // n0 = all reads) and the window counts U(class, haplotype) at the column's rank
 template <class UF>
@@ -535,7 +528,7 @@ __device__ __forceinline__ int8_t indel_decide_tab(int k, int n0, int n1, UF U, 
     return -1;
 }
 
-constexpr int EV_SUB = 1024, EV_MARGIN = 256, EV_CAP = 2048, EV_NT = NC_EV_NT;
+constexpr int EV_SUB = 1024, EV_MARGIN = 256, EV_CAP = 2048, EV_NT = 512;
 
 // read index of every tile entry (its slot offset is unique) and its event cursors: for the tile's 1024-column blocks h = 0 .. SPT-1 (and the
 // one after the tile) the first event of the read at or after (tile start + 1024 h - EV_BACK).  Once per call, one wave per tile, so that
@@ -775,9 +768,6 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
         }
     }
     __syncthreads();
-#ifdef NC_ABL_EVT_A
-    return;
-#endif
     const int32_t k0 = sh_k0, nk = sh_k1 - k0 + 1;
     int8_t *col_type = col_type_all + c.coloff;
     if (sh_k1 < 0) {                                                 // no yielded column here
@@ -807,9 +797,6 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
     }
     __syncthreads();
     const int32_t m_lo = sh_mlo;
-#ifdef NC_ABL_EVT_A2
-    return;
-#endif
     auto qualifies = [](int32_t sl, int cls) {
         const int32_t ln = sl < 0 ? -sl : sl;
         const bool ins = sl > 0;
@@ -889,9 +876,6 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
             if (tid < 256 && total <= EV_CAP) for (int u = 0; u < cnt; u++) own[wp + inc - cnt + u] = (uint8_t)tid;
             __syncthreads();
             // ---- one event per thread
-#ifdef NC_ABL_EVT_B
-            if (total >= 0) { __syncthreads(); continue; }
-#endif
             if (total <= EV_CAP) {
                 // the batch's events into LDS (independent loads), then every look-up at a neighbour is an LDS read
                 constexpr int EVU = 4;                                            // (a thread's events in one round trip to HBM)
@@ -918,9 +902,6 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
                     }
                 }
                 __syncthreads();
-#ifdef NC_ABL_EVT_C
-                if (total >= 0) { __syncthreads(); continue; }
-#endif
                 for (int idx = tid; idx < total; idx += EV_NT) {
                     const int k = evk[idx], qm = evq[idx];
                     if (k < 0 || qm == 0) continue;
@@ -996,9 +977,6 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
             __syncthreads();
         }
     }
-#ifdef NC_ABL_EVT_D
-    return;
-#endif
     const uint16_t *depth = reinterpret_cast<const uint16_t *>(ck_depth(ws, c));
     constexpr int DCOL = EV_SUB / EV_NT;
     int dn0[DCOL], dn1[DCOL];
@@ -1033,9 +1011,6 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
         }
     }
     __syncthreads();
-#ifdef NC_ABL_EVT_E
-    return;
-#endif
     // the columns' decisions (k_indel_decide_b's, without the window counts' trip through HBM)
 #pragma unroll
     for (int u = 0; u < DCOL; u++) {

@@ -17,28 +17,19 @@
 
 namespace {
 
-#ifndef NC_HUFF_DT_BITS
-#define NC_HUFF_DT_BITS 5
-#endif
-constexpr int LT_BITS = 8, DT_BITS = NC_HUFF_DT_BITS, LT_SZ = 1 << LT_BITS, DT_SZ = 1 << DT_BITS;
+constexpr int LT_BITS = 8, DT_BITS = 5, LT_SZ = 1 << LT_BITS, DT_SZ = 1 << DT_BITS;
 // one lane's LDS, in BYTES: the two first-level tables (uint16), the canonical arrays of both codes -- count[16] (uint16) and the symbols by code as
 // BYTES (the literal / length code's ninth bit in a bit mask: 30 of its 286 symbols need it) --, the code lengths of the block being set up as
 // NIBBLES, the walk's start.  [r5] 1,164 + 144 bytes of window = 1,308 per member instead of 2,460: 16 members per workgroup, seven workgroups per
 // CU.  The symbol loop is bound by instruction issue -- a wave instruction costs its four cycles whether 8 or 16 of the 64 lanes are live -- and the
 // members in flight by LDS, so what a member's tables do not take, further lanes do.  (An 8-bit first-level table alone, at 8 lanes a wave, was
 // within 4 % either way in round 4: more WAVES per SIMD do not help an issue-bound loop; more LANES per wave do.)
-#ifndef NC_HUFF_WINPAD
-#define NC_HUFF_WINPAD 4
-#endif
 constexpr int B_LT = 0, B_DT = B_LT + 2 * LT_SZ, B_HLC = B_DT + 2 * DT_SZ, B_HLS = B_HLC + 32, B_HLM = B_HLS + 288, B_HDC = B_HLM + 36, B_HDS = B_HDC + 32,
               B_LENS = B_HDS + 32, B_WALK = B_LENS + 160, B_END = B_WALK + 8;
 static_assert(B_HLC % 2 == 0 && B_HDC % 2 == 0 && B_WALK % 2 == 0, "uint16 sections");
 constexpr int TAB_WORDS = (B_END + 3) / 4 | 1;                      // odd pitch in words: lanes spread over the banks
-#ifndef NC_HUFF_LPW_SH
-#define NC_HUFF_LPW_SH 4
-#endif
-constexpr int LPW_SH = NC_HUFF_LPW_SH, LPW = 1 << LPW_SH;                                 // members (= lanes) per workgroup of k_huff, and its log2.  One workgroup's duration is its slowest member's
-constexpr int WIN_DW = 32, WIN_PITCH = WIN_DW + NC_HUFF_WINPAD;     // a lane's window of the compressed stream: 32 dwords (+ pad: banks spread), topped up every 8 steps
+constexpr int LPW_SH = 4, LPW = 1 << LPW_SH;                                 // members (= lanes) per workgroup of k_huff, and its log2.  One workgroup's duration is its slowest member's
+constexpr int WIN_DW = 32, WIN_PITCH = WIN_DW + 4;                  // a lane's window of the compressed stream: 32 dwords (+ pad: banks spread), topped up every 8 steps
 
 struct InflateArgs {
     const uint8_t *comp;        // compressed payloads (the buffer is readable 8 bytes past the last payload)

@@ -778,10 +778,8 @@ __device__ __forceinline__ int row_scan_max(int x)
 }
 __device__ __forceinline__ int row_last(int x) { return __shfl(x, (int)(threadIdx.x | 15)); }      // lane 15 of the row
 
-#ifndef NC_WIN16_WAVES
-#define NC_WIN16_WAVES 6
-#endif
-__global__ __launch_bounds__(64, NC_WIN16_WAVES) void k_windows16(WinArgs p, int32_t force_serial)
+constexpr int WIN16_WAVES = 6;
+__global__ __launch_bounds__(64, WIN16_WAVES) void k_windows16(WinArgs p, int32_t force_serial)
 {
     __shared__ int32_t s_pos[4][WIN_EV_CAP], s_len[4][WIN_EV_CAP];       // s_len > 0: inserted bases, <= 0: minus the deleted columns
     __shared__ uint32_t s_row[4][WIN_ROW / 4];
@@ -1346,11 +1344,7 @@ __global__ __launch_bounds__(64) void k_fill16q(FillArgs p)
             chunk = chunk_nxt;
             chunk_nxt = load_chunk(t - 1 + 16 + q);
         }
-#ifdef NC_ABL_FILL_NOBPERM
-        const uint32_t c_new = chunk;
-#else
         const uint32_t c_new = (uint32_t)__shfl((int)chunk, (lane & 48) | ((t - 1) & 15));
-#endif
         c1 = dpp_shr1_u(splat16(4), c1);
         if (q == 0) c1 = c_new;
         uint32_t nh = dpp_shr1_u(0u, h_out), ne = dpp_shr1_u(splat16(NEG16), e_out);
@@ -1396,9 +1390,6 @@ __global__ __launch_bounds__(64) void k_fill16q(FillArgs p)
 #pragma unroll
             for (int k = 0; k < 2; k++) {
                 if (!(live[k] && i <= n1[k] && q * CPL < n2[k])) continue;
-#ifdef NC_ABL_FILL_NOSTORE
-                if (i != 100000) continue;
-#endif
                 uint32_t wd[4] = {0, 0, 0, 0};
 #pragma unroll
                 for (int j = 0; j < NWD; j++) {

@@ -22,9 +22,6 @@
 #include "nc_host.h"
 
 #define WIRE_BLOCK 1024
-#ifndef NC_WIRE_U
-#define NC_WIRE_U 4
-#endif
 
 struct nc_wire {
     std::vector<int32_t> rd_start, rd_end;
@@ -379,12 +376,8 @@ __device__ __noinline__ uint4 wire_group_general(int64_t B, int64_t r, int32_t n
 // kernel writing 63 M scattered bytes re-reads and re-writes the whole 1.9 GB array: +0.6 ms per chr20-sized pass).
 // BYTES (round 6): the events one byte each (nc_wire_build2 flag 1): `events` is that byte stream, blk_off counts bytes.  A lane takes four bytes (one
 // dword), the columns they skip are summed across the wave, and an event's code follows from the predicted code already in the image (wire_which).
-#ifndef NC_WIRE_UB
-#define NC_WIRE_UB 4                  // blocks per wave of the byte-event form
-#endif
-#ifndef NC_WIRE_EVL
-#define NC_WIRE_EVL 2                 // byte events per lane and round of k_wire_expand<.., true>: 4 (round 6's first form), 2 or 1
-#endif
+constexpr int WIRE_U = 4;             // blocks per wave
+constexpr int WIRE_EVL = 2;           // byte events per lane and round of k_wire_expand<.., true>: 4 (round 6's first form), 2 or 1
 template <int U, bool DEL, bool BYTES>
 __global__ __launch_bounds__(256) void k_wire_expand(int32_t n_reads, const int32_t *__restrict__ rd_start, const int32_t *__restrict__ rd_end,
                                                      const int64_t *__restrict__ slot_off, const uint8_t *__restrict__ ref_wire,
@@ -450,7 +443,7 @@ __global__ __launch_bounds__(256) void k_wire_expand(int32_t n_reads, const int3
     uint4 rv[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
-        if constexpr (BYTES) pr0[u] = (u < nu && lane < 16 * NC_WIRE_EVL) ? load_quad((e0[u] & ~3u) + 4 * lane, e1[u]) : 0u;
+        if constexpr (BYTES) pr0[u] = (u < nu && lane < 16 * WIRE_EVL) ? load_quad((e0[u] & ~3u) + 4 * lane, e1[u]) : 0u;
         else pr0[u] = u < nu ? load_pair((e0[u] & ~1u) + 2 * lane, e0[u], e1[u], blk0 + u == n_blocks - 1) : 0xffffffffu;
         if (ri0[u] >= 0) rv[u] = *reinterpret_cast<const uint4 *>(ref_wire + ri0[u] + lane * 16);
     }
@@ -470,11 +463,11 @@ __global__ __launch_bounds__(256) void k_wire_expand(int32_t n_reads, const int3
         if (a != 0xffffu) im[a & 0x3ffu] = (uint8_t)(a >> 12);
         if (b != 0xffffu) im[b & 0x3ffu] = (uint8_t)(b >> 12);
     };
-    // BYTES: NC_WIRE_EVL events of a lane (a round of the wave = 64 NC_WIRE_EVL bytes, loaded as dwords by its first 16 NC_WIRE_EVL lanes; a block of an
+    // BYTES: WIRE_EVL events of a lane (a round of the wave = 64 WIRE_EVL bytes, loaded as dwords by its first 16 WIRE_EVL lanes; a block of an
     // ONT contig has ~61 events: with four per lane three lanes in four carried none and the wave still ran four scatter steps; with two a round of
     // 128 bytes covers nearly every block at half the steps); `carry` = columns covered by the block's earlier bytes
     auto scatter4 = [&](uint8_t *im, uint32_t qd, uint32_t kb, uint32_t ea, uint32_t eb, int32_t &carry) {
-        constexpr int EVL = NC_WIRE_EVL;
+        constexpr int EVL = WIRE_EVL;
         uint32_t q = qd;
         if constexpr (EVL == 2) q = ((uint32_t)__shfl((int)qd, lane >> 1) >> (16 * (lane & 1))) & 0xffffu;
         else if constexpr (EVL == 1) q = ((uint32_t)__shfl((int)qd, lane >> 2) >> (8 * (lane & 3))) & 0xffu;
@@ -506,16 +499,12 @@ __global__ __launch_bounds__(256) void k_wire_expand(int32_t n_reads, const int3
     for (int u = 0; u < U; u++) {
         uint8_t *im = img + u * WIRE_BLOCK;
         if constexpr (BYTES) {
-#ifdef NC_ABL_NOSCATTER
-            if (u < 0) {
-#else
             if (u < nu) {
-#endif
                 int32_t carry = 0;
-                constexpr uint32_t RB = 64 * NC_WIRE_EVL;                 // bytes a round of the wave takes
+                constexpr uint32_t RB = 64 * WIRE_EVL;                 // bytes a round of the wave takes
                 scatter4(im, pr0[u], e0[u] & ~3u, e0[u], e1[u], carry);
                 for (uint32_t kb = (e0[u] & ~3u) + RB; kb < e1[u]; kb += RB)
-                    scatter4(im, lane < 16 * NC_WIRE_EVL ? load_quad(kb + 4 * lane, e1[u]) : 0u, kb, e0[u], e1[u], carry);
+                    scatter4(im, lane < 16 * WIRE_EVL ? load_quad(kb + 4 * lane, e1[u]) : 0u, kb, e0[u], e1[u], carry);
             }
         } else {
             scatter(im, pr0[u]);
@@ -551,11 +540,7 @@ __global__ __launch_bounds__(256) void k_wire_expand(int32_t n_reads, const int3
 #pragma unroll
     for (int u = 0; u < U; u++) {
         const int64_t B = (blk0 + u) * WIRE_BLOCK + (int64_t)lane * 16;
-#ifdef NC_ABL_NOSTORE
-        if (u < nu && B + 16 <= codes_len && B == 12345) {
-#else
         if (u < nu && B + 16 <= codes_len) {
-#endif
             // streaming store: the expanded codes are read once by the scan, later, from HBM
             const u32x4 v = *reinterpret_cast<const u32x4 *>(img + u * WIRE_BLOCK + lane * 16);
             __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(codes + B));
@@ -615,20 +600,13 @@ static int wire_expand(nc_ctx *ctx, int32_t n_reads, const int32_t *d_rd_start, 
         (n_blocks + 3) / 4 > INT32_MAX || ((uintptr_t)d_codes & 15) || ((uintptr_t)d_events & 3) || ((uintptr_t)d_ref_wire & 15) || (d_ref_code && ((uintptr_t)d_ref_code & 15)))
         return nc_fail(ctx, NC_ERR_ARG, "nc_wire_expand: bad argument");
     NC_HIP(ctx, hipSetDevice(ctx->device));
-    static const int U = [] { const char *e = getenv("NC_WIRE_U"); const int v = e ? atoi(e) : NC_WIRE_U; return (v == 1 || v == 2 || v == 8) ? v : 4; }();
-#define NC_LAUNCH_EXPAND(UU, DD)                                                                                                                         \
-    hipLaunchKernelGGL((k_wire_expand<UU, DD, false>), dim3((unsigned)((n_blocks + 4 * UU - 1) / (4 * UU))), dim3(256), 0, ctx->stream, n_reads, d_rd_start, \
-                       d_rd_end, d_slot_off, d_ref_wire, ref_pos0, ref_len, d_blk_off, d_blk_read, d_events, n_blocks, d_codes, codes_len, d_blk_ev,         \
-                       d_ev_off, d_ev_pos, d_ev_len)
-#define NC_LAUNCH_EXPAND_B(DD)                                                                                                                          \
-    hipLaunchKernelGGL((k_wire_expand<NC_WIRE_UB, DD, true>), dim3((unsigned)((n_blocks + 4 * NC_WIRE_UB - 1) / (4 * NC_WIRE_UB))), dim3(256), 0, ctx->stream, n_reads, d_rd_start, d_rd_end,  \
-                       d_slot_off, d_ref_wire, ref_pos0, ref_len, d_blk_off, d_blk_read, d_events, n_blocks, d_codes, codes_len, d_blk_ev, d_ev_off,    \
-                       d_ev_pos, d_ev_len)
-    if (bytes) { if (d_blk_ev) NC_LAUNCH_EXPAND_B(true); else NC_LAUNCH_EXPAND_B(false); }
-    else if (d_blk_ev) { if (U == 1) NC_LAUNCH_EXPAND(1, true); else if (U == 2) NC_LAUNCH_EXPAND(2, true); else if (U == 8) NC_LAUNCH_EXPAND(8, true); else NC_LAUNCH_EXPAND(4, true); }
-    else { if (U == 1) NC_LAUNCH_EXPAND(1, false); else if (U == 2) NC_LAUNCH_EXPAND(2, false); else if (U == 8) NC_LAUNCH_EXPAND(8, false); else NC_LAUNCH_EXPAND(4, false); }
-#undef NC_LAUNCH_EXPAND
-#undef NC_LAUNCH_EXPAND_B
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n_blocks + 4 * WIRE_U - 1) / (4 * WIRE_U))), dim3(256), 0, ctx->stream, n_reads, d_rd_start, d_rd_end,
+                           d_slot_off, d_ref_wire, ref_pos0, ref_len, d_blk_off, d_blk_read, d_events, n_blocks, d_codes, codes_len, d_blk_ev, d_ev_off,
+                           d_ev_pos, d_ev_len);
+    };
+    if (bytes) launch(d_blk_ev ? k_wire_expand<WIRE_U, true, true> : k_wire_expand<WIRE_U, false, true>);
+    else launch(d_blk_ev ? k_wire_expand<WIRE_U, true, false> : k_wire_expand<WIRE_U, false, false>);
     if (d_ref_code && ref_len) {
         const int64_t groups = (ref_len + 15) / 16;
         hipLaunchKernelGGL(k_ref_from_wire, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, ctx->stream, d_ref_wire, d_ref_code, ref_len);

@@ -148,7 +148,7 @@ def _golden_inputs(case):
 
 @pytest.fixture(params=["fp16x3", "fp32"])
 def precision(eng, request):
-    """both trunk kernels: k5_trunk_h3 (fp16x3 split precision, the default) and k4_conv12 (exact fp32 MFMA)"""
+    """both precisions of the trunk: fp16x3 split precision, the default (k5_trunk_p3 on these float32 tensors), and k4_conv12 (exact fp32 MFMA)"""
     eng.set_cnn_precision(exact_fp32=(request.param == "fp32"))
     yield request.param
     eng.set_cnn_precision(exact_fp32=False)
@@ -230,10 +230,10 @@ def test_snp_cnn_odd_site_counts(eng, n, precision):
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 255, 257, 513, 1300])
-def test_three_stage_trunk_equals_two_stage_trunk(eng, n, monkeypatch):
-    """k5_trunk_p3 (the default: conv1 | conv2 | conv3 on three consecutive sites, one barrier per site) runs the same MFMA sequence per
-    accumulator as k5_trunk_h3 (NC_TRUNK_P3=0): the probabilities are equal bit for bit, for site counts around the pipeline's fill / drain (1, 2, 3 sites
-    per workgroup) and the grid's edges, float32 and int16 tensors"""
+def test_three_stage_trunk_at_pipeline_edges(eng, n, monkeypatch):
+    """k5_trunk_p3 (conv1 | conv2 | conv3 on three consecutive sites, one barrier per site) against the float64 oracle for site counts around the
+    pipeline's fill / drain (1, 2, 3 sites per workgroup) and the grid's edges; float32 and int16 tensors of the same integer entries give the same
+    probabilities bit for bit"""
     import torch
     from nanocaller_amd import _lib
     from nanocaller_amd.weights import Weights, get_SNP_model
@@ -250,19 +250,18 @@ def test_three_stage_trunk_equals_two_stage_trunk(eng, n, monkeypatch):
     rd, sd = torch.from_numpy(ref_code).cuda(), torch.from_numpy(scale).cuda()
     ep, _ = oracle.snp_forward(w.flat, x, ref_code, scale, precision="f64")
     try:
+        monkeypatch.setenv("NC_TRUNK_LIN", "0")                          # (int16 tensors would otherwise take k5_trunk_lin: its own test below)
+        got = {}
         for i16 in (False, True):
             xd = torch.from_numpy(x).cuda()
             if i16:
                 assert np.array_equal(x, np.rint(x)) and np.abs(x).max() < 32768
                 xd = xd.to(torch.int16)
             eng.set_tensor_format(int16=i16)
-            got = {}
-            monkeypatch.setenv("NC_TRUNK_LIN", "0")                      # (int16 tensors would otherwise take k5_trunk_lin: its own test below)
-            for p3 in ("0", "1"):
-                monkeypatch.setenv("NC_TRUNK_P3", p3)
-                got[p3] = eng.snp_forward(_lib.MODEL_SNP, xd, rd, sd)[0].cpu().numpy()
-            assert np.array_equal(got["0"], got["1"]), (n, i16)
-            assert np.abs(got["1"] - ep).max() < 2e-5
+            assert eng.trunk_info()[1] == "k5_trunk_p3"
+            got[i16] = eng.snp_forward(_lib.MODEL_SNP, xd, rd, sd)[0].cpu().numpy()
+            assert np.abs(got[i16] - ep).max() < 2e-5, (n, i16)
+        assert np.array_equal(got[False], got[True]), n
     finally:
         eng.set_tensor_format(int16=False)
 
@@ -401,7 +400,7 @@ def test_indel_tensor_and_cnn_match_oracle(eng):
 
 @pytest.mark.parametrize("n", [1, 17, 333])
 def test_indel_cnn_split_precision_on_dense_inputs(eng, n):
-    """k8_conv23_h3 (fp16 hi/lo planes, three MFMA products per fp32 product) against the float64 oracle and the exact
+    """k10_indel_trunk_h3 (fp16 hi/lo planes, three MFMA products per fp32 product) against the float64 oracle and the exact
     fp32 kernels on dense random tensors (every tap and channel exercised, site counts that leave partial tiles)"""
     import torch
     from nanocaller_amd import _lib
