@@ -3087,54 +3087,79 @@ extern "C" int nc_indel_sites_run(nc_ctx *ctx, float *x_dev)
         }
         return NC_OK;
     };
-    int dump_g = -1;
+    // NC_PIPE_DUMP (debugging aid): the run's arrays as files <dump>.<name> -- the per-site ones once, the per-alignment and per-set ones of every
+    // group appended in group order (a run's files cover all its alignments and sets).  Class bytes: 0 = 32 diagonals, 1 = 64, 2 = full matrix by
+    // width, 3 = full matrix after a banded try (an edge touch; for the allele alignments also a band without its certificate), -1 = band off
+    const char *dump = getenv("NC_PIPE_DUMP");
+    auto dump_wr = [&](int g, const char *name, const void *src, size_t bytes, bool on_host) {
+        if (!src || !bytes) return;
+        std::vector<char> h;
+        if (!on_host) {
+            h.resize(bytes);
+            if (hipMemcpy(h.data(), src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
+            src = h.data();
+        }
+        char path[512];
+        snprintf(path, sizeof path, "%s.%s", dump, name);
+        if (FILE *fp = fopen(path, g == 0 ? "wb" : "ab")) { fwrite(src, 1, bytes, fp); fclose(fp); }
+    };
+    // the class of every item from the three lists: a banded try that failed is listed in its band's list AND in the full matrix's
+    auto dump_classes = [&](int g, const char *name, int32_t n, const void *lists, size_t pitch, const void *counts, bool banded) {
+        std::vector<int8_t> cls((size_t)std::max(n, 0), -1);
+        if (banded && n > 0) {
+            std::vector<int32_t> l(pitch * 3), c(4);
+            if (hipMemcpy(l.data(), lists, pitch * 3 * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
+            if (hipMemcpy(c.data(), counts, 16, hipMemcpyDeviceToHost) != hipSuccess) return;
+            for (int k = 0; k < 3; k++)
+                for (int32_t i = 0; i < std::min<int32_t>(c[k], (int32_t)pitch); i++) {
+                    const int32_t a = l[(size_t)k * pitch + i];
+                    if (a < 0 || a >= n) continue;
+                    int8_t &v = cls[(size_t)a];
+                    v = k < 2 ? (int8_t)k : v < 0 ? 2 : 3;
+                }
+        }
+        dump_wr(g, name, cls.data(), cls.size(), true);
+    };
     NC_TRY(stage_a(0));
     for (int g = 0; g < G; g++) {
         if (!timing && g + 1 < G) NC_TRY(stage_a(g + 1));            // the next group's alignments are enqueued before the host waits for this one's row count
         NC_TRY(stage_b1(g));
         volatile int32_t *mb = ctx->mbox + 36;
         NC_HIP(ctx, hipStreamSynchronize(sB));
-        if (const char *dump = getenv("NC_PIPE_DUMP")) {              // debugging aid: the group's alignments as files <dump>.<name>
+        const int k0 = groups[(size_t)g].first, k1 = groups[(size_t)g].second;
+        if (dump) {                                                  // (debugging aid: the group's alignments)
             const int b = g & 1;
-            const int32_t Ag = al0h[groups[(size_t)g].second] - al0h[groups[(size_t)g].first];
+            const int32_t Ag = al0h[k1] - al0h[k0];
             nc_pipe_state::GroupBufs &B = s->gb[b];
-            auto wr = [&](const char *name, const void *dev, size_t bytes) {
-                std::vector<char> h(bytes);
-                if (hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
-                char path[512];
-                snprintf(path, sizeof path, "%s.%s", dump, name);
-                if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), 1, bytes, fp); fclose(fp); }
-            };
-            wr("trace", B.trace.p, (size_t)Ag * EW * 4);
-            wr("win", B.win.p, (size_t)Ag * WS);
-            wr("n1", B.n1.p, (size_t)Ag * 4);
-            wr("al_site", (const int32_t *)s->al_site.p + al0h[groups[(size_t)g].first], (size_t)Ag * 4);
-            wr("al_read", (const int32_t *)s->al_read.p + al0h[groups[(size_t)g].first], (size_t)Ag * 4);
-            wr("site_pos", s->site_pos.p, (size_t)ns * 4);
-            wr("site_n2", s->site_n2.p, (size_t)ns * 4);
-            if (B.band_lo.p) wr("band_lo", B.band_lo.p, (size_t)Ag);
-            dump_g = g;
+            dump_wr(g, "trace", B.trace.p, (size_t)Ag * EW * 4, false);
+            dump_wr(g, "win", B.win.p, (size_t)Ag * WS, false);
+            dump_wr(g, "n1", B.n1.p, (size_t)Ag * 4, false);
+            dump_wr(g, "al_site", (const int32_t *)s->al_site.p + al0h[k0], (size_t)Ag * 4, false);
+            dump_wr(g, "al_read", (const int32_t *)s->al_read.p + al0h[k0], (size_t)Ag * 4, false);
+            if (g == 0) {
+                dump_wr(g, "site_pos", s->site_pos.p, (size_t)ns * 4, false);
+                dump_wr(g, "site_n2", s->site_n2.p, (size_t)ns * 4, false);
+            }
+            if (band_of[b]) dump_wr(g, "band_lo", B.band_lo.p, (size_t)Ag, false);
+            dump_classes(g, "cls", Ag, B.lists.p, (size_t)std::max(Ag, 1), B.counts.p, band_of[b]);
         }
         const int64_t rows = ((int64_t)mb[1] << 31) | (int64_t)(mb[0] & 0x7fffffff);
         NC_TRY(stage_b2(g, rows));
-        if (dump_g == g) {                                           // (debugging aid, continued: the allele stage's arrays of the group)
-            const char *dump = getenv("NC_PIPE_DUMP");
+        if (dump) {                                                  // (debugging aid, continued: the allele stage's arrays of the group)
             NC_HIP(ctx, hipStreamSynchronize(sB));
-            const int k0 = groups[(size_t)g].first, nset = (groups[(size_t)g].second - k0) * S;
+            const int nset = (k1 - k0) * S;
             nc_pipe_state::GroupBufs &B = s->gb[g & 1];
-            auto wr = [&](const char *name, const void *dev, size_t bytes) {
-                std::vector<char> h(bytes);
-                if (!dev || hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
-                char path[512];
-                snprintf(path, sizeof path, "%s.%s", dump, name);
-                if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), 1, bytes, fp); fclose(fp); }
-            };
-            wr("cns", B.cns.p, (size_t)nset * CNS_CAP);
-            wr("ncns", B.ncns.p, (size_t)nset * 4);
-            wr("rlen", (const int32_t *)s->rlen.p + (size_t)k0 * S, (size_t)nset * 4);
-            wr("alen", (const int32_t *)s->alen.p + (size_t)k0 * S, (size_t)nset * 4);
-            wr("ab_lo", s->ab_lo.p, (size_t)nset);
-            wr("ab_counts", s->ab_counts.p, 16);
+            const char *bae = getenv("NC_PIPE_BAND_ALLELES");
+            const bool ab = band_of[g & 1] && !(bae && atoi(bae) == 0);
+            dump_wr(g, "cns", B.cns.p, (size_t)nset * CNS_CAP, false);
+            dump_wr(g, "ncns", B.ncns.p, (size_t)nset * 4, false);
+            dump_wr(g, "rlen", (const int32_t *)s->rlen.p + (size_t)k0 * S, (size_t)nset * 4, false);
+            dump_wr(g, "alen", (const int32_t *)s->alen.p + (size_t)k0 * S, (size_t)nset * 4, false);
+            if (ab) {
+                dump_wr(g, "ab_lo", s->ab_lo.p, (size_t)nset, false);
+                dump_wr(g, "ab_counts", s->ab_counts.p, 16, false);
+            }
+            dump_classes(g, "ab_cls", nset, s->ab_lists.p, (size_t)std::max(nset, 1), s->ab_counts.p, ab);
         }
         if (timing && g + 1 < G) NC_TRY(stage_a(g + 1));
     }

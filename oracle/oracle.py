@@ -710,10 +710,11 @@ def records_from_indel_pack(read_start, read_end, codes_of, ev_of, ins_of, names
 
 
 def indel_site_ref(records, hap, ps, ref, v_pos, window_after, mincov, maxcov, aligner=None, scoring=(25, 1, 20, -10), haploid=False, band=False,
-                   how_out=None):
+                   how_out=None, reads_out=None):
     """One pass-2 site from records: read sets (first-maxcov policy), star alignment (`aligner(names, seqs, ref)` or the pure-Python
     star_msa_ref; band=True: every pairwise alignment on the band its CIGAR allows, as the device pipeline runs it), msa()'s tensor by
-    the C oracle.  -> None when the site fails the set-size tests, else (x float32 [S,5,128,2], [consensus strings], reference window, phase)"""
+    the C oracle.  -> None when the site fails the set-size tests, else (x float32 [S,5,128,2], [consensus strings], reference window, phase).
+    how_out / reads_out (band=True): extended set by set with how each window was aligned / its (record index, window length)"""
     win = ref[v_pos - 1:min(len(ref), v_pos + window_after)]
     if any(ch not in "AGTC" for ch in win):
         return None
@@ -733,6 +734,8 @@ def indel_site_ref(records, hap, ps, ref, v_pos, window_after, mincov, maxcov, a
             cig, how = star_cigars_banded_ref(seqs, [window_band_ref(records[k], v_pos, window_after) for k, _ in st], win, *scoring)
             if how_out is not None:
                 how_out.extend(how)
+            if reads_out is not None:
+                reads_out.extend((k, len(s)) for k, s in st)
             rows, ref_row = star_msa_ref(seqs, win, *scoring, cigars=cig)
         else:
             rows, ref_row = star_msa_ref(seqs, win, *scoring)

@@ -29,23 +29,10 @@ def _run(eng, pack, reads_c, L, chunks, **kw):
 
 
 def _records(pack, info, hi):
-    from oracle import oracle
-    r1 = int(np.searchsorted(info["read_start"], hi + 400))
-    s, e = info["read_start"][:r1], info["read_end"][:r1]
-    slot = pack.reads["slot_off"][:r1 + 1].cpu().numpy()
-    codes = pack.codes[:int(slot[-1])].cpu().numpy()
-    ev_off = pack.events["ev_off"][:r1 + 1].cpu().numpy()
-    ev_pos = pack.events["ev_pos"][:int(ev_off[-1])].cpu().numpy()
-    ev_len = pack.events["ev_len"][:int(ev_off[-1])].cpu().numpy()
-    ins_off = info["tensors"]["ins_off"][:int(ev_off[-1]) + 1].cpu().numpy()
-    ins = info["tensors"]["ins_bases"][:max(int(ins_off[-1]), 1)].cpu().numpy()
-    recs = oracle.records_from_indel_pack(
-        s, e, lambda r: codes[int(slot[r]) + (int(s[r]) & 15):int(slot[r]) + (int(s[r]) & 15) + int(e[r] - s[r])],
-        lambda r: list(zip(ev_pos[ev_off[r]:ev_off[r + 1]].tolist(), ev_len[ev_off[r]:ev_off[r + 1]].tolist())),
-        lambda r, k: ins[ins_off[int(ev_off[r]) + k]:ins_off[int(ev_off[r]) + k + 1]])
-    ref = np.frombuffer(b"AGTCN", np.uint8)[info["tensors"]["ref"][1:hi + 401].cpu().numpy()].tobytes().decode()
-    masked = pack.ref_code[1:hi + 401].cpu().numpy() == 4
-    return recs, "".join(c.lower() if m else c for c, m in zip(ref, masked))
+    from util import IndelReadsHost
+    host = IndelReadsHost(pack, info, hi=hi + 400)
+    recs, _ = host.records(1, hi + 400)                                            # every read from the contig's start: record index = read index
+    return recs, host.ref
 
 
 def _properties(res, x, n, chunks, S, win_size=40):

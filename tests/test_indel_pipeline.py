@@ -16,6 +16,8 @@ from nanocaller_amd import generate_indel_pileups as gip
 from nanocaller_amd.bam import decode_parallel
 
 import bamio
+import oracle_pool
+from util import IndelReadsHost, device_alleles, oracle_alleles
 
 
 @pytest.fixture(scope="module")
@@ -257,7 +259,7 @@ def _same_tuples(got, exp):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant", ["ont", "ont_mincov2_maxcov9", "maxcov300", "pacbio_window", "haploid", "small_chunks", "excluded"])
-def test_device_pipeline_returns_the_host_routes_tuples(world_files, variant, monkeypatch):
+def test_device_pipeline_returns_the_host_routes_tuples(world_files, variant, monkeypatch, capsys):
     w, bam, fa = world_files
     kw, haploid, step = {}, False, 50_000
     if variant == "ont_mincov2_maxcov9":
@@ -290,13 +292,54 @@ def test_device_pipeline_returns_the_host_routes_tuples(world_files, variant, mo
     # ... and on the band (the default) the same sites, with the tensors and alleles of all but a few sites identical (a banded alignment is the
     # full-matrix one unless the optimal path leaves the band without the banded path touching its edge: non-homologous stretches, read ends)
     monkeypatch.delenv("NC_PIPE_BAND")
+    runs = []
+    real = gip.indel_sites_device
+    monkeypatch.setattr(gip, "indel_sites_device", lambda *a, **k: runs.append(real(*a, **k)) or runs[-1])
     band = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=haploid)
-    same = 0
+    monkeypatch.setattr(gip, "indel_sites_device", real)
+    site = [(r, k) for r in runs for k in range(r["n"])]                           # the device's sites in tuple order (chunk-major)
+    assert len(site) == n_sites
+    same, diff, g = 0, [], 0
     for t, e in zip(band, exp):
         assert list(t[0]) == list(e[0])
         for k in range(len(e[0])):
-            same += all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) if isinstance(b, np.ndarray) else a[k] == b[k] for a, b in zip(t[1:], e[1:]))
+            ok = all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) if isinstance(b, np.ndarray) else a[k] == b[k] for a, b in zip(t[1:], e[1:]))
+            same += ok
+            if not ok:
+                diff.append((g, e, k))
+            g += 1
     assert same >= 0.98 * n_sites, (same, n_sites)
+    # every site that differs is explained by the band rules, not by a kernel: the band run is the oracle's banded restatement there, the host
+    # route its full-matrix form, and the two forms differ.  Records: the BAM's, in its order (the pileup order), HP / PS from their tags
+    recs = [rc for rc in bamio.world_to_records(w, None) if not rc["flag"] & 0xF04]
+    beg = np.array([rc["pos0"] + 1 for rc in recs])
+    end = beg + np.array([sum(n for op, n in rc["cigar"] if op in "MDN=X") for rc in recs])
+    hap = np.array([rc["tags"].get("HP", 0) for rc in recs])
+    ps = np.array([rc["tags"].get("PS", 0) for rc in recs])
+    wa = 260 if dct["seq"] == "pacbio" else 160
+    tasks = []
+    for g, e, k in diff:
+        p = int(e[0][k])
+        ids = np.nonzero((beg <= p) & (end > p))[0]
+        for band_form in (True, False):
+            tasks.append(oracle_pool.site_task(p, [recs[i] for i in ids], hap[ids], ps[ids], w.ref, wa, dct["mincov"], dct["maxcov"], haploid=haploid,
+                                               band=band_form))
+    got = oracle_pool.map_sites(tasks)
+    S = 1 if haploid else 3
+    for j, (g, e, k) in enumerate(diff):
+        ob, of = got[2 * j], got[2 * j + 1]
+        assert ob is not None and of is not None, (variant, e[0][k])
+        r, i = site[g]
+        typ = int(r["type"][i])
+        assert np.array_equal(r["x"][i].cpu().numpy().reshape(S, 5, 128, 2), ob["x"]), (variant, e[0][k])
+        assert device_alleles(r, i) == oracle_alleles(ob["cns"], ob["win"], typ) and ob["phase"] == int(r["phase"][i]), (variant, e[0][k])
+        xe = np.asarray(e[1][k]) if haploid else np.stack([np.asarray(e[c][k]) for c in (1, 2, 3)])
+        ale = [e[2][k]] if haploid else e[4][k]
+        assert np.array_equal(xe.reshape(S, 5, 128, 2), of["x"].astype(np.float64)), (variant, e[0][k])
+        assert [None if a is None else (len(a), b) for a, b in ale] == oracle_alleles(of["cns"], of["win"], typ), (variant, e[0][k])
+        assert not np.array_equal(ob["x"], of["x"]) or oracle_alleles(ob["cns"], ob["win"], typ) != oracle_alleles(of["cns"], of["win"], typ), (variant, e[0][k])
+    with capsys.disabled():
+        print("\n[%s] band vs host route (full matrix): %d of %d sites differ, each the oracle's band-vs-full difference" % (variant, len(diff), n_sites))
 
 
 @pytest.mark.gpu
@@ -455,30 +498,6 @@ def test_indel_run_native_text_equals_the_python_rules(world_files, tmp_path, mo
     assert outs[0] == outs[1] and outs[0].count("\n") > 60
 
 
-def _host_sample(pack, reads_c, info, r1):
-    """host copies of the first r1 reads of a synthetic device workload, as callables for oracle.records_from_indel_pack"""
-    s, e = info["read_start"][:r1], info["read_end"][:r1]
-    slot = pack.reads["slot_off"][:r1 + 1].cpu().numpy()
-    codes = pack.codes[:int(slot[-1])].cpu().numpy()
-    ev_off = pack.events["ev_off"][:r1 + 1].cpu().numpy()
-    ev_pos = pack.events["ev_pos"][:int(ev_off[-1])].cpu().numpy()
-    ev_len = pack.events["ev_len"][:int(ev_off[-1])].cpu().numpy()
-    ins_off = info["tensors"]["ins_off"][:int(ev_off[-1]) + 1].cpu().numpy()
-    ins = info["tensors"]["ins_bases"][:int(ins_off[-1])].cpu().numpy()
-
-    def codes_of(r):
-        o = int(slot[r]) + (int(s[r]) & 15)
-        return codes[o:o + int(e[r] - s[r])]
-
-    def ev_of(r):
-        return list(zip(ev_pos[ev_off[r]:ev_off[r + 1]].tolist(), ev_len[ev_off[r]:ev_off[r + 1]].tolist()))
-
-    def ins_of(r, k):
-        a = int(ev_off[r]) + k
-        return ins[ins_off[a]:ins_off[a + 1]]
-    return s, e, codes_of, ev_of, ins_of
-
-
 @pytest.mark.gpu
 def test_device_pipeline_on_the_synthetic_workload_equals_the_oracle_restatement(tmp_path, monkeypatch):
     """the bench workload (generated in HBM, no BAM behind it): sites, tensors, consensus-derived alleles and phase of the device
@@ -499,12 +518,10 @@ def test_device_pipeline_on_the_synthetic_workload_equals_the_oracle_restatement
     assert r["n"] > 80
     x = r["x"].cpu().numpy()
     hi = 100_000
-    r1 = int(np.searchsorted(info["read_start"], hi + 400))
-    s, e, codes_of, ev_of, ins_of = _host_sample(pack, reads_c, info, r1)
-    recs = oracle.records_from_indel_pack(s, e, codes_of, ev_of, ins_of)
-    ref = np.frombuffer(b"AGTCN", np.uint8)[info["tensors"]["ref"].cpu().numpy()[1:]].tobytes().decode()
-    masked = pack.ref_code[1:L + 1].cpu().numpy() == 4
-    ref = "".join(c.lower() if m else c for c, m in zip(ref[:hi + 400], masked[:hi + 400]))      # soft-masked runs: not upper-case AGTC
+    host = IndelReadsHost(pack, info, hi=hi + 400)
+    recs, ids = host.records(1, hi + 400)                                          # every read from the contig's start: record index = read index
+    assert np.array_equal(ids, np.arange(len(recs)))
+    ref = host.ref                                                                 # soft-masked runs: not upper-case AGTC
     alt_all = np.frombuffer(b"AGTCN", np.uint8)[r["alt"]].tobytes().decode()
     aoff = np.zeros(r["n"] * 3 + 1, np.int64)
     np.cumsum(np.maximum(r["alt_len"].reshape(-1), 0), out=aoff[1:])
@@ -626,7 +643,7 @@ def test_a_contig_of_one_group_after_a_contig_of_several_allocates_nothing(monke
 
 
 @pytest.mark.gpu
-def test_banded_star_alignment_against_the_full_matrix(monkeypatch):
+def test_banded_star_alignment_against_the_full_matrix(monkeypatch, capsys):
     """the default (every read window aligned on the 32 / 64 diagonals its own CIGAR allows, full matrix after an edge touch) against the
     full matrix for every window: same sites, and all but a few per ten thousand tensors / alleles identical; most windows fit 32 diagonals"""
     import torch
@@ -651,9 +668,31 @@ def test_banded_star_alignment_against_the_full_matrix(monkeypatch):
     assert f["n"] == b["n"] > 3000
     for k in ("pos", "chunk", "type", "phase"):
         assert np.array_equal(np.asarray(f[k]), np.asarray(b[k])), k
-    dx = int((f["x"] != b["x"]).reshape(f["n"], -1).any(1).sum())
+    xd = (f["x"] != b["x"]).reshape(f["n"], -1).any(1).cpu().numpy()
+    dx = int(xd.sum())
     dal = int(((f["ref_len"] != b["ref_len"]) | (f["alt_len"] != b["alt_len"])).any(1).sum())
     assert dx <= 0.002 * f["n"] and dal <= 0.002 * f["n"], (dx, dal, f["n"])
+    # every site where the two runs differ (tensor, or REF / ALT) is explained by the band rules, not by a kernel: the banded run is the oracle's
+    # banded restatement there, the full-matrix run its full-matrix form, and the two forms differ
+    diff = [k for k in range(f["n"]) if xd[k] or device_alleles(f, k) != device_alleles(b, k)]
+    tasks = []
+    if diff:
+        host = IndelReadsHost(pack, info, hi=int(f["pos"][diff[-1]]))
+        for k in diff:
+            p = int(f["pos"][k])
+            recs, ids = host.records(p, p)
+            for band in (True, False):
+                tasks.append(oracle_pool.site_task(p, recs, host.hap[ids], host.ps[ids], host.ref, 160, 4, 160, band=band))
+    got = oracle_pool.map_sites(tasks)
+    for j, k in enumerate(diff):
+        ob, of = got[2 * j], got[2 * j + 1]
+        p, typ = int(f["pos"][k]), int(f["type"][k])
+        assert ob is not None and of is not None, p
+        assert np.array_equal(b["x"][k].cpu().numpy().reshape(3, 5, 128, 2), ob["x"]) and device_alleles(b, k) == oracle_alleles(ob["cns"], ob["win"], typ), p
+        assert np.array_equal(f["x"][k].cpu().numpy().reshape(3, 5, 128, 2), of["x"]) and device_alleles(f, k) == oracle_alleles(of["cns"], of["win"], typ), p
+        assert not np.array_equal(ob["x"], of["x"]) or oracle_alleles(ob["cns"], ob["win"], typ) != oracle_alleles(of["cns"], of["win"], typ), p
+    with capsys.disabled():
+        print("\nband vs full matrix: %d of %d sites differ (%d in the tensor), each the oracle's band-vs-full difference" % (len(diff), f["n"], dx))
 
 
 @pytest.mark.gpu

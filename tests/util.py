@@ -98,3 +98,79 @@ def indel_scan_cases(haploid=False):
                         ins_t=float(z["s%d_ins_t" % k]), del_t=float(z["s%d_del_t" % k]),
                         exclude=[(int(a), int(b)) for a, b in z["s%d_excl" % k]], pos=z["s%d_pos" % k], type=z["s%d_type" % k]))
     return out
+
+
+class IndelReadsHost:
+    """Host copies of the reads of a synthetic device workload (synth_device.make_indel_device_workload) that start at or before `hi`
+    (default: all of them), and the oracle's SAM-like records rebuilt from them (oracle.records_from_indel_pack) for the reads that
+    overlap any [lo, hi].  Records keep the workload's read order -- the pipeline's pileup order, which the first-maxcov cut of a read
+    set follows -- and come with the reads' global indices, HP and PS."""
+
+    def __init__(self, pack, info, hi=None):
+        s, e = info["read_start"], info["read_end"]
+        r1 = len(s) if hi is None else int(np.searchsorted(s, hi, side="right"))
+        self.s, self.e = s[:r1], e[:r1]
+        self.hap, self.ps = np.asarray(info["hap"])[:r1], np.asarray(info["ps"])[:r1]
+        self.slot = pack.reads["slot_off"][:r1 + 1].cpu().numpy()
+        self.codes = pack.codes[:int(self.slot[-1])].cpu().numpy()
+        self.ev_off = pack.events["ev_off"][:r1 + 1].cpu().numpy()
+        n_ev = int(self.ev_off[-1])
+        self.ev_pos = pack.events["ev_pos"][:n_ev].cpu().numpy()
+        self.ev_len = pack.events["ev_len"][:n_ev].cpu().numpy()
+        self.ins_off = info["tensors"]["ins_off"][:n_ev + 1].cpu().numpy()
+        self.ins = info["tensors"]["ins_bases"][:max(int(self.ins_off[-1]), 1)].cpu().numpy()
+        self.length = int(info["L"])
+        # the reference as the oracle reads it: 1-based positions up to the last read's end (+ a window), soft-masked runs in lower case
+        n = min(self.length, int(self.e.max()) + 400 if r1 else 0)
+        ref = info["tensors"]["ref"][1:n + 1].cpu().numpy()
+        masked = pack.ref_code[1:n + 1].cpu().numpy() == 4
+        self.ref = np.where(masked, np.frombuffer(b"agtcn", np.uint8)[ref], np.frombuffer(b"AGTCN", np.uint8)[ref]).tobytes().decode()
+
+    def overlapping(self, lo, hi):
+        """global indices of the reads with start <= hi and end > lo, ascending"""
+        r1 = int(np.searchsorted(self.s, hi, side="right"))
+        return np.nonzero(self.e[:r1] > lo)[0]
+
+    def records(self, lo, hi):
+        """-> (records, read ids): oracle records of the reads overlapping [lo, hi], in read order"""
+        from oracle import oracle
+        ids = self.overlapping(lo, hi)
+        s, e, slot, ev_off = self.s, self.e, self.slot, self.ev_off
+
+        def codes_of(j):
+            r = ids[j]
+            o = int(slot[r]) + (int(s[r]) & 15)
+            return self.codes[o:o + int(e[r] - s[r])]
+
+        def ev_of(j):
+            r = ids[j]
+            return list(zip(self.ev_pos[ev_off[r]:ev_off[r + 1]].tolist(), self.ev_len[ev_off[r]:ev_off[r + 1]].tolist()))
+
+        def ins_of(j, k):
+            a = int(ev_off[ids[j]]) + k
+            return self.ins[self.ins_off[a]:self.ins_off[a + 1]]
+        return oracle.records_from_indel_pack(s[ids], e[ids], codes_of, ev_of, ins_of), ids
+
+
+def device_alleles(r, k):
+    """[(REF length, ALT string) or None per read set] of site k of a fetched gip.indel_sites_device result"""
+    S = r["sets"]
+    if "_aoff" not in r:
+        r["_aoff"] = np.concatenate([[0], np.cumsum(np.maximum(np.asarray(r["alt_len"]).reshape(-1), 0))])
+        r["_alt"] = np.frombuffer(b"AGTCN", np.uint8)[np.asarray(r["alt"])].tobytes().decode()
+    out = []
+    for t in range(S):
+        rl, al, o = int(r["ref_len"][k, t]), int(r["alt_len"][k, t]), int(r["_aoff"][k * S + t])
+        out.append(None if rl < 0 else (rl, r["_alt"][o:o + al]))
+    return out
+
+
+def oracle_alleles(cns, win, var_type):
+    """device_alleles' form of allele_prediction on the oracle's consensus strings (max_range 40 for a type-0 site, else 10)"""
+    from nanocaller_amd import generate_indel_pileups as gip
+    out = []
+    for c in cns:
+        ref, alt = gip.allele_prediction(c, win, 40 if var_type == 0 else 10)
+        assert ref is None or ref == win[:len(ref)]
+        out.append(None if ref is None else (len(ref), alt))
+    return out
