@@ -258,6 +258,32 @@ int nc_inflate_device_phase(nc_ctx *ctx, int32_t phase, int32_t n_blocks, const 
 int nc_bgzf_crc_device(nc_ctx *ctx, int32_t n_blocks, const uint8_t *d_comp, const int64_t *d_coff, const int32_t *d_clen, const uint8_t *d_out,
                        const int64_t *d_ooff, const int32_t *d_isize, int32_t *d_status);
 
+/* Writing BAM on the device (csrc/nc_bamwrite.hip): the haplotagged BAM of phase_run (nanocaller_src/indelCaller.py:243-246, `whatshap haplotag
+ * | samtools view -b --write-index`) from the inflated record stream in HBM.  All pointers dev; every call runs on the context's stream.
+ * nc_bam_retag_sizes: d_rec_off = n_rec record starts in d_raw (their block_size field); d_hash [n_tags] ascending FNV-1a read-name hashes
+ *   of a haplotag table, d_ps its PS values.  -> d_new_size = bytes of each record once its HP / PS / PC fields are dropped and, when its
+ *   name is in the table, HP (type C) and PS (the smallest of C / S / I that holds it; c / s / i below zero) are appended; d_tag_idx = the
+ *   table row or -1; d_out_off [n_rec + 1] = exclusive prefix sums of d_new_size (the last: the total).  d_status (one int32, zeroed by the
+ *   caller): bit 0 a record whose fixed fields do not fit its block_size, bit 1 an aux field that runs past it or has an unknown type.
+ * nc_bam_retag: the records, so re-tagged, at d_out + d_out_off[i] (every other byte as it was; block_size updated).  After
+ *   nc_bam_retag_sizes reported status 0.
+ * nc_bgzf_deflate_device: member b = d_in + d_ioff[b], d_ilen[b] <= 65,280 bytes -> one raw-deflate stream (a dynamic-Huffman block, or a
+ *   stored block when that is not larger) at d_out + d_ooff[b] (room for 65,536 bytes), d_clen[b] bytes; d_crc (NULL: not computed) [b] =
+ *   CRC-32 of the member's bytes; d_status[b] = 0, or 1 for a length out of range.
+ * nc_bgzf_crc32_device: the CRC-32s alone.
+ * nc_bgzf_assemble_device: d_foff [n + 1] = where every member starts in the BGZF file image (exclusive prefix sums of 26 + d_clen), the
+ *   last = where the EOF block goes; with d_file != NULL also the image: per member the gzip header with the BC field, the payload from
+ *   d_pay + d_poff[b], the CRC-32 d_crc[b] and ISIZE d_isize[b] (SAMv1 4.1); the 28-byte EOF block behind them (d_foff[n] + 28 bytes). */
+int nc_bam_retag_sizes(nc_ctx *ctx, const uint8_t *d_raw, int32_t n_rec, const int64_t *d_rec_off, const uint64_t *d_hash, const int32_t *d_ps,
+                       int32_t n_tags, int32_t *d_new_size, int32_t *d_tag_idx, int64_t *d_out_off, int32_t *d_status);
+int nc_bam_retag(nc_ctx *ctx, const uint8_t *d_raw, int32_t n_rec, const int64_t *d_rec_off, const uint8_t *d_hp, const int32_t *d_ps,
+                 const int32_t *d_tag_idx, const int64_t *d_out_off, uint8_t *d_out);
+int nc_bgzf_deflate_device(nc_ctx *ctx, int32_t n, const uint8_t *d_in, const int64_t *d_ioff, const int32_t *d_ilen, uint8_t *d_out,
+                           const int64_t *d_ooff, int32_t *d_clen, uint32_t *d_crc, int32_t *d_status);
+int nc_bgzf_crc32_device(nc_ctx *ctx, int32_t n, const uint8_t *d_in, const int64_t *d_ioff, const int32_t *d_ilen, uint32_t *d_crc);
+int nc_bgzf_assemble_device(nc_ctx *ctx, int32_t n, const uint8_t *d_pay, const int64_t *d_poff, const int32_t *d_clen, const uint32_t *d_crc,
+                            const int32_t *d_isize, int64_t *d_foff, uint8_t *d_file);
+
 /* BAM records on the device (csrc/nc_ingest.hip): from the inflated BGZF stream in HBM to the slots of the read pack, for the SNP route --
  * what nc_bam_decode + nc_pack_fill do on host threads (generate_SNP_pileups.py:134-164's input).
  * nc_bgzf_members (host): the members of a BGZF file image: payload offset / length and inflated size of each (the arguments of

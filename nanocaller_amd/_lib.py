@@ -44,6 +44,7 @@ EXPORTS = [
     "nc_decoded_check", "nc_indel_pack_build", "nc_indel_pack_view", "nc_indel_pack_free", "nc_indel_sites_plan", "nc_indel_sites_run",
     "nc_indel_sites_fetch", "nc_indel_sites_fetch_alt", "nc_indel_sites_stage_ms", "nc_indel_sites_band_stats", "nc_indel_sites_band", "nc_indel_events_pack", "nc_indel_events_expand", "nc_inflate_device", "nc_inflate_device_phase", "nc_bgzf_crc_device", "nc_bgzf_members", "nc_bgzf_scan", "nc_bam_walk", "nc_bam_meta", "nc_bam_codes", "nc_bam_indel_reads", "nc_indel_sites_scoring", "nc_indel_vcf_format", "nc_synth_indel_truth", "nc_synth_indel_reads", "nc_cnn_x_limit", "nc_cnn_range_watch", "nc_snp_trunk_info",
     "nc_snp_phase_gather", "nc_snp_phase_load", "nc_snp_phase_solve", "nc_haplotag_run", "nc_snp_phase_view", "nc_snp_phase_free",
+    "nc_bam_retag_sizes", "nc_bam_retag", "nc_bgzf_deflate_device", "nc_bgzf_crc32_device", "nc_bgzf_assemble_device",
 ]
 
 
@@ -260,6 +261,11 @@ def lib():
         L.nc_haplotag_run.argtypes = [vp, vp, i32, vp]
         L.nc_snp_phase_view.argtypes = [vp, C.POINTER(PhaseArraysC)]
         L.nc_snp_phase_free.argtypes = [vp]
+        L.nc_bam_retag_sizes.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.nc_bam_retag.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.nc_bgzf_deflate_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.nc_bgzf_crc32_device.argtypes = [vp, i32, vp, vp, vp, vp]
+        L.nc_bgzf_assemble_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

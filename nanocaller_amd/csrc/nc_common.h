@@ -50,6 +50,8 @@ struct nc_ctx {
     bool cnn_exact_fp32 = false;   // false: fp16x3 split-precision trunk (default); true: exact fp32 MFMA trunk
     bool k10_lds_set[2] = {false, false};   // k10_indel_trunk_h3<15 / 5>: dynamic LDS limit raised on this device
     bool huff_lds_set = false;              // k_huff: the same
+    bool deflate_lds_set = false;           // k_deflate (nc_bamwrite.hip): the same
+    DevBuf deflate_tok;                     // k_deflate's token slots: 65,536 per workgroup
     size_t k7_budget = 0;                   // bytes of K7 workspace per group of chunks (set from this context's device at its first plan)
     // alignments that share a read name (nc_snp_set_mates): borrowed device pointers, read by the next nc_snp_featurize calls
     int32_t n_mates = 0;

@@ -417,6 +417,33 @@ class Engine:
         finally:
             L.nc_snp_phase_free(h)
 
+    # ---- writing BAM (csrc/nc_bamwrite.hip; bam_write.py).  Device tensors in and out, on the context's stream.
+    def bam_retag_sizes(self, raw, rec_off, thash, tps, new_size, tag_idx, out_off, status, raw_byte_off=0):
+        """new size, table row and output offset of every record (nc_bam_retag_sizes); thash int64 tensor of the uint64 hashes, ascending"""
+        self._check(self.L.nc_bam_retag_sizes(self.ctx, C.c_void_p(raw.data_ptr() + raw_byte_off), int(rec_off.numel()), _ptr(rec_off),
+                                              _ptr(thash) if thash.numel() else None, _ptr(tps) if tps.numel() else None, int(thash.numel()),
+                                              _ptr(new_size), _ptr(tag_idx), _ptr(out_off), _ptr(status)), "nc_bam_retag_sizes")
+
+    def bam_retag(self, raw, rec_off, thp, tps, tag_idx, out_off, out, out_byte_off=0, raw_byte_off=0):
+        """the re-tagged records at out + out_byte_off + out_off[i] (nc_bam_retag)"""
+        self._check(self.L.nc_bam_retag(self.ctx, C.c_void_p(raw.data_ptr() + raw_byte_off), int(rec_off.numel()), _ptr(rec_off),
+                                        _ptr(thp) if thp.numel() else None, _ptr(tps) if tps.numel() else None, _ptr(tag_idx), _ptr(out_off),
+                                        C.c_void_p(out.data_ptr() + out_byte_off)), "nc_bam_retag")
+
+    def bgzf_deflate(self, data, ioff, ilen, out, ooff, clen, status, crc=None):
+        """raw-deflate payload of every member data[ioff[b] : ioff[b] + ilen[b]] at out[ooff[b]:], clen[b] bytes (nc_bgzf_deflate_device);
+        crc: also their CRC-32s"""
+        self._check(self.L.nc_bgzf_deflate_device(self.ctx, int(ioff.numel()), _ptr(data), _ptr(ioff), _ptr(ilen), _ptr(out), _ptr(ooff), _ptr(clen),
+                                                  _ptr(crc), _ptr(status)), "nc_bgzf_deflate_device")
+
+    def bgzf_crc32(self, data, ioff, ilen, crc):
+        self._check(self.L.nc_bgzf_crc32_device(self.ctx, int(ioff.numel()), _ptr(data), _ptr(ioff), _ptr(ilen), _ptr(crc)), "nc_bgzf_crc32_device")
+
+    def bgzf_assemble(self, pay, poff, clen, crc, isize, foff, file=None):
+        """member offsets foff [n + 1] in the BGZF file image; with `file`, the image itself (nc_bgzf_assemble_device)"""
+        self._check(self.L.nc_bgzf_assemble_device(self.ctx, int(clen.numel()), _ptr(pay), _ptr(poff), _ptr(clen), _ptr(crc), _ptr(isize), _ptr(foff),
+                                                   _ptr(file)), "nc_bgzf_assemble_device")
+
     def indel_scan(self, dp: DevicePack, start, end, *, mincov, win_size, small_win_size, ins_t, del_t, excl=None, haploid=False, impute=False):
         """K7 -> int8 [end-start+1] per-column decision (-1 none, 0 long-window rule, 1 small-window rule, 2 impute_indel_phase
         candidate when impute=True)."""

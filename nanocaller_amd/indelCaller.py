@@ -298,7 +298,7 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
     import os
 
     from . import vcfio
-    from .phase import device_phaser_selected
+    from .phase import device_phaser_selected, phased_bam_selected
     from .utils import run_cmd
     contig = contig_dict['name']
     phase_dir = params['intermediate_phase_files_dir']
@@ -325,6 +325,10 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
             haplotags = os.path.join(phase_dir, '%s.haplotags.npz' % contig)
             save_haplotags(haplotags, res.haplotags)
             phased = True
+            if phased_bam_selected(params) and isinstance(sam_path, str):      # :243-246, written on the device (bam_write.py)
+                from .bam_write import write_haplotagged_bam
+                write_haplotagged_bam(sam_path, contig, res.haplotags, os.path.join(phase_dir, '%s.phased.bam' % contig),
+                                      contig_dict['start'], contig_dict['end'], device=device)
         elif _whatshap_available() and isinstance(sam_path, str):
             unph = os.path.join(phase_dir, '%s.snps.unphased.vcf' % contig)
             raw = os.path.join(phase_dir, '%s.snps.phased.raw.vcf' % contig)
@@ -452,9 +456,11 @@ def call_manager(params, devices=None, aligner=None):
             tagged = os.path.join(params['intermediate_phase_files_dir'], '%s.phased.bam' % name)
             tags = os.path.join(params['intermediate_phase_files_dir'], '%s.haplotags.npz' % name)
             for chunk in indel_dict.pop(name):
-                chunk['sam_path'] = tagged if os.path.exists(tagged) else params['sam_path']
-                if os.path.exists(tags):                                       # the device phaser's haplotags (phase_run)
+                if os.path.exists(tags):                                       # the device phaser's haplotags (phase_run): the table route,
+                    chunk['sam_path'] = params['sam_path']                     # whether or not it also wrote <contig>.phased.bam
                     chunk['haplotags'] = tags
+                else:
+                    chunk['sam_path'] = tagged if os.path.exists(tagged) else params['sam_path']
                 job_Q.put(('indel', chunk))
     caller(params, job_Q, counter_Q, indel_dict, phased_snp_files_list, indel_files_list, device=device, worker_id=rank + 1,
            aligner=aligner)

@@ -29,6 +29,14 @@ def device_phaser_selected(params) -> bool:
     return os.environ.get("NC_PHASER") == "device"
 
 
+def phased_bam_selected(params) -> bool:
+    """params['phased_bam'] truthy; without that key, the environment's NC_PHASED_BAM == '1' (phase_run writes <contig>.phased.bam behind
+    the device phaser: bam_write.py)"""
+    if "phased_bam" in params:
+        return bool(params["phased_bam"])
+    return os.environ.get("NC_PHASED_BAM") == "1"
+
+
 def name_hash(names) -> np.ndarray:
     """FNV-1a (64 bit) of every read name with its terminating NUL: the hash of the BAM record's read_name field, as the device
     ingest computes it (nc_ingest.hip, meta rows M_HASH_LO / M_HASH_HI)"""
