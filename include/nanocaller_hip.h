@@ -830,6 +830,15 @@ int nc_synth_indel_reads(nc_ctx *ctx, int64_t L, uint64_t seed, double p_sub, do
  * nc_snp_phase_gather: the alleles of the kept reads of a resident pack (codes dev; rd_start / rd_end (exclusive) / slot_off dev, the
  *   pack's read table: read r's code at position p is codes[slot_off[r] + (rd_start[r] & 15) + p - rd_start[r]]) -> a phasing handle
  *   holding the read -> (site, allele) CSR, on the device and on the host.  Site arrays are host.
+ * nc_snp_phase_realign: the same handle with the alleles detected by local realignment instead of the column code (WhatsHap's
+ *   realignment mode with its default overhang of 10 and unit-cost edit distance, restated in DESIGN.md): for a read whose alignment covers
+ *   the reference window p - 10 .. p + 10 of a site (cut at the contig's ends, no N in it), the read's own bases over those columns (its
+ *   insertions between them included, its deleted columns left out; the pack's codes, `reads`' events and inserted bases) are compared by
+ *   Levenshtein distance with the window carrying the first and the second allele: the closer one is the read's allele, a tie or a query
+ *   window of more than 64 bases gives none.  codes / reads' arrays dev as nc_indel_sites_plan takes them (tails, PS and HP are not read;
+ *   read_flag may be NULL), n_events / n_ins_bases the lengths of ev_pos and ins_bases; ref_code dev [ref_len]: the code of position p at
+ *   index p - 1, A0 G1 T2 C3 in either letter case, 4 otherwise.  NC_ERR_ARG when a read's events or inserted bases point outside their
+ *   arrays (checked on the device, nothing out of bounds is read).
  * nc_snp_phase_load: the same handle from a host CSR (entry_off [n_reads + 1], entry_site ascending per read, entry_allele 0 / 1).
  * nc_snp_phase_solve: read selection (max_cov in [1, 15]), blocks, slots (host) and the DP (one workgroup per block).  NC_ERR_CAPACITY
  *   when a partition cost exceeds the DP's 16-bit relative range.
@@ -857,6 +866,8 @@ typedef struct {
 } nc_phase_arrays;
 int nc_snp_phase_gather(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, int32_t n_reads, const int32_t *rd_start, const int32_t *rd_end,
                         const int64_t *slot_off, int32_t n_sites, const int32_t *site_pos, const uint8_t *site_alleles, nc_phase **out);
+int nc_snp_phase_realign(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, const nc_indel_reads *reads, int64_t n_events, int64_t n_ins_bases,
+                         const uint8_t *ref_code, int32_t ref_len, int32_t n_sites, const int32_t *site_pos, const uint8_t *site_alleles, nc_phase **out);
 int nc_snp_phase_load(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32_t *site_pos, const int64_t *entry_off, const int32_t *entry_site,
                       const uint8_t *entry_allele, nc_phase **out);
 int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov);

@@ -5,11 +5,12 @@
 //   k_hp_gather<false>  per read: the number of its alleles at the het sites (code == first / second allele)
 //   k_hp_scan           one workgroup: exclusive prefix of those counts (nc_wave_incl_scan) -> read -> entry offsets
 //   k_hp_gather<true>   per read: the (site, allele) CSR entries
+//   (nc_hprealign.hip)  instead of k_hp_gather, opt-in: the alleles by local realignment of the read against both haplotypes
 //   host                read selection (max_cov), blocks, slot assignment, per-column masks, backtrace offsets
 //   k_hp_dp             one workgroup per block: the 2^15 partition costs in LDS (uint16, relative to the column minimum),
 //                       leaving slots minimised out, backtrace in HBM, traceback by the same workgroup
 //   k_hp_tag            one thread per read-name group: per-block scores -> HP / PS
-#include "nc_common.h"
+#include "nc_happhase.h"
 
 #include <algorithm>
 #include <chrono>
@@ -20,7 +21,6 @@ namespace {
 
 constexpr int HP_SLOTS = 15;
 constexpr int HP_STATES = 1 << HP_SLOTS;
-constexpr int HP_THREADS = 1024;
 
 struct HpCol {            // one column of a block: the active slots, those continuing from the previous column, the allele masks
     uint16_t act, keep, m0, m1;
@@ -51,16 +51,6 @@ __device__ __forceinline__ uint32_t hp_wave_min(uint32_t v)
     return v;
 }
 
-__device__ __forceinline__ int32_t hp_lower_bound(const int32_t *a, int32_t lo, int32_t hi, int32_t v)
-{
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // one thread per kept read; codes of read r at position p: codes[slot_off[r] + (start & 15) + p - start]
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_hp_gather(const uint8_t *__restrict__ codes, int32_t n_reads, const int32_t *__restrict__ rs,
@@ -87,29 +77,6 @@ __global__ __launch_bounds__(256) void k_hp_gather(const uint8_t *__restrict__ c
         }
     }
     if (!FILL) cnt[r] = n;
-}
-
-__global__ __launch_bounds__(HP_THREADS) void k_hp_scan(const int32_t *__restrict__ cnt, int32_t n, int64_t *__restrict__ off)
-{
-    __shared__ int32_t wsum[HP_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int64_t carry = 0;
-    if (tid == 0) off[0] = 0;
-    for (int32_t base = 0; base < n; base += HP_THREADS) {
-        const int32_t i = base + tid;
-        const int32_t inc = nc_wave_incl_scan(i < n ? cnt[i] : 0);
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int32_t pre = 0, tot = 0;
-        for (int k = 0; k < HP_THREADS / 64; k++) {
-            const int32_t s = wsum[k];
-            pre += k < w ? s : 0;
-            tot += s;
-        }
-        if (i < n) off[i + 1] = carry + pre + inc;
-        carry += tot;
-        __syncthreads();
-    }
 }
 
 // One workgroup per block [bfirst, blast] of columns (= sites).  D(j, B) for the subsets B of the active slots lives in LDS as
@@ -280,31 +247,7 @@ __global__ __launch_bounds__(256) void k_hp_tag(int32_t n_groups, const int32_t 
     gps[g] = hp ? best_ps : 0;
 }
 
-double hp_now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
-
-struct nc_phase {
-    nc_ctx *ctx = nullptr;
-    int32_t n_reads = 0, n_sites = 0, n_groups = 0;
-    std::vector<int32_t> site_pos;
-    std::vector<int64_t> off;
-    std::vector<int32_t> esite;
-    std::vector<uint8_t> eal;
-    int64_t *d_off = nullptr;
-    int32_t *d_site = nullptr;
-    uint8_t *d_al = nullptr;
-    std::vector<int8_t> side;
-    std::vector<int32_t> site_block, site_ps, block_first, block_last, block_ps;
-    std::vector<uint8_t> site_h, site_phased, group_hp;
-    std::vector<int64_t> block_cost;
-    std::vector<int32_t> group_ps;
-    float ms[4] = {0, 0, 0, 0};
-    bool solved = false;
-};
 
 static void hp_free_dev(nc_phase *ph)
 {
@@ -315,25 +258,6 @@ static void hp_free_dev(nc_phase *ph)
     ph->d_site = nullptr;
     ph->d_al = nullptr;
 }
-
-// device scratch of one call, released on every return path
-struct HpScratch {
-    std::vector<void *> p;
-    ~HpScratch()
-    {
-        for (void *q : p) (void)hipFree(q);
-    }
-    template <class T>
-    int get(nc_ctx *ctx, T **out, size_t n)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, n * sizeof(T) + 16);
-        if (e != hipSuccess) return nc_fail(ctx, NC_ERR_NOMEM, "hipMalloc(%zu) failed: %s", n * sizeof(T), hipGetErrorString(e));
-        p.push_back(q);
-        *out = (T *)q;
-        return NC_OK;
-    }
-};
 
 static int hp_upload_csr(nc_phase *ph)
 {
@@ -348,13 +272,6 @@ static int hp_upload_csr(nc_phase *ph)
         NC_HIP(ctx, hipMemcpyAsync(ph->d_al, ph->eal.data(), ne, hipMemcpyHostToDevice, ctx->stream));
     }
     NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NC_OK;
-}
-
-static int hp_check_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *pos)
-{
-    for (int32_t s = 1; s < n_sites; s++)
-        if (pos[s] <= pos[s - 1]) return nc_fail(ctx, NC_ERR_ARG, "phasing sites must ascend strictly (site %d)", s);
     return NC_OK;
 }
 

@@ -380,14 +380,24 @@ class Engine:
         self._check(self.L.nc_indel_forward(self.ctx, kind, n, _ptr(x), _ptr(probs)), "nc_indel_forward")
         return probs
 
-    def snp_phase(self, site_pos, site_alleles, read_group, n_groups, *, max_cov=15, reads=None, csr=None) -> dict:
+    def snp_phase(self, site_pos, site_alleles, read_group, n_groups, *, max_cov=15, reads=None, csr=None, realign=None) -> dict:
         """Read-based phasing + haplotags (nc_snp_phase_*, nc_haplotag_run) -> dict of host arrays (see nc_phase_arrays).
         reads: (codes, rd_start, rd_end, slot_off) device tensors of a resident pack's kept reads (alleles gathered on the device);
-        csr: (entry_off int64, entry_site int32, entry_allele uint8) host arrays instead."""
+        csr: (entry_off int64, entry_site int32, entry_allele uint8) host arrays instead;
+        realign: (codes, IndelReadsC, n_events, n_ins_bases, ref_code) -- the pack's codes, its read table with the events and the inserted
+        bases, and the contig's reference codes [length] (device uint8, position p at p - 1, 4 = not a base): alleles by local
+        realignment (nc_snp_phase_realign)."""
         L = self.L
         pos = np.ascontiguousarray(site_pos, np.int32)
         h = C.c_void_p()
-        if reads is not None:
+        if realign is not None:
+            codes, reads_c, n_events, n_ins, ref_code = realign
+            al = np.ascontiguousarray(site_alleles, np.uint8).reshape(-1, 2)
+            torch.cuda.current_stream(self.device).synchronize()
+            rc = L.nc_snp_phase_realign(self.ctx, _ptr(codes), codes.numel(), C.byref(reads_c), int(n_events), int(n_ins), _ptr(ref_code),
+                                        int(ref_code.numel()), pos.size, _lib.npp(pos), _lib.npp(al), C.byref(h))
+            self._check(rc, "nc_snp_phase_realign")
+        elif reads is not None:
             codes, rs, re_, so = reads
             al = np.ascontiguousarray(site_alleles, np.uint8).reshape(-1, 2)
             torch.cuda.current_stream(self.device).synchronize()            # (the pack's upload may still be in flight on torch's stream)

@@ -294,7 +294,8 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
     then release the contig's indel chunks with chunk['sam_path'] = the haplotagged BAM (or params['sam_path']).
     With the built-in phaser selected (params['phaser'] = 'device', or NC_PHASER=device without that key; phase.py) the confident
     SNPs are phased on `device` from the contig's resident reads, the haplotags go to <contig>.haplotags.npz and the contig's
-    indel chunks carry chunk['haplotags'] = that file beside chunk['sam_path'] = params['sam_path']."""
+    indel chunks carry chunk['haplotags'] = that file beside chunk['sam_path'] = params['sam_path'].  params['phase_realign'] (or
+    NC_PHASE_REALIGN=1 without that key) makes that phaser detect the reads' alleles by local realignment (phase.phase_contig(realign=True))."""
     import os
 
     from . import vcfio
@@ -319,8 +320,9 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
         phased = False
         haplotags = None
         if device_phaser_selected(params):
-            from .phase import phase_contig, save_haplotags
-            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device)
+            from .phase import phase_contig, phase_realign_selected, save_haplotags
+            realign = dict(realign=True) if phase_realign_selected(params) else {}      # (off: the call as it always was)
+            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device, **realign)
             vcfio.write_sorted_vcf(out_vcf, _with_phase_format(header), res.records, [contig])
             haplotags = os.path.join(phase_dir, '%s.haplotags.npz' % contig)
             save_haplotags(haplotags, res.haplotags)

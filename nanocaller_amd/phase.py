@@ -6,7 +6,8 @@ algorithm (an exact minimum-error-correction phaser, WhatsHap's model, every tie
 decoded twice) and returns the phased records, the blocks and a haplotag table: per read NAME its 64-bit FNV-1a hash (the hash
 the device ingest's record meta carries), HP and PS.  The indel pass takes HP / PS from such a table instead of the BAM's own tags
 when a chunk carries `haplotags` (`TaggedBam`).  Opt-in: params['phaser'] = 'device', or NC_PHASER=device when params has no
-'phaser' key (`device_phaser_selected`).
+'phaser' key (`device_phaser_selected`).  Behind it, params['phase_realign'] / NC_PHASE_REALIGN=1 (`phase_realign_selected`) selects the
+alleles by local realignment (WhatsHap's `--reference` mode restated) instead of the pileup column's code.
 """
 from __future__ import annotations
 
@@ -35,6 +36,14 @@ def phased_bam_selected(params) -> bool:
     if "phased_bam" in params:
         return bool(params["phased_bam"])
     return os.environ.get("NC_PHASED_BAM") == "1"
+
+
+def phase_realign_selected(params) -> bool:
+    """params['phase_realign'] truthy; without that key, the environment's NC_PHASE_REALIGN == '1' (the device phaser takes a read's allele
+    at a site from a local realignment against both haplotypes instead of the code in the site's column: `phase_contig(realign=True)`)"""
+    if "phase_realign" in params:
+        return bool(params["phase_realign"])
+    return os.environ.get("NC_PHASE_REALIGN") == "1"
 
 
 def name_hash(names) -> np.ndarray:
@@ -120,9 +129,44 @@ def kept_reads(world: World, supplementary):
     return kept, rs, re_, slot
 
 
-def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, supplementary=False, max_cov=15, device=0) -> PhaseResult:
+def _ref_codes(fasta: str) -> np.ndarray:
+    """uint8 [L]: A0 G1 T2 C3 in either letter case, 4 otherwise (position p at index p - 1)"""
+    lut = np.full(256, 4, np.uint8)
+    for k, b in enumerate("AGTC"):
+        lut[ord(b)] = lut[ord(b.lower())] = k
+    return lut[np.frombuffer(fasta.encode("ascii"), np.uint8)]
+
+
+def _realign_inputs(sam_path, fasta_path, chrom, supplementary, device):
+    """what nc_snp_phase_realign reads beside the sites: the contig's pack with its events and inserted bases, as the indel route loads them (from
+    the BAM on the device where that route is open, else from the host decode), and the reference codes -> (pack, Engine.snp_phase's `realign`)"""
+    import torch
+
+    from . import _lib
+    if not (isinstance(sam_path, str) and os.path.exists(sam_path)) or not fasta_path:
+        raise _lib.NanoCallerHipError("phase_contig(realign=True) needs a BAM file and its FASTA: the alignments %r carry no inserted bases to rebuild "
+                                      "the reads' query windows from (the column rule is not substituted)" % (sam_path,))
+    from . import generate_indel_pileups as gip
+    dct = dict(fasta_path=fasta_path, supplementary=bool(supplementary))
+    eng, dp, reads_c, ctg, _ = gip._indel_pack_for(dct, [dict(chrom=chrom, sam_path=sam_path)], device)
+    if ctg.get("device_ingest"):
+        ix = dp.indel
+    else:
+        flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if supplementary else 0x800)
+        ix = ctg[("dev_reads", flag, device)][1]
+    if dp.events is None or dp.reads is None or ix is None:
+        raise _lib.NanoCallerHipError("phase_contig(realign=True): the pack of %r, contig %s, carries no indel events / inserted bases" % (sam_path, chrom))
+    key = ("phase_ref_code", device)
+    if key not in ctg:
+        ctg[key] = torch.from_numpy(_ref_codes(ctg["fasta"])).to(eng.device)
+    return dp, (dp.codes, reads_c, dp.events["ev_pos"].numel(), ix["ins_bases"].numel(), ctg[key])
+
+
+def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, supplementary=False, max_cov=15, device=0, realign=False) -> PhaseResult:
     """Phase the het SNP calls `snp_records` (VCF lines of contig `chrom`) from the reads of `sam_path` (a BAM path, a World or a
-    registered key) and haplotag the reads.  -> PhaseResult"""
+    registered key) and haplotag the reads.  -> PhaseResult
+    realign: a read's allele at a site comes from a local realignment of its bases against the reference window with either allele (DESIGN.md
+    "Read-based phasing", the allele detectors) instead of the code in the site's column; needs a BAM file (the reads' inserted bases)."""
     import torch
 
     from .engine import get_engine
@@ -130,8 +174,12 @@ def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, sup
     eng = get_engine(device)
     eng.use_torch_stream()
     rec_idx, pos, alleles, _ = het_sites(snp_records, phase_qual_score)
+    ra = None
+    if realign:
+        dp, ra = _realign_inputs(sam_path, fasta_path, chrom, supplementary, device)
     world = _resolve(sam_path, chrom, fasta_path)
-    dp = device_pack(sam_path, fasta_path, chrom, bool(supplementary), None, device, by_name=True)[0]
+    if not realign:
+        dp = device_pack(sam_path, fasta_path, chrom, bool(supplementary), None, device, by_name=True)[0]
     kept, rs, re_, slot = kept_reads(world, supplementary)
     if dp.reads is not None:
         if dp.reads["n_reads"] != kept.size:
@@ -150,7 +198,12 @@ def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, sup
     else:                                                               # no names: every alignment is its own read
         hashes = np.zeros(kept.size, np.uint64)
         uniq, group = np.zeros(kept.size, np.uint64), np.arange(kept.size)
-    r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, reads=reads)
+    if realign:
+        if dp.reads is None or ra[1].n_reads != kept.size:
+            raise RuntimeError("phase_contig: the indel read table holds %d reads, the flag filter keeps %d" % (ra[1].n_reads, kept.size))
+        r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, realign=ra)
+    else:
+        r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, reads=reads)
     out = list(snp_records)
     for k in np.flatnonzero(r["site_phased"]).tolist():
         out[int(rec_idx[k])] = phased_record(snp_records[int(rec_idx[k])], int(r["site_h"][k]), int(r["site_ps"][k]))

@@ -1,6 +1,7 @@
 """Wall time of the read-based phaser on a chr20-sized synthetic ONT contig (64.4 Mb, 30x, generated in HBM by nc_synth_indel_*):
 allele gather, read selection + blocks + slots (host), the MEC DP, haplotagging.  The het sites are the generator's own (its truth,
-recomputed from the same seed); every read is its own name.  Prints one JSON line.  Usage: python tools/bench_phase.py [--length L] [--reps N]"""
+recomputed from the same seed); every read is its own name.  --realign: the alleles by local realignment (nc_snp_phase_realign) instead of
+the column gather.  Prints one JSON line.  Usage: python tools/bench_phase.py [--length L] [--reps N] [--realign | --compare N]"""
 import argparse
 import ctypes as C
 import json
@@ -22,11 +23,13 @@ def main():
     ap.add_argument("--depth", type=float, default=30.0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=812)
+    ap.add_argument("--realign", action="store_true")
+    ap.add_argument("--compare", type=int, default=0, help="N interleaved runs of the column gather and of the realignment, medians and their ratio")
     a = ap.parse_args()
     eng = get_engine(0)
     eng.use_torch_stream()
     L = a.length
-    pack, _, info = make_indel_device_workload(eng, L, depth=a.depth, seed=a.seed)
+    pack, reads_c, info = make_indel_device_workload(eng, L, depth=a.depth, seed=a.seed)
     # the generator's haplotype bases (make_indel_device_workload's defaults): het SNP sites and their two alleles
     ref = torch.zeros(L + 1, dtype=torch.uint8, device=eng.device)
     hapb = torch.zeros(2 * (L + 1), dtype=torch.uint8, device=eng.device)
@@ -42,14 +45,39 @@ def main():
     R = info["n_reads"]
     reads = (pack.codes, pack.reads["rd_start"], pack.reads["rd_end"], pack.reads["slot_off"])
     group = np.arange(R, dtype=np.int32)
+    kw = dict(reads=reads)
+    if a.realign:                                                       # reference codes with position p at index p - 1
+        kw = dict(realign=(pack.codes, reads_c, info["n_events"], info["n_ins_bases"], ref[1:].contiguous()))
+    if a.compare:
+        # both allele detectors on the same contig, interleaved, median of `compare` runs each (the column gather is the yardstick)
+        kws = dict(column=dict(reads=reads), realign=dict(realign=(pack.codes, reads_c, info["n_events"], info["n_ins_bases"], ref[1:].contiguous())))
+        eng.snp_phase(het, alleles, group, R, **kws["column"])
+        walls, stages, last = {k: [] for k in kws}, {k: [] for k in kws}, {}
+        for _ in range(a.compare):
+            for k, kw in kws.items():
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                last[k] = eng.snp_phase(het, alleles, group, R, **kw)
+                walls[k].append(time.perf_counter() - t)
+                stages[k].append(last[k]["ms"])
+        med = lambda v: float(np.median(v))                              # noqa: E731
+        out = dict(metric="phase_chr20_sized_realign_over_column", value=round(med(walls["realign"]) / med(walls["column"]), 4), length=L, depth=a.depth,
+                   reads=R, het_sites=int(het.size), runs=a.compare,
+                   pairs=int((np.searchsorted(het, info["read_end"]) - np.searchsorted(het, info["read_start"])).sum()))
+        for k in kws:
+            out[k] = dict(wall_s=round(med(walls[k]), 4), walls_s=[round(x, 4) for x in walls[k]], entries=int(last[k]["entry_site"].size),
+                          phased_sites=int(last[k]["site_phased"].sum()), tagged_reads=int((last[k]["group_hp"] > 0).sum()),
+                          stage_ms={s_: round(med([m[s_] for m in stages[k]]), 3) for s_ in stages[k][0]})
+        print(json.dumps(out))
+        return
     runs = []
     for _ in range(a.reps + 1):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        res = eng.snp_phase(het, alleles, group, R, reads=reads)
+        res = eng.snp_phase(het, alleles, group, R, **kw)
         runs.append((time.perf_counter() - t, res["ms"]))
     wall, ms = min(runs[1:], key=lambda x: x[0])
-    out = dict(metric="phase_chr20_sized_s", value=round(wall, 4), length=L, depth=a.depth, reads=R, het_sites=int(het.size),
+    out = dict(metric="phase_chr20_sized_s", value=round(wall, 4), realign=bool(a.realign), length=L, depth=a.depth, reads=R, het_sites=int(het.size),
                phased_sites=int(res["site_phased"].sum()), blocks=int(res["block_first"].size), entries=int(res["entry_site"].size),
                tagged_reads=int((res["group_hp"] > 0).sum()), stage_ms={k: round(v, 2) for k, v in ms.items()})
     print(json.dumps(out))
