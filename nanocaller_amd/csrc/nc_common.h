@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/nanocaller_hip.h"
 
@@ -23,9 +24,21 @@ __device__ __forceinline__ int32_t nc_wave_incl_scan(int32_t v)
     return v;
 }
 
+// A device allocation owned by the struct that holds it (nc_ensure grows it).  It frees itself with its owner, so nc_ctx and nc_pipe_state are deleted
+// with their device current; no owner keeps a list of its buffers.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
 };
 
 struct nc_weights {
@@ -221,3 +234,9 @@ struct IndelChunk {
     int64_t coloff;      // offset of this chunk's col_type in the concatenated output
     int32_t tile0, blk0; // first tile of the chunk on the pack's grid, first k_hap_depth_b block of the chunk
 };
+// K7 for the device pipeline's plan (nc_pipe.hip): a group of chunks enqueued, col_type left on the device; the argument checks of the scan
+int nc_indel_scan_group_launch(nc_ctx *ctx, const nc_readpack *pack, const nc_indel_events *ev, const uint8_t *excl_dev, int32_t n_chunks,
+                               const int32_t *starts, const int32_t *ends, const nc_indel_scan_params *prm, int32_t *consumed,
+                               std::vector<IndelChunk> &ck, const IndelChunk **ck_dev_out, const int8_t **ctype_out, const int64_t *slot_off_dev, int32_t *err_bits_dev,
+                               const int32_t *rd_start_dev, const int32_t *rd_end_dev, bool reuse_tables);
+int nc_indel_check(nc_ctx *ctx, const nc_readpack *pack, const nc_indel_events *ev, const nc_indel_scan_params *prm, const char *who);

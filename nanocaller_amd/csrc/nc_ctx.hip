@@ -133,26 +133,11 @@ int nc_ctx_create(int device_id, nc_ctx **out)
     return NC_OK;
 }
 
-static void freebuf(DevBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
 int nc_ctx_destroy(nc_ctx *ctx)
 {
     if (!ctx) return NC_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->stage_nbr, &ctx->stage_cpos, &ctx->stage_cn, &ctx->stage_calt, &ctx->tile_cnt,
-                      &ctx->tile_pre, &ctx->nbr_pos, &ctx->cand_pos, &ctx->cand_n, &ctx->cand_alt,
-                      &ctx->chunk_start, &ctx->chunk_end, &ctx->chunk_lo, &ctx->chunk_cnt, &ctx->chunk_off,
-                      &ctx->site_pos, &ctx->site_chunk, &ctx->site_n, &ctx->site_alt, &ctx->totals,
-                      &ctx->cnn_a, &ctx->cnn_b, &ctx->cnn_c, &ctx->chunk_depth, &ctx->nbr_idx, &ctx->indel_ws, &ctx->indel_ent_read,
-                      &ctx->msa_reads, &ctx->msa_read_off, &ctx->msa_read_set, &ctx->msa_refs, &ctx->msa_ref_off, &ctx->msa_rows_hf,
-                      &ctx->msa_hcol, &ctx->msa_tb, &ctx->msa_trace, &ctx->msa_cols, &ctx->msa_out, &ctx->msa_dup, &ctx->deflate_tok};
-    for (DevBuf *b : bufs) freebuf(*b);
     nc_pipe_destroy(ctx);
     for (auto &w : ctx->w) {
         if (w.dev) (void)hipFree(w.dev);
@@ -169,7 +154,7 @@ int nc_ctx_destroy(nc_ctx *ctx)
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->mbox) (void)hipHostFree(ctx->mbox);
     if (ctx->stage_h) (void)hipHostFree(ctx->stage_h);
-    delete ctx;
+    delete ctx;                                                    // (its DevBufs free themselves; the device is still current)
     return NC_OK;
 }
 

@@ -89,7 +89,7 @@ __device__ __forceinline__ uint32_t lut8i(uint32_t x, uint32_t lo, uint32_t hi) 
 
 // All chunks of a call run in the same launches (chunk = a grid dimension), each chunk with its own workspace slice and
 // the reference's per-chunk semantics (window deques start empty at the chunk's first column)
-// IndelChunk: nc_common.h (shared with the device-resident pipeline, nc_pipe.hip)
+// IndelChunk: nc_common.h (shared with the device-resident pipeline, nc_pipe.hip, as are the two entry points its plan calls)
 __device__ __forceinline__ int32_t *ck_depth(char *ws, const IndelChunk &c) { return (int32_t *)(ws + c.ws); }
 __device__ __forceinline__ int32_t *ck_rank(char *ws, const IndelChunk &c) { return (int32_t *)(ws + c.ws) + (int64_t)3 * c.ncol; }
 __device__ __forceinline__ int32_t *ck_diff(char *ws, const IndelChunk &c) { return (int32_t *)(ws + c.ws) + (int64_t)3 * c.ncol + c.ncol + 1; }

@@ -521,7 +521,7 @@ def read_windows_ref(records, anchors, window_before, window_after, flag_filter)
     return out
 
 
-# ---- the banded form of the star alignment (the product's default: nc_pipe.hip k_fill_band / k_trace_band), restated independently.
+# ---- the banded form of the star alignment (the product's default: nc_pipe_align.hip k_fill_band / nc_pipe_trace.hip k_trace_band12), restated independently.
 # The band is derived from the read's own CIGAR inside the window; an alignment whose band would be wider than 64 diagonals, or whose
 # banded path touches an edge diagonal, is the full-matrix alignment (nw_cigar_free_tail_ref).
 BAND_MARGIN = 6

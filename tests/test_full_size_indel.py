@@ -1,4 +1,4 @@
-"""BASELINE.json configs[2] / configs[4] at their sizes for the INDEL half of the path (csrc/nc_pipe.hip), through size-independent
+"""BASELINE.json configs[2] / configs[4] at their sizes for the INDEL half of the path (csrc/nc_pipe.hip, nc_pipe_*.hip), through size-independent
 properties -- the oracle cannot run these sizes in seconds: a chr1-sized ONT 30x contig (248,956,422 bp, 2,490 chunks of 100 kb, ~155 k
 candidate sites, ~4.1 M read windows in three balanced alignment groups) and a chr20-sized contig through the haploid model's shape
 (--haploid_genome: one read set per site) with the 260-base windows of the pacbio preset (banded like the 160-base ones).

@@ -1,4 +1,4 @@
-"""Every alignment class of the device indel pipeline (csrc/nc_pipe.hip) against the oracle's restatement, site by site.
+"""Every alignment class of the device indel pipeline (csrc/nc_pipe.hip, nc_pipe_*.hip) against the oracle's restatement, site by site.
 
 A read window is aligned to its reference window on 32 diagonals, on 64, or on the full matrix (listF): a band too wide for 64 diagonals,
 or a banded path that touched an edge diagonal and was re-run.  The consensus alleles run on a band with a certificate, and on the full

@@ -1,4 +1,4 @@
-"""The device-resident indel path (csrc/nc_pipe.hip: nc_indel_sites_plan / _run / _fetch, rows a10-a15 of SURVEY.md 8a) and its host pieces.
+"""The device-resident indel path (csrc/nc_pipe.hip, nc_pipe_*.hip: nc_indel_sites_plan / _run / _fetch, rows a10-a15 of SURVEY.md 8a) and its host pieces.
 
 CPU: nc_indel_pack_build (bases without a reference column) against a restatement from the decoded query sequences;
 nc_decoded_check (reference skips, same-name overlaps -> NC_ERR_UNSUPPORTED); nc_indel_vcf_format against the Python statement

@@ -33,8 +33,6 @@ for rep in range(reps):
     r = gip.indel_sites_device(eng, pack, reads_c, L, chunks, fetch=False, **kw)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    if os.environ.get("NC_PIPE_STOP_AFTER_FILL"):
-        continue
     probs = eng.indel_forward(_lib.MODEL_INDEL, r["x"])
     torch.cuda.synchronize()
     t2 = time.perf_counter()
@@ -59,8 +57,6 @@ eng.L.nc_indel_sites_stage_ms(eng.ctx, _lib.npp(ms), _lib.npp(cells))
 print("stages (ms): plan %.2f, windows %.2f, fill %.2f, trace %.2f, tensor %.2f, alleles %.2f; DP cells %.3g + %.3g -> fill %.0f Gcells/s"
       % (*ms, cells[0], cells[1], cells[0] / (ms[2] * 1e-3) / 1e9 if ms[2] > 0 else 0), flush=True)
 print("max HBM %.2f GB" % (torch.cuda.max_memory_allocated() / 1e9))
-if os.environ.get("NC_PIPE_STOP_AFTER_FILL"):
-    sys.exit(0)
 # concordance: planted indels (either haplotype) whose length comes back in an allele called at a site up to 60 bp before them
 truth = info["truth"].cpu().numpy()
 tp = np.nonzero((truth[0] != 0) | (truth[1] != 0))[0]

@@ -2,6 +2,8 @@
 """Compare the device ISA of HIP sources kernel by kernel (the gate of a refactor that must not change code generation).
 
     python3 tools/isa_diff.py OLD NEW                      # two .s listings, or two .hip files (compiled here)
+    python3 tools/isa_diff.py OLD -- NEW1 NEW2 ...         # several files a side (a unit that was split): the union of their functions
+    python3 tools/isa_diff.py --rev HEAD --into a.hip,b.hip nanocaller_amd/csrc/nc_pipe.hip      # FILE at REV against the units it was split into
     python3 tools/isa_diff.py --rev HEAD nanocaller_amd/csrc/nc_cnn.hip ...   # each file at REV against the working tree
 
 A .hip file is compiled with `hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only`; with --rev the sources of REV
@@ -81,8 +83,16 @@ def resources(body):
     return r
 
 
+def union(paths):
+    out = {}
+    for p in paths:
+        out.update(functions(p))
+    return out
+
+
 def compare(old_s, new_s, label):
-    a, b = functions(old_s), functions(new_s)
+    """old_s / new_s: a listing or a list of listings"""
+    a, b = union([old_s] if isinstance(old_s, str) else old_s), union([new_s] if isinstance(new_s, str) else new_s)
     bad = renamed = 0
     gone, new = set(a) - set(b), set(b) - set(a)
     for n in sorted(new):
@@ -113,6 +123,7 @@ def compare(old_s, new_s, label):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--rev", help="compare each FILE at this git revision against the working tree")
+    ap.add_argument("--into", help="with --rev: comma-separated working-tree files that replace FILE (default: FILE itself)")
     ap.add_argument("files", nargs="+")
     args = ap.parse_args()
     bad = 0
@@ -128,18 +139,23 @@ def main():
                 od, nd = os.path.join(td, "a"), os.path.join(td, "b")
                 os.makedirs(od, exist_ok=True)
                 os.makedirs(nd, exist_ok=True)
-                bad += compare(compile_listing(os.path.join(old_tree, rel), od), compile_listing(f, nd), os.path.basename(f))
+                new = args.into.split(",") if args.into else [f]
+                bad += compare(compile_listing(os.path.join(old_tree, rel), od), [compile_listing(n, nd) for n in new], os.path.basename(f))
         else:
-            if len(args.files) != 2:
-                ap.error("without --rev give exactly two files, OLD and NEW")
-            old, new = args.files
-            if old.endswith(".hip"):
-                os.makedirs(os.path.join(td, "a"))
-                old = compile_listing(old, os.path.join(td, "a"))
-            if new.endswith(".hip"):
-                os.makedirs(os.path.join(td, "b"))
-                new = compile_listing(new, os.path.join(td, "b"))
-            bad += compare(old, new, os.path.basename(args.files[1]))
+            if "--" in sys.argv:                                         # (argparse drops the separator: find the split in the raw arguments)
+                cut = sys.argv[sys.argv.index("--") + 1:]
+                old, new = args.files[:len(args.files) - len(cut)], cut
+            elif len(args.files) == 2:
+                old, new = args.files[:1], args.files[1:]
+            else:
+                ap.error("without --rev give OLD NEW, or OLD... -- NEW...")
+            if not old or not new:
+                ap.error("a side is empty")
+            for sub in ("a", "b"):
+                os.makedirs(os.path.join(td, sub))
+            old = [compile_listing(f, os.path.join(td, "a")) if f.endswith(".hip") else f for f in old]
+            new = [compile_listing(f, os.path.join(td, "b")) if f.endswith(".hip") else f for f in new]
+            bad += compare(old, new, os.path.basename(args.files[-1]))
     sys.exit(1 if bad else 0)
 
 
