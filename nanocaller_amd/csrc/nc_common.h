@@ -44,9 +44,8 @@ struct DevBuf {
 struct nc_weights {
     float *dev = nullptr;      // canonical flat blob
     size_t n = 0;
-    float *packed = nullptr;   // kernel-specific repack (see nc_cnn.hip)
-    size_t n_packed = 0;
-    void *packed_h = nullptr;  // fp16x3 fragments of the trunk kernel
+    float *packed = nullptr;   // SNP models: fp32 fragments of k4_conv12 (nc_cnn_fp32.hip)
+    void *packed_h = nullptr;  // fp16x3 fragments of the split-precision kernels (nc_cnn_snp.inc / nc_cnn_indel.inc)
     float x_limit = 0.0f;      // largest |input value| for which the L1 norms of conv1-3 prove that no activation reaches the fp16 clamp
 };
 

@@ -4,8 +4,11 @@ import hashlib
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRUNK_SOURCES = ("nanocaller_amd/csrc/nc_cnn.hip",)
-INDEL_SOURCES = ("nanocaller_amd/csrc/nc_cnn.hip", "nanocaller_amd/csrc/nc_indel.hip", "nanocaller_amd/csrc/nc_pipe.hip")
+CSRC = "nanocaller_amd/csrc/"
+CNN_SOURCES = tuple(CSRC + f for f in ("nc_cnn.h", "nc_cnn.hip", "nc_cnn_fp32.hip", "nc_cnn_h3.hip", "nc_cnn_snp.inc", "nc_cnn_indel.inc"))
+TRUNK_SOURCES = CNN_SOURCES
+INDEL_SOURCES = CNN_SOURCES + tuple(CSRC + f for f in ("nc_indel.hip", "nc_pipe.h", "nc_pipe.hip", "nc_pipe_plan.hip", "nc_pipe_windows.hip", "nc_pipe_align.hip",
+                                                       "nc_pipe_trace.hip", "nc_pipe_sites.hip"))
 
 
 def build_tag(files, root=ROOT):

@@ -4,7 +4,7 @@
     python3 tools/isa_diff.py OLD NEW                      # two .s listings, or two .hip files (compiled here)
     python3 tools/isa_diff.py OLD -- NEW1 NEW2 ...         # several files a side (a unit that was split): the union of their functions
     python3 tools/isa_diff.py --rev HEAD --into a.hip,b.hip nanocaller_amd/csrc/nc_pipe.hip      # FILE at REV against the units it was split into
-    python3 tools/isa_diff.py --rev HEAD nanocaller_amd/csrc/nc_cnn.hip ...   # each file at REV against the working tree
+    python3 tools/isa_diff.py --rev HEAD nanocaller_amd/csrc/nc_cnn_h3.hip ...   # each file at REV against the working tree
 
 A .hip file is compiled with `hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only`; with --rev the sources of REV
 (nanocaller_amd/csrc and include, from `git archive`) are compiled in a temporary directory.  Each listing is split into

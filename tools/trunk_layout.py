@@ -1,5 +1,5 @@
 """LDS layout of the split-precision SNP trunk (k5_trunk_p3's X image; the A1 / A2 activations k5_trunk_p3 and k5_trunk_lin share): checks the
-DS access patterns of conv1-3 against the gfx950 bank model (tools/lds_sim.py) and prints the constant tables nc_cnn.hip embeds.  Design tool, not product."""
+DS access patterns of conv1-3 against the gfx950 bank model (tools/lds_sim.py) and prints the constant tables nanocaller_amd/csrc/nc_cnn_snp.inc embeds.  Design tool, not product."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
