@@ -311,6 +311,15 @@ int nc_bam_walk(nc_ctx *ctx, const uint8_t *d_raw, int64_t raw_len, int32_t n_se
 int nc_bam_meta(nc_ctx *ctx, const uint8_t *d_raw, int64_t n_rec, const int64_t *d_rec_off, int32_t *d_meta, int32_t *d_status);
 int nc_bam_codes(nc_ctx *ctx, const uint8_t *d_raw, int32_t n_reads, const int64_t *d_rec, const int64_t *d_slot, const int32_t *d_cigd,
                  const int32_t *d_ncig, const int32_t *d_start, uint8_t *d_codes);
+/* Which kept alignments share a read name, from the record stream (csrc/nc_ingest_names.hip) -- nc_decoded_name_groups' answer without a host
+ * decode.  The n_cand candidates are the alignments whose name hash (nc_bam_meta) occurs more than once among the kept ones of a contig,
+ * sorted by (hash, file order): d_rec_off = their record offsets in d_raw[0, raw_len), d_hash = their hashes.  d_gid[i] = index (into the
+ * candidates) of the first candidate whose NAME -- length and bytes -- equals candidate i's, -1 when no other candidate carries it: two
+ * names with one hash stay two groups.  d_status (one int32, written here): non-zero when a record or its name does not lie inside the
+ * stream; the call then returns NC_ERR_ARG.  Runs on the context's own stream and returns when d_gid is complete, so a thread that
+ * prepares a contig may call it while another enqueues on the launch stream; the inputs must be complete at the call. */
+int nc_bam_name_groups(nc_ctx *ctx, const uint8_t *d_raw, int64_t raw_len, int64_t n_cand, const int64_t *d_rec_off, const uint64_t *d_hash,
+                       int32_t *d_gid, int32_t *d_status);
 /* The indel path's per-read sections of the same kept reads -- what nc_bam_decode's events and nc_indel_pack_build make on the host
  * (generate_indel_pileups.py:216-231's '+n' / '-n' markers, the inserted bases, the query bases behind the last aligned one).  Pass 1
  * (d_ev_off == NULL): d_counts = int32 [3][n_reads]: events, inserted bases, tail bases (at most tail_cap) per read.  Pass 2: d_ev_off /

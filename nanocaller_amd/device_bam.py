@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from .engine import DevicePack, get_engine
-from .pack import pileup_depth_cap
+from .pack import mate_table, name_groups, pileup_depth_cap
 from .synth import FLAG_FILTER_DEFAULT, FLAG_FILTER_SUPPL
 
 META_COLS = 12
@@ -474,6 +474,7 @@ class DeviceBam:
                 self.tid_range[t] = (a, b)
         LAST_LOAD["walk_meta"] = time.perf_counter() - t0
         LAST_LOAD["members"], LAST_LOAD["records"], LAST_LOAD["inflated_bytes"] = n_mem, self.n_rec, total
+        self.raw_len = total
         self.loaded = True
         return self
 
@@ -488,9 +489,14 @@ class DeviceBam:
         return out
 
     # ------------------------------------------------------------------ one contig: the host's decisions
-    def prepare(self, chrom, ref, supplementary=False, exclude=None, span=None, tile_size=2048, haplotags=None):
+    def prepare(self, chrom, ref, supplementary=False, exclude=None, span=None, tile_size=2048, haplotags=None, by_name=False):
         """host half (numpy + native, no GPU call: may run on a worker thread).  ref: the contig's sequence.  haplotags: path of a haplotag
-        table (phase.save_haplotags) whose HP / PS replace the records' own tags, by read-name hash.  -> dict for pack()"""
+        table (phase.save_haplotags) whose HP / PS replace the records' own tags, by read-name hash.  -> dict for pack()
+        by_name (the SNP route): kept alignments that share a read name are not refused but keyed by name as the host route keys them
+        (pack.name_groups -> mate_table: bit 3 and the name's strand in the tile entries, `mates` in the result).  When, and only when, name
+        hashes repeat among the kept alignments, THIS call then touches the GPU: one nc_bam_name_groups launch on the context's own stream and
+        one copy of 4 bytes per candidate back, both waited for here.  It stays safe on a worker thread -- the launch stream and the
+        context's state are left alone -- but it is no longer host work only."""
         if not self.loaded:
             raise RuntimeError("DeviceBam.load() first")
         if chrom not in self.ref_names:
@@ -512,7 +518,7 @@ class DeviceBam:
         kept_for_check = (flag & mask) == 0
         n_skip = int(np.count_nonzero(kept_for_check & ((flag & _lib.FLAG_REFSKIP) != 0)))
         h = (m[M_HASH_LO][idx].astype(np.uint32).astype(np.uint64) | (m[M_HASH_HI][idx].astype(np.uint32).astype(np.uint64) << np.uint64(32)))
-        n_dup = self._same_name_overlaps(h, start, end, kept_for_check, a + idx, any_pair=bool(supplementary))
+        n_dup = 0 if by_name else self._same_name_overlaps(h, start, end, kept_for_check, a + idx, any_pair=bool(supplementary))
         if n_skip or n_dup:
             what = []
             if n_skip:
@@ -532,6 +538,14 @@ class DeviceBam:
         else:
             hap, ps = m[M_HAP][idx].astype(np.uint8), m[M_PS][idx]
         strand = np.ascontiguousarray(((flag & 0x10) != 0).astype(np.uint8) | ((hap & 3) << 1))
+        mates = None
+        if by_name:
+            # every kept alignment whose name occurs more than once, overlapping or not, under both filters: what the host route does
+            gid = self._name_gid(h, (flag & filt) == 0, a + idx)
+            nxt, gstrand = name_groups(None, flag, keep, gid=gid) if gid is not None else (None, None)
+            if nxt is not None:
+                strand = np.ascontiguousarray(gstrand | ((nxt >= 0).astype(np.uint8) << 3) | ((hap & 3) << 1))   # (as pack.pack_reads builds it)
+                mates = mate_table(nxt, keep, start, end)
         # tile index + slot layout (nc_pack_plan / nc_pack_fill, index only: what wire.build_wire does)
         L = _lib.lib()
         ref_bytes = np.frombuffer(ref.encode("ascii") if isinstance(ref, str) else ref, np.uint8)
@@ -568,6 +582,8 @@ class DeviceBam:
                      slot_off=np.concatenate([slot, [int(size.sum())]]).astype(np.int64), read_hap=np.ascontiguousarray(hap[kk]),
                      read_ps=np.ascontiguousarray(ps[kk], np.int32), read_flag=np.ascontiguousarray((mk[M_LSEQ] == 0).astype(np.uint8)), tile_off=tile_off,
                      tile_ent=tile_ent.view(np.uint8).reshape(-1), ref_letters=ref_bytes[ga - 1:gb] if gb >= ga else ref_bytes[:0])
+        if mates is not None:
+            parts.update(mate_key=mates[0], mate_rec=np.ascontiguousarray(mates[1]).reshape(-1))
         sections, total_b = {}, 0
         for k, v in parts.items():
             sections[k] = (total_b, v.dtype, int(v.size))
@@ -580,7 +596,35 @@ class DeviceBam:
         return dict(chrom=chrom, n_kept=int(kk.size), staged=staged, sections=sections, ref_span=(ga, gb), exclude=list(exclude or ()),
                     codes_len=int(codes_len.value), tile_size=tile_size,
                     tile_pos0=int(tile_pos0.value), n_tiles=int(n_tiles.value), n_entries=int(n_ent.value), pos_lo=pos_lo, pos_hi=pos_hi,
-                    n_reads=n, read_start=start, read_end=end, read_flag=flag, keep=keep)
+                    n_reads=n, read_start=start, read_end=end, read_flag=flag, keep=keep, mates=mates)
+
+    def _name_gid(self, h, keep, recs):
+        """nc_decoded_name_groups' answer from the record stream: per alignment the first kept alignment (file order) of its read name when
+        another kept one carries it, else -1; None when no name hash repeats among the kept alignments (no launch).  The candidates -- kept
+        alignments whose hash occurs more than once -- go to nc_bam_name_groups sorted by (hash, file order); the names themselves are
+        compared there, so two names with one hash stay apart."""
+        k = np.flatnonzero(keep)
+        if k.size < 2:
+            return None
+        _, inv, cnt = np.unique(h[k], return_inverse=True, return_counts=True)
+        cand = k[cnt[inv] > 1]
+        if cand.size == 0:
+            return None
+        cand = cand[np.argsort(h[cand], kind="stable")]
+        dev = self.eng.device
+        d_gid = torch.empty(cand.size, dtype=torch.int32, device=dev)
+        d_status = torch.empty(1, dtype=torch.int32, device=dev)
+        d_off = torch.from_numpy(np.ascontiguousarray(self.rec_off[recs[cand]])).to(dev)      # (blocking copies: complete when the call is made)
+        d_hash = torch.from_numpy(h[cand].view(np.int64)).to(dev)
+        vp = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        rc = _lib.lib().nc_bam_name_groups(self.eng.ctx, vp(self.raw), self.raw_len, int(cand.size), vp(d_off), vp(d_hash), vp(d_gid), vp(d_status))
+        if rc != _lib.NC_OK:
+            raise _lib.NanoCallerHipError("%s: nc_bam_name_groups failed (%d)%s" % (self.path, rc, ": corrupt BAM records" if rc == _lib.NC_ERR_ARG else ""))
+        g = d_gid.cpu().numpy()
+        gid = np.full(h.size, -1, np.int32)
+        m = g >= 0
+        gid[cand[m]] = cand[g[m]]
+        return gid
 
     def _same_name_overlaps(self, h, start, end, keep, recs, any_pair=False):
         """bam.same_name_overlaps on name hashes; hash-equal pairs are confirmed on the names themselves.  any_pair: count every pair of kept
@@ -646,6 +690,8 @@ class DeviceBam:
                 ref_code[max(lo, 0):min(hi, ref_len)] = 4
         dp = DevicePack(codes=codes, tile_off=sec("tile_off"), tile_ent=sec("tile_ent"), ref_code=ref_code, tile_size=prep["tile_size"],
                         tile_pos0=prep["tile_pos0"], n_tiles=prep["n_tiles"], n_entries=prep["n_entries"], pos_lo=prep["pos_lo"], pos_hi=prep["pos_hi"])
+        if prep.get("mates") is not None:                                # prepare(by_name=True): the featuriser's table of the shared names (nc_snp_set_mates)
+            dp.mates = (sec("mate_key"), sec("mate_rec").view(-1, 4))
         if indel:
             K = prep["n_kept"]
             i32 = lambda n_: torch.zeros(max(int(n_), 4), dtype=torch.int32, device=dev)   # noqa: E731

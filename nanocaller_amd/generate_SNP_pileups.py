@@ -60,7 +60,8 @@ class _LRU:
 
 
 _BAM_WORLDS = _LRU(2)        # (bam, fasta, contig) -> decoded World
-_PACKS = _LRU(3)             # (source, fasta, contig, supplementary, exclusions, device) -> (DevicePack, World)
+_PACKS = _LRU(3)             # (source, fasta, contig, supplementary, exclusions, device) -> (DevicePack, World); a pack the device ingest made
+                             # by name (device_ingest_pack) carries a marker + the file's identity behind these and no World
 
 
 # BED files of centromere / telomere intervals that ship with the reference (data; `--exclude_bed hg38` of its CLI resolves to
@@ -205,8 +206,38 @@ def device_pack(sam_path, fasta_path, chrom, supplementary=False, excl=None, dev
     return _PACKS.get(key, make)
 
 
+def device_ingest_pack(dct, chrom, device=0, span=None):
+    """The SNP pass's pack of contig `chrom` made on the device from the BAM file itself (device_bam.py), alignments that share a read name
+    keyed by name (prepare(by_name=True)) -- for callers that ask for it with dct['device_ingest'] = True.  Without the key these single-contig
+    entry points decode on the host: that decode is the World the indel route and the phaser share.  None when the route is not open (not an
+    indexed BAM file, no FASTA, too large for HBM): the host route follows.  The entry is kept apart from the host route's and from the indel
+    route's (by_name=False: it refuses such files) by its key."""
+    sam_path, fasta_path = dct["sam_path"], dct.get("fasta_path")
+    if not dct.get("device_ingest") or not isinstance(sam_path, str) or sam_path in _SOURCES or not os.path.exists(sam_path) or not fasta_path:
+        return None
+    from .device_bam import DeviceIngestUnavailable, open_device_bam
+    try:
+        dbam = open_device_bam(sam_path, device, contigs=[chrom])
+    except DeviceIngestUnavailable:
+        return None
+    st = os.stat(sam_path)
+    supp, excl = bool(dct.get("supplementary")), _exclude_rows(dct, chrom)
+    key = (sam_path, fasta_path, chrom, supp, excl, device, "device ingest, by name", st.st_size, st.st_mtime_ns) + ((span,) if span else ())
+
+    def make():
+        from .bam import read_fasta_bytes
+        get_engine(device).use_torch_stream()
+        prep = dbam.prepare(chrom, read_fasta_bytes(fasta_path, chrom), supplementary=supp, exclude=excl, span=span, by_name=True,
+                            haplotags=getattr(sam_path, "tags", None))
+        return (dbam.pack(prep), None)
+    return _PACKS.get(key, make)[0]
+
+
 def device_pack_for(dct, chrom, device=0, span=None):
     """Packed + uploaded alignments of contig `chrom` of dct['sam_path'] (cached per source / contig / filter / exclusions / span)."""
+    dp = device_ingest_pack(dct, chrom, device, span)
+    if dp is not None:
+        return dp
     return device_pack(dct["sam_path"], dct.get("fasta_path"), chrom, dct.get("supplementary"), _exclude_rows(dct, chrom), device, span, by_name=True)[0]
 
 
@@ -237,4 +268,4 @@ def get_snp_testing_candidates(dct, region, device=0):
             sites.rev_dp.cpu().numpy()[valid].astype(np.float64))
 
 
-__all__ = ["get_snp_testing_candidates", "register_alignments", "device_pack_for", "device_pack", "release_contig", "_lib"]
+__all__ = ["get_snp_testing_candidates", "register_alignments", "device_pack_for", "device_pack", "device_ingest_pack", "release_contig", "_lib"]

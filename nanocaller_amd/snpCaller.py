@@ -327,7 +327,8 @@ def _prepare_wire(params, chrom, grp):
 
 def _prepare_device(dbam, params, chrom, grp, ref=None):
     """host half of a group's ingest on the device route (device_bam.py), on a worker thread: the contig's reference sequence, which of its
-    alignments the pileup keeps, the tile index -- from the per-record fields the device extracted when the file was loaded"""
+    alignments the pileup keeps, the tile index -- from the per-record fields the device extracted when the file was loaded.  Alignments that
+    share a read name are keyed by name (by_name=True: when name hashes repeat, one small launch on the context's own stream confirms the names)"""
     from .bam import read_fasta_bytes
     from .generate_SNP_pileups import _exclude_rows
     # (contig_span's rule, on the lengths the loader already holds: no second open of the BAM)
@@ -336,7 +337,7 @@ def _prepare_device(dbam, params, chrom, grp, ref=None):
     hi = min(length, max(c['end'] for c in grp) + _lib.FLANK)
     span = None if (hi - lo + 1) >= 0.9 * length else (lo, hi)
     ref = ref.result() if ref is not None else read_fasta_bytes(params['fasta_path'], chrom)
-    return dbam.prepare(chrom, ref, supplementary=bool(params.get('supplementary')), exclude=_exclude_rows(params, chrom), span=span)
+    return dbam.prepare(chrom, ref, supplementary=bool(params.get('supplementary')), exclude=_exclude_rows(params, chrom), span=span, by_name=True)
 
 
 def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
@@ -411,8 +412,9 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
         # that alone does not fit is decoded by the host threads.
         dev_codes, refs = [None], {}
         run_end, run_dev = [len(keys)] * len(keys), [None] * len(keys)       # per group: where its run of groups ends; the run's contigs (None: host route)
-        # (dct['supplementary']: a split read's records are keyed by NAME, pack.name_groups -- the host route's builders do that; the CLI never sets it)
-        if piped and keys and params.get('device_ingest', os.environ.get('NC_DEVICE_INGEST', '1') != '0') and params.get('fasta_path') and not params.get('supplementary'):
+        # (alignments that share a read name -- a split read's records under dct['supplementary'], paired mates -- are keyed by NAME on both routes:
+        # pack.name_groups, fed by nc_decoded_name_groups on the host route and by nc_bam_name_groups here)
+        if piped and keys and params.get('device_ingest', os.environ.get('NC_DEVICE_INGEST', '1') != '0') and params.get('fasta_path'):
             from .bam import read_fasta_bytes
             from .device_bam import DeviceIngestUnavailable, open_device_bam, plan_shares
             try:
