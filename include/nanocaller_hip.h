@@ -103,7 +103,7 @@ typedef struct {
     int32_t end;        /* one past the last covered position */
     int64_t base_flag;  /* (base & ~15) | flags; bit0 = reverse strand ((flag & 0x910)/16, :143);
                            bits 1-2 = haplotype tag HP (0 untagged, 1, 2; generate_indel_pileups.py:180-185);
-                           bit 3 = the read name is shared with another kept alignment (nc_snp_set_mates) */
+                           bit 3 = the read name is shared with another kept alignment (nc_snp_set_mates, nc_indel_set_mates) */
 } nc_tile_entry;
 
 typedef struct {
@@ -403,6 +403,18 @@ int nc_snp_featurize(nc_ctx *ctx, const nc_readpack *pack,
  * 16-byte aligned = {start, end, table index of the next alignment of the same name (circular), 0}.  Needs the int16 tensor format and
  * maxcov < 256 (NC_ERR_UNSUPPORTED from nc_snp_featurize otherwise). */
 int nc_snp_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d_mate_key, const int32_t *d_mate_rec);
+
+/* The same for the device indel pipeline: the table of the kept alignments that share a read name, read by the following nc_indel_sites_plan
+ * calls (n_mates = 0 clears it; the pointers are borrowed).  The reference keys its hap sets, phase_dict, the per-column event sets of pass 1 and
+ * the read dicts of pass 2 by NAME (generate_indel_pileups.py:180-188,218-235,310-338; the haploid twin likewise): with the table set, a column's
+ * haplotype depths count a shared name once, an event set holds a name once whichever of its alignments carries the event (the window union
+ * likewise), and an anchor's read sets hold a name once, at the rank of its first alignment there with the window of its last; haplotype and PS
+ * are the name's.  d_mate_key as for nc_snp_set_mates; d_mate_rec [n_mates][8] int32, 16-byte aligned = {start, end, table index of the next
+ * alignment of the name (circular, file order), index of the alignment among the pack's kept reads, the name's haplotype mask (bit 0: one of its
+ * records has HP 1, bit 1: HP 2), phase_dict[name] = PS of the name's last record (0 when that record has no HP), 0, 0}.  A plan with the table
+ * set and impute_indel_phase, or with chunks that leave the pack's tile grid, returns NC_ERR_UNSUPPORTED.  The kernels follow a name's ring for at most
+ * 64 alignments: the caller hands over no table with a longer ring (generate_indel_pileups.indel_mate_table refuses it).  (ABI 11: an added export.) */
+int nc_indel_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d_mate_key, const int32_t *d_mate_rec);
 
 /* Per-site coverage scale (snpCaller.py:93-96, 170-173) for the sites of the last scan:
  * mode 0: scale[s] = train_coverage / mean(site_depth over the site's chunk) (chunk constant, quirk E2)

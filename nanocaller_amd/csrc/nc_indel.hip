@@ -108,11 +108,14 @@ __global__ void k_blk_chunks(const IndelChunk *__restrict__ ck, int32_t n_chunks
 
 // per-column depth by haplotype tag; same access scheme as k_scan (one aligned dwordx4 of codes per read and lane).
 // STAR: count the reads whose code is 4 (deleted at this column) of all haplotypes instead, into cnt[0]
-template <int BLOCK, bool STAR>
+// MATES: the pack holds alignments that share read names (entries with bit 3 of base_flag; nc_indel_set_mates).  len_seq_0 / len_seq_1 are sizes of
+// name SETS (:219-223): such an alignment counts on the planes of its NAME's haplotype mask (both when records of the name carry HP 1 and HP 2),
+// and not at the columns an earlier alignment of the name is present at.  (Haploid: the depth is len(read_names), duplicates included.)
+template <int BLOCK, bool STAR, bool MATES>
 __global__ __launch_bounds__(BLOCK) void k_hap_depth_b(const uint8_t *__restrict__ codes, const int32_t *__restrict__ tile_off,
                                                        const nc_tile_entry *__restrict__ tile_ent, int32_t tile_pos0,
                                                        const IndelChunk *__restrict__ ck, const int32_t *__restrict__ blk_chunk, char *__restrict__ ws, int32_t haploid,
-                                                       const uint8_t *__restrict__ excl, int32_t grid_lo, int32_t *__restrict__ blk_yield)
+                                                       const uint8_t *__restrict__ excl, int32_t grid_lo, int32_t *__restrict__ blk_yield, IndelMates mt)
 {
     constexpr int TILE = BLOCK * 16;
     const IndelChunk c = ck[blk_chunk[blockIdx.x]];
@@ -144,6 +147,33 @@ __global__ __launch_bounds__(BLOCK) void k_hap_depth_b(const uint8_t *__restrict
             uint32_t pres[4];
 #pragma unroll
             for (int d = 0; d < 4; d++) pres[d] = STAR ? lut8i(w[d], 0u, 0x00000001u) : lut8i(w[d], 0x01010101u, 0x00000001u);   // code 4 | codes 0..4 -> 1
+            if constexpr (MATES && !STAR) {
+                if ((ent.base_flag & 8) && !haploid) {
+                    const int self = imate_find(mt, (ent.base_flag & ~int64_t(15)) + slo);
+                    if (self >= 0) {
+                        int j = imate_get(mt, self).next;
+                        for (int guard = 0; guard < 64 && j != self && j >= 0 && j < mt.n; guard++) {      // (a damaged ring must not hang the wave)
+                            const IndelMate o = imate_get(mt, j);
+                            if (j < self && P0 >= (o.start & ~15) && P0 < ((o.end + 15) & ~15)) {
+                                const uint4 ov = *reinterpret_cast<const uint4 *>(codes + (mt.key[j] - (o.start & ~15)) + P0);
+                                pres[0] &= ~lut8i(ov.x, 0x01010101u, 0x00000001u);
+                                pres[1] &= ~lut8i(ov.y, 0x01010101u, 0x00000001u);
+                                pres[2] &= ~lut8i(ov.z, 0x01010101u, 0x00000001u);
+                                pres[3] &= ~lut8i(ov.w, 0x01010101u, 0x00000001u);
+                            }
+                            j = o.next;
+                        }
+                        const int nm = imate_get(mt, self).hap & 3;
+#pragma unroll
+                        for (int d = 0; d < 4; d++) {
+                            if (nm & 1) acc[0][d] += pres[d];
+                            if (nm & 2) acc[1][d] += pres[d];
+                            if (!nm) acc[2][d] += pres[d];
+                        }
+                        continue;
+                    }
+                }
+            }
             if (STAR || plane == 0) {
 #pragma unroll
                 for (int d = 0; d < 4; d++) acc[0][d] += pres[d];
@@ -668,6 +698,61 @@ __global__ __launch_bounds__(64) void k_entry_rows(const int32_t *__restrict__ t
     }
 }
 
+// the classes (bit cls) an event of signed length sl qualifies for: 0 / 1 deletions / insertions of 3 .. 50 bases, 2 / 3 of at most 10
+__device__ __forceinline__ uint32_t ev_qmask(int32_t sl)
+{
+    const int32_t ln = sl < 0 ? -sl : sl;
+    const bool ins = sl > 0;
+    return ((ln > 2 && ln <= 50) ? (ins ? 2u : 1u) : 0u) | (ln <= 10 ? (ins ? 8u : 4u) : 0u);
+}
+// k_event_tiles<true>: an event's owner is its read NAME (:225-235 build sets of names).  For the event `ev` (column p, rank k, classes qm) of table
+// member `self`: the classes for which another alignment of the name holds a qualifying event within the class's window before it (-> prevf) / after
+// it (-> nextf), in the order (column, table index); rkf(column) = its rank or -1, lo_pos / hi_pos = the columns rkf covers.
+template <class RK>
+__device__ __forceinline__ void mate_neighbours(const IndelMates &mt, int self, int32_t p, int k, uint32_t qm, int win, int small_win,
+                                                const int32_t *__restrict__ ev_off, const int32_t *__restrict__ ev_pos, const int32_t *__restrict__ ev_len,
+                                                int32_t lo_pos, int32_t hi_pos, RK rkf, uint32_t &prevf, uint32_t &nextf)
+{
+    int j = imate_get(mt, self).next;
+    for (int guard = 0; guard < 64 && j != self && j >= 0 && j < mt.n; guard++) {
+        const IndelMate o = imate_get(mt, j);
+        const int ea = ev_off[o.read], eb = ev_off[o.read + 1];
+        const int32_t want = j < self ? p + 1 : p;                    // first event of j that comes after this one
+        int x = ea, y = eb;
+        while (x < y) { const int mid = (x + y) >> 1; if (ev_pos[mid] < want) x = mid + 1; else y = mid; }
+        uint32_t need = qm & ~prevf;
+        for (int e2 = x - 1; e2 >= ea && need; e2--) {
+            const int32_t p2 = ev_pos[e2];
+            if (p2 < lo_pos) break;
+            const int k2 = rkf(p2);
+            if (k2 < 0) continue;
+            const int d = k - k2;
+            if (d > win - 1) need &= ~3u;
+            if (d > small_win - 1) need &= ~12u;
+            const uint32_t f = ev_qmask(ev_len[e2]) & need;
+            prevf |= f;
+            need &= ~f;
+        }
+        need = qm & ~nextf;
+        for (int e2 = x; e2 < eb && need; e2++) {
+            const int32_t p2 = ev_pos[e2];
+            if (p2 > hi_pos) break;
+            const int k2 = rkf(p2);
+            if (k2 < 0) continue;
+            const int d = k2 - k;
+            if (d > win - 1) need &= ~3u;
+            if (d > small_win - 1) need &= ~12u;
+            const uint32_t f = ev_qmask(ev_len[e2]) & need;
+            nextf |= f;
+            need &= ~f;
+        }
+        j = o.next;
+    }
+}
+
+// MATES: entries with bit 3 of base_flag (nc_indel_set_mates) are keyed by name: tagged by the name's haplotype mask (en_h 2 = both rows), and an
+// event opens / closes a window interval only if no alignment of the name holds a qualifying event within the window before / after it.
+template <bool MATES>
 __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restrict__ tile_off, const nc_tile_entry *__restrict__ tile_ent, int32_t tile_pos0,
                                                      int32_t tile_size, const int32_t *__restrict__ ent_read, const int32_t *__restrict__ ent_cur,
                                                      const int32_t *__restrict__ ev_off, const int32_t *__restrict__ ev_pos,
@@ -675,7 +760,7 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
                                                      const IndelChunk *__restrict__ ck, const int32_t *__restrict__ blk_chunk, char *__restrict__ ws, int32_t win,
                                                      int32_t small_win, int32_t haploid, int32_t mincov, double ins_t, double del_t,
                                                      int8_t *__restrict__ col_type_all, int32_t *__restrict__ err_bits, const uint16_t *__restrict__ dec_tab,
-                                                     const int32_t *__restrict__ blk_base, int32_t dec_n)
+                                                     const int32_t *__restrict__ blk_base, int32_t dec_n, IndelMates mt)
 {
     // interval ends per (class, haplotype) row and rank as 16-bit fields, two ranks per word, each biased by 0x4000: +1 is an atomic add and
     // -1 an atomic SUBTRACT of the field's unit, so neither carries into the neighbour field (16 KB instead of 32: a fourth workgroup per CU)
@@ -685,6 +770,13 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
     __shared__ int32_t rkw[EV_SUB + EV_MARGIN];
     __shared__ int32_t en_e0[256], en_pre[257], en_lim[256];
     __shared__ uint8_t en_h[256];
+    __shared__ int32_t en_mate[MATES ? 256 : 1];                     // (MATES) the entry's row in the table of shared names, -1: its name is its own
+    // hp tag / table row of an entry: the name's haplotype mask for a shared name (3: records with HP 1 and with HP 2)
+    auto name_tag = [&](const nc_tile_entry &en, int &hp) {
+        int row = -1;
+        if ((en.base_flag & 8) && (row = imate_find(mt, (en.base_flag & ~int64_t(15)) + (en.start & ~15))) >= 0) hp = haploid ? hp : imate_get(mt, row).hap & 3;
+        return row;
+    };
     __shared__ int32_t evk[EV_CAP];                                  // the batch's events: rank of the column (-1 excluded), classes they qualify for
     __shared__ uint8_t evq[EV_CAP];
     __shared__ uint8_t own[EV_CAP];                                  // entry (of the batch's 256) every event of the batch belongs to
@@ -759,12 +851,15 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
     {
         const int32_t ft_lo = tile_pos0 + f_tt * tile_size;
         const bool mine = f_tt == t || f_ent.end <= ft_lo + tile_size;
-        const int hp = (int)((f_ent.base_flag >> 1) & 3);
-        if (f_on && mine && f_ent.start <= b_hi && f_ent.end > m_fix && (haploid || hp == 1 || hp == 2)) {
+        int hp = (int)((f_ent.base_flag >> 1) & 3);
+        int row = -1;
+        if constexpr (MATES) { if (f_on) row = name_tag(f_ent, hp); }
+        if (f_on && mine && f_ent.start <= b_hi && f_ent.end > m_fix && (haploid || hp == 1 || hp == 2 || (MATES && hp == 3))) {
             f_cnt = max(f_x1 - f_x0, 0);
             en_e0[tid] = f_x0;
             en_lim[tid] = f_x1;
             en_h[tid] = (uint8_t)(haploid ? 0 : hp - 1);
+            if constexpr (MATES) en_mate[tid] = row;
         }
     }
     __syncthreads();
@@ -828,8 +923,11 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
                 // a read is taken at the LAST of these tiles that lists it: tile t's entry knows where the block's events begin and end
                 // (k_entry_cursors), an entry of an earlier tile is of a read that ends before tile t
                 const bool mine = tt == t || ent.end <= tt_lo + tile_size;
-                const int hp = (int)((ent.base_flag >> 1) & 3);
-                if (mine && ent.start <= b_hi && ent.end > m_lo && (haploid || hp == 1 || hp == 2)) {
+                int hp = (int)((ent.base_flag >> 1) & 3);
+                int row = -1;
+                if constexpr (MATES) row = name_tag(ent, hp);
+                if (mine && ent.start <= b_hi && ent.end > m_lo && (haploid || hp == 1 || hp == 2 || (MATES && hp == 3))) {
+                    if constexpr (MATES) en_mate[tid] = row;
                     if (tt < t - 1) {                                         // (a margin longer than a tile: excluded stretch)
                         x0 = ea;
                         int y0 = eb;
@@ -931,10 +1029,23 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
                         nextf |= f;
                         need &= ~f;
                     }
+                    if constexpr (MATES) {
+                        if (en_mate[lo] >= 0) {
+                            const int32_t p = ev_pos[en_e0[lo] + (idx - i0)];
+                            mate_neighbours(mt, en_mate[lo], p, k, (uint32_t)qm, win, small_win, ev_off, ev_pos, ev_len, c.lo, b_hi, rkf, prevf, nextf);
+                        }
+                    }
 #pragma unroll
                     for (int cls = 0; cls < 4; cls++) {
                         if (!((qm >> cls) & 1)) continue;
                         const int w = cls < 2 ? win : small_win;
+                        if constexpr (MATES) {                               // (h = 2: the name is in both hap sets)
+                            for (int hh = (h == 1 ? 1 : 0); hh <= (h == 0 ? 0 : 1); hh++) {
+                                if (!((prevf >> cls) & 1)) dif_add(cls * 2 + hh, max(k, k0) - k0);
+                                if (!((nextf >> cls) & 1) && max(k + w, k0) - k0 < nk) dif_sub(cls * 2 + hh, max(k + w, k0) - k0);
+                            }
+                            continue;
+                        }
                         if (!((prevf >> cls) & 1)) dif_add(cls * 2 + h, max(k, k0) - k0);
                         if (!((nextf >> cls) & 1) && max(k + w, k0) - k0 < nk) dif_sub(cls * 2 + h, max(k + w, k0) - k0);
                     }
@@ -951,11 +1062,15 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
                 const int32_t p = ev_pos[ev], sl = ev_len[ev];
                 const int k = rkf(p);
                 if (k < 0) continue;                                              // excluded column
+                uint32_t m_prev = 0, m_next = 0;
+                if constexpr (MATES) {
+                    if (en_mate[j] >= 0) mate_neighbours(mt, en_mate[j], p, k, ev_qmask(sl), win, small_win, ev_off, ev_pos, ev_len, c.lo, b_hi, rkf, m_prev, m_next);
+                }
 #pragma unroll
                 for (int cls = 0; cls < 4; cls++) {
                     if (!qualifies(sl, cls)) continue;
                     const int w = cls < 2 ? win : small_win;
-                    bool has_prev = false, has_next = false;
+                    bool has_prev = MATES && ((m_prev >> cls) & 1), has_next = MATES && ((m_next >> cls) & 1);
                     for (int e2 = ev - 1; e2 >= ef; e2--) {
                         const int k2 = rkf(ev_pos[e2]);
                         if (k2 < 0) continue;
@@ -970,6 +1085,13 @@ __global__ __launch_bounds__(EV_NT, 8) void k_event_tiles(const int32_t *__restr
                     }
                     // ends clipped to the block's first rank: a margin event whose own window stops short of the block may still open the
                     // chain a later margin event continues into it (+1 and -1 on rank k0 cancel when nothing does)
+                    if constexpr (MATES) {
+                        for (int hh = (h == 1 ? 1 : 0); hh <= (h == 0 ? 0 : 1); hh++) {
+                            if (!has_prev) dif_add(cls * 2 + hh, max(k, k0) - k0);
+                            if (!has_next && max(k + w, k0) - k0 < nk) dif_sub(cls * 2 + hh, max(k + w, k0) - k0);
+                        }
+                        continue;
+                    }
                     if (!has_prev) dif_add(cls * 2 + h, max(k, k0) - k0);
                     if (!has_next && max(k + w, k0) - k0 < nk) dif_sub(cls * 2 + h, max(k + w, k0) - k0);
                 }
@@ -1089,7 +1211,7 @@ int nc_indel_check(nc_ctx *ctx, const nc_readpack *pack, const nc_indel_events *
 int nc_indel_scan_group_launch(nc_ctx *ctx, const nc_readpack *pack, const nc_indel_events *ev, const uint8_t *excl_dev, int32_t n_chunks,
                                const int32_t *starts, const int32_t *ends, const nc_indel_scan_params *prm, int32_t *consumed,
                                std::vector<IndelChunk> &ck, const IndelChunk **ck_dev_out, const int8_t **ctype_out, const int64_t *slot_off_dev,
-                               int32_t *err_bits_dev, const int32_t *rd_start_dev, const int32_t *rd_end_dev, bool reuse_tables)
+                               int32_t *err_bits_dev, const int32_t *rd_start_dev, const int32_t *rd_end_dev, bool reuse_tables, const IndelMates *mates)
 {
     // reuse_tables: a later group of chunks of the SAME pack and events (the device pipeline's plan): the cursor table of the first group stands
     if (!reuse_tables) ctx->indel_ent_of = nullptr;
@@ -1148,6 +1270,11 @@ int nc_indel_scan_group_launch(nc_ctx *ctx, const nc_readpack *pack, const nc_in
     char *ws = (char *)ctx->indel_ws.p;
     const bool no_tiles = getenv("NC_K7_EVENT_ATOMICS") != nullptr;                         // k_event_intervals_w + k_prefix_rows_b + k_indel_decide_b, for A/B checks (read per call: tests flip it)
     const bool tiles = slot_off_dev && err_bits_dev && !impute && !no_tiles && !clipped && ev->n_reads > 0 && nblk > 0 && tile % EV_SUB == 0;
+    // alignments that share read names (nc_indel_set_mates): keyed by name in the tiled form only
+    const bool by_name = mates && mates->n > 0;
+    if (by_name && !tiles)
+        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "alignments that share read names: the indel scan keys them by name on its tiled route only (no impute_indel_phase, chunks inside the pack's tile grid)");
+    const IndelMates mt = by_name ? *mates : IndelMates{nullptr, nullptr, 0};
     // the tiled form writes every word it reads (depths, ranks, window counts in LDS, decisions); the other one accumulates into zeros
     if (!tiles) NC_HIP(ctx, hipMemsetAsync(ws, 0, o_type, ctx->stream));
     IndelChunk *ck_dev = (IndelChunk *)(ws + o_ck);
@@ -1156,17 +1283,21 @@ int nc_indel_scan_group_launch(nc_ctx *ctx, const nc_readpack *pack, const nc_in
     int32_t *blk_chunk = (int32_t *)(ws + o_blk);
     int32_t *blk_yield = tiles ? blk_chunk + nblk : nullptr, *blk_base = blk_chunk + 2 * (size_t)nblk;
     if (nblk > 0) hipLaunchKernelGGL(k_blk_chunks, dim3((ng + 255) / 256), dim3(256), 0, ctx->stream, ck_dev, ng, nblk, blk_chunk);
-#define NC_HAP_DEPTH(B, STAR)                                                                                                        \
-    hipLaunchKernelGGL((k_hap_depth_b<B, STAR>), dim3(nblk), dim3(B), 0, ctx->stream, pack->codes, pack->tile_off, pack->tile_ent, \
-                       pack->tile_pos0, ck_dev, blk_chunk, ws, prm->haploid, excl_dev, grid_lo, (STAR) ? nullptr : blk_yield)
+#define NC_HAP_DEPTH(B, STAR, MATES)                                                                                                        \
+    hipLaunchKernelGGL((k_hap_depth_b<B, STAR, MATES>), dim3(nblk), dim3(B), 0, ctx->stream, pack->codes, pack->tile_off, pack->tile_ent, \
+                       pack->tile_pos0, ck_dev, blk_chunk, ws, prm->haploid, excl_dev, grid_lo, (STAR) ? nullptr : blk_yield, mt)
     if (nblk > 0) {
-        if (tile == 1024) NC_HAP_DEPTH(64, false);
-        else if (tile == 2048) NC_HAP_DEPTH(128, false);
-        else NC_HAP_DEPTH(256, false);
+        if (by_name) {
+            if (tile == 1024) NC_HAP_DEPTH(64, false, true);
+            else if (tile == 2048) NC_HAP_DEPTH(128, false, true);
+            else NC_HAP_DEPTH(256, false, true);
+        } else if (tile == 1024) NC_HAP_DEPTH(64, false, false);
+        else if (tile == 2048) NC_HAP_DEPTH(128, false, false);
+        else NC_HAP_DEPTH(256, false, false);
         if (impute) {
-            if (tile == 1024) NC_HAP_DEPTH(64, true);
-            else if (tile == 2048) NC_HAP_DEPTH(128, true);
-            else NC_HAP_DEPTH(256, true);
+            if (tile == 1024) NC_HAP_DEPTH(64, true, false);
+            else if (tile == 2048) NC_HAP_DEPTH(128, true, false);
+            else NC_HAP_DEPTH(256, true, false);
         }
     }
 #undef NC_HAP_DEPTH
@@ -1198,9 +1329,13 @@ int nc_indel_scan_group_launch(nc_ctx *ctx, const nc_readpack *pack, const nc_in
         const int32_t dec_n = dn ? std::max(0, std::min(DEC_N, atoi(dn))) : DEC_N;
         ctx->indel_ent_of = pack->tile_ent;                              // (the device pipeline's k_sets / k_windows use the tables too)
         ctx->indel_ent_spt = SPT;
-        hipLaunchKernelGGL(k_event_tiles, dim3(nblk * (tile / EV_SUB)), dim3(EV_NT), 0, ctx->stream, pack->tile_off, pack->tile_ent, pack->tile_pos0, tile,
-                           ent_read, ent_cur, ev->ev_off, ev->ev_pos, ev->ev_len, ev->read_hap, ck_dev, blk_chunk, ws, prm->win_size,
-                           prm->small_win_size, prm->haploid, prm->mincov, prm->ins_t, prm->del_t, ctype, err_bits_dev, dec_tab, blk_base, dec_n);
+#define NC_EVENT_TILES(MATES)                                                                                                                          \
+    hipLaunchKernelGGL(k_event_tiles<MATES>, dim3(nblk * (tile / EV_SUB)), dim3(EV_NT), 0, ctx->stream, pack->tile_off, pack->tile_ent, pack->tile_pos0, tile, \
+                       ent_read, ent_cur, ev->ev_off, ev->ev_pos, ev->ev_len, ev->read_hap, ck_dev, blk_chunk, ws, prm->win_size,                    \
+                       prm->small_win_size, prm->haploid, prm->mincov, prm->ins_t, prm->del_t, ctype, err_bits_dev, dec_tab, blk_base, dec_n, mt)
+        if (by_name) NC_EVENT_TILES(true);
+        else NC_EVENT_TILES(false);
+#undef NC_EVENT_TILES
     } else if (ev->n_reads > 0) {
         static const bool per_thread = getenv("NC_K7_THREAD_PER_READ") != nullptr;          // the round-1 form, kept for A/B checks
         if (per_thread)

@@ -78,6 +78,10 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     const bool impute = prm->impute && !prm->haploid;                 // (generate_indel_pileups.py:278: the diploid function only)
     if (impute && (!reads->ins_off || !reads->ins_bases)) return nc_fail(ctx, NC_ERR_ARG, "nc_indel_sites_plan: impute_indel_phase needs the inserted bases");
     if (cpl_for(window_after + 1) == 0) return nc_fail(ctx, NC_ERR_CAPACITY, "nc_indel_sites_plan: windows longer than 271 bases");
+    // alignments that share read names (nc_indel_set_mates): K7 and k_sets key them by name; the read grouping of impute_indel_phase does not
+    const IndelMates mates = {ctx->imate_key, ctx->imate_rec, ctx->n_imates};
+    if (mates.n > 0 && impute)
+        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_indel_sites_plan: impute_indel_phase on a contig whose kept alignments share read names");
     nc_indel_events ev;
     ev.n_reads = reads->n_reads; ev.ev_off = reads->ev_off; ev.ev_pos = reads->ev_pos; ev.ev_len = reads->ev_len; ev.read_hap = reads->read_hap;
     NC_TRY(nc_indel_check(ctx, pack, &ev, prm, "nc_indel_sites_plan"));
@@ -141,7 +145,7 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
         const IndelChunk *ck_dev = nullptr;
         const int8_t *ctype = nullptr;
         NC_TRY(nc_indel_scan_group_launch(ctx, pack, &ev, excl_dev, n_chunks - c0, starts + c0, ends + c0, prm, &used, ck, &ck_dev, &ctype,
-                                          ev.n_reads == reads->n_reads ? reads->slot_off : nullptr, err, reads->rd_start, reads->rd_end, c0 > 0));
+                                          ev.n_reads == reads->n_reads ? reads->slot_off : nullptr, err, reads->rd_start, reads->rd_end, c0 > 0, &mates));
         for (int32_t k = 0; k < used; k++) pcs[(size_t)(c0 + k)].coloff = ck[(size_t)k].coloff;
         NC_TRY(nc_h2d_pieces(ctx, (PipeChunk *)s->pc.p + c0, pcs.data() + c0, (size_t)used * sizeof(PipeChunk), ctx->stream));
         if (impute) {                                                 // the read grouping of every col_type-2 column: 3 (an anchor) or -1
@@ -195,6 +199,7 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     sa.n_anchor = na; sa.anc_pos = (const int32_t *)s->anc_pos.p; sa.anc_chunk = (const int32_t *)s->anc_chunk.p; sa.anc_type = (const int8_t *)s->anc_type.p;
     sa.kept = (int32_t *)s->kept.p; sa.nuniq = (int32_t *)s->nuniq.p;
     sa.imp = imp; sa.imp.ent_read = sa.ent_read; sa.err = err;
+    sa.mt = mates;
     nc_pipe_launch_sets(ctx->stream, sa, false, impute);
     NC_TRY(nc_pipe_scan_i32(ctx, ctx->stream, s->part_a, (const int32_t *)s->kept.p, na, (int32_t *)s->site_of.p));
     NC_TRY(nc_pipe_scan_i32(ctx, ctx->stream, s->part_a, (const int32_t *)s->nuniq.p, na, (int32_t *)s->al_of.p));
@@ -250,6 +255,17 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
         (void)hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
         s->stage_ms[0] = ms;
     }
+    return NC_OK;
+}
+
+extern "C" int nc_indel_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d_mate_key, const int32_t *d_mate_rec)
+{
+    if (!ctx) return NC_ERR_ARG;
+    if (n_mates < 0 || (n_mates > 0 && (!d_mate_key || !d_mate_rec || ((uintptr_t)d_mate_rec & 15))))
+        return nc_fail(ctx, NC_ERR_ARG, "nc_indel_set_mates: bad argument");
+    ctx->n_imates = n_mates;
+    ctx->imate_key = n_mates ? d_mate_key : nullptr;
+    ctx->imate_rec = n_mates ? d_mate_rec : nullptr;
     return NC_OK;
 }
 

@@ -377,7 +377,11 @@ __global__ __launch_bounds__(256) void k_flatten(const PipeChunk *__restrict__ p
     }
 }
 
-template <bool FILL, bool IMP>
+// MATES: the pack holds alignments that share read names (entries with bit 3 of base_flag; SetArgs::mt).  Pass 2's dicts are keyed by name
+// (:322-338): where several alignments of a name cover the anchor, the name is one entry at the rank of the first of them (a dict keeps the order of
+// first insertion) with the window of the last (`d_tot[qname] = dt` overwrites); its haplotype is the name's (hap0 when records of the name carry
+// HP 1 and HP 2: `if ... elif`), and the site's phase is phase_dict[name].  Every other entry takes the code of the plain form.
+template <bool FILL, bool IMP, bool MATES>
 __global__ __launch_bounds__(256) void k_sets(SetArgs p)
 {
     __shared__ ImpLds imp_lds[IMP ? 4 : 1];
@@ -398,6 +402,7 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
         ok = ok && __all(mine);
     }
     int n_all = 0, n_1 = 0, n_2 = 0, n_u = 0, first0 = -1;
+    int32_t first_ps = 0;                                            // (MATES) phase_dict of set 0's first name
     // an imputed anchor (impute_indel_phase): the two read sets of its source column stand where the HP tags stand otherwise (:310-312)
     int n_imp = -1;
     if constexpr (IMP) {
@@ -419,8 +424,31 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
             nc_tile_entry ent;
             ent.start = 0; ent.end = 0; ent.base_flag = 0;
             if (e < e1) ent = p.tile_ent[e];
-            const bool cov = e < e1 && ent.start <= v && v < ent.end;            // the pileup at the anchor, in pack (= file) order
+            bool cov = e < e1 && ent.start <= v && v < ent.end;                  // the pileup at the anchor, in pack (= file) order
             int hp = (int)((ent.base_flag >> 1) & 3);
+            int r_name = -1;                                                     // (MATES) the read whose window stands for the name
+            int32_t ps_name = 0;
+            if constexpr (MATES) {
+                if (cov && (ent.base_flag & 8)) {
+                    const int self = imate_find(p.mt, (ent.base_flag & ~int64_t(15)) + (ent.start & ~15));
+                    if (self >= 0) {
+                        const IndelMate me = imate_get(p.mt, self);
+                        int first = self, last = self, j = me.next;
+                        r_name = me.read;
+                        for (int guard = 0; guard < 64 && j != self && j >= 0 && j < p.mt.n; guard++) {     // (a damaged ring must not hang the wave)
+                            const IndelMate o = imate_get(p.mt, j);
+                            if (o.start <= v && v < o.end) {
+                                first = min(first, j);
+                                if (j > last) { last = j; r_name = o.read; }
+                            }
+                            j = o.next;
+                        }
+                        if (first != self) cov = false;
+                        hp = (me.hap & 1) ? 1 : (me.hap & 2) ? 2 : 0;
+                        ps_name = me.ps;
+                    }
+                }
+            }
             if constexpr (IMP) {
                 if (n_imp >= 0) {
                     hp = 0;
@@ -455,6 +483,11 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
                         r = lo;
                     }
                 }
+                int32_t my_ps = 0;
+                if constexpr (MATES) {
+                    if (!p.haploid && cov && hp == 1 && first0 < 0) my_ps = r_name >= 0 ? ps_name : p.read_ps[r];
+                    if (r_name >= 0) r = r_name;
+                }
                 if (member != 0) {
                     const int w = al0 + n_u + __popcll(m_u & lt);
                     p.al_read[w] = r;
@@ -466,11 +499,13 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
                         const int h = (v - (p.tile_pos0 + t * p.tile_size)) >> 10;
                         const int32_t *cur = p.ent_cur + (int64_t)e * NC_ENT_CUR_PITCH(p.spt);
                         p.al_ev[w] = make_int2(cur[h], h + 2 <= p.spt ? cur[h + 2] : p.ev_off[r + 1]);
+                        if constexpr (MATES) { if (r_name >= 0) p.al_ev[w] = make_int2(p.ev_off[r], p.ev_off[r + 1]); }      // (the cursors are the entry's own read's)
                     }
                 }
                 if (first0 < 0) {
                     const uint64_t mf = p.haploid ? m_all : m_1;
                     if (mf) first0 = __shfl(r, __ffsll((long long)mf) - 1);
+                    if constexpr (MATES) { if (mf) first_ps = __shfl(my_ps, __ffsll((long long)mf) - 1); }
                 }
             }
             n_all += __popcll(m_all);
@@ -490,6 +525,8 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
         p.site_pos[site] = v;
         p.site_chunk[site] = p.anc_chunk[a];
         p.site_type[site] = p.anc_type[a] & 1;                                          // (the window rule; bits 1-5: an imputed anchor's source)
+        if constexpr (MATES) p.site_phase[site] = (!p.haploid && first0 >= 0) ? first_ps : 0;
+        else
         p.site_phase[site] = (!p.haploid && first0 >= 0) ? p.read_ps[first0] : 0;       // :349 (set 0 holds HP-tagged reads only)
         p.site_al0[site] = al0;
         p.site_n2[site] = (int32_t)(b - v);
@@ -516,10 +553,13 @@ void nc_pipe_launch_flatten(hipStream_t st, int n_chunks, const PipeChunk *pc, c
 void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impute)
 {
     const dim3 grid((sa.n_anchor + 3) / 4);
-    if (fill && impute) hipLaunchKernelGGL((k_sets<true, true>), grid, dim3(256), 0, st, sa);
-    else if (fill) hipLaunchKernelGGL((k_sets<true, false>), grid, dim3(256), 0, st, sa);
-    else if (impute) hipLaunchKernelGGL((k_sets<false, true>), grid, dim3(256), 0, st, sa);
-    else hipLaunchKernelGGL((k_sets<false, false>), grid, dim3(256), 0, st, sa);
+    if (sa.mt.n > 0 && !impute) {                                     // (shared names with impute_indel_phase: refused by the plan)
+        if (fill) hipLaunchKernelGGL((k_sets<true, false, true>), grid, dim3(256), 0, st, sa);
+        else hipLaunchKernelGGL((k_sets<false, false, true>), grid, dim3(256), 0, st, sa);
+    } else if (fill && impute) hipLaunchKernelGGL((k_sets<true, true, false>), grid, dim3(256), 0, st, sa);
+    else if (fill) hipLaunchKernelGGL((k_sets<true, false, false>), grid, dim3(256), 0, st, sa);
+    else if (impute) hipLaunchKernelGGL((k_sets<false, true, false>), grid, dim3(256), 0, st, sa);
+    else hipLaunchKernelGGL((k_sets<false, false, false>), grid, dim3(256), 0, st, sa);
 }
 int nc_pipe_scan_i32(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int32_t *out)
 {

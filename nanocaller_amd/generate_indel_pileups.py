@@ -605,10 +605,11 @@ def device_indel_reads(ctg, flag, dp, device):
 
 
 def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, win_size, small_win_size, ins_t, del_t, window_after,
-                       haploid=False, excl=None, fetch=True, impute=False):
+                       haploid=False, excl=None, fetch=True, impute=False, mates=None):
     """nc_indel_sites_plan + _run (+ _fetch) for a list of (start, end) chunks of one contig -> dict: n, x (device float32
     [n, sets * 5, 128, 2]: the CNN input), and with fetch: pos / chunk / type / phase int32 [n], ref_len / alt_len int32 [n, sets],
-    alt (uint8 codes, the ALT prefixes back to back in (site, set) order).  Raises NanoCallerHipError with .status."""
+    alt (uint8 codes, the ALT prefixes back to back in (site, set) order).  mates: indel_mate_table's (key, rec) when kept alignments share read
+    names.  Raises NanoCallerHipError with .status."""
     L = eng.L
     prm = _lib.IndelScanParamsC(mincov=int(mincov), win_size=int(win_size), small_win_size=int(small_win_size), ins_t=float(ins_t),
                                 del_t=float(del_t), haploid=1 if haploid else 0, impute=1 if (impute and not haploid) else 0)
@@ -624,13 +625,21 @@ def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, w
             err.status = rc
             raise err
     check(L.nc_indel_sites_scoring(eng.ctx, *[int(v) for v in _lib.STAR_SCORING]), "nc_indel_sites_scoring")
-    check(L.nc_indel_sites_plan(eng.ctx, C.byref(pc), C.c_void_p(dp.ref_code.data_ptr()), dp.tile_pos0, dp.ref_code.numel(), int(chrom_len),
-                                C.byref(reads_c), C.c_void_p(excl.data_ptr()) if excl is not None else None, len(chunks), _lib.npp(starts),
-                                _lib.npp(ends), C.byref(prm), int(window_after), int(maxcov), C.byref(n), C.byref(na)), "nc_indel_sites_plan")
+    # alignments that share read names: the plan keys them by name from this table (none: no table, the plain kernels run).  The context borrows
+    # the pointers, so the table is cleared again once the plan's and the run's launches are enqueued, whatever their outcome
+    check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,
+                               C.c_void_p(mates[1].data_ptr()) if mates else None), "nc_indel_set_mates")
     S = 1 if haploid else 3
-    N = n.value
-    x = torch.empty((N, S * 5, 128, 2), dtype=torch.float32, device=eng.device)
-    check(L.nc_indel_sites_run(eng.ctx, C.c_void_p(x.data_ptr())), "nc_indel_sites_run")
+    try:
+        check(L.nc_indel_sites_plan(eng.ctx, C.byref(pc), C.c_void_p(dp.ref_code.data_ptr()), dp.tile_pos0, dp.ref_code.numel(), int(chrom_len),
+                                    C.byref(reads_c), C.c_void_p(excl.data_ptr()) if excl is not None else None, len(chunks), _lib.npp(starts),
+                                    _lib.npp(ends), C.byref(prm), int(window_after), int(maxcov), C.byref(n), C.byref(na)), "nc_indel_sites_plan")
+        N = n.value
+        x = torch.empty((N, S * 5, 128, 2), dtype=torch.float32, device=eng.device)
+        check(L.nc_indel_sites_run(eng.ctx, C.c_void_p(x.data_ptr())), "nc_indel_sites_run")
+    finally:
+        if mates:
+            L.nc_indel_set_mates(eng.ctx, 0, None, None)
     out = dict(n=N, sets=S, x=x, n_alignments=na.value)
     if fetch:
         out.update(indel_sites_fetch(eng, N, S))
@@ -656,17 +665,64 @@ def indel_sites_fetch(eng, N, S):
     return dict(pos=pos[:N], chunk=chunk[:N], type=typ[:N], phase=phase[:N], ref_len=rl[:N], alt_len=al[:N], alt=alt[:int(nb.value)])
 
 
-_DEV_INGEST = {}              # one contig at a time: (BAM, contig, FASTA, flag filter, device, file identity) -> (pack, nc_indel_reads, contig dict)
+MATE_RING_CAP = 64           # alignments of one read name that k_hap_depth_b, k_event_tiles and k_sets<.., true> walk (their `guard` loops)
 
 
-def _device_ingest_contig(dct, sam_path, chrom, supp, device):
+def indel_mate_table(dp, read_ps):
+    """nc_indel_set_mates' table of a pack whose kept alignments share read names (dp.mates: pack.mate_table's key / rec on the device), or None.
+    The reference keys hap_reads_0 / hap_reads_1 and phase_dict by name (generate_indel_pileups.py:178-188): a name is in a hap set when ANY of its
+    records carries that HP (in both when they disagree), and phase_dict[name] is the PS of its LAST record in file order, None (0 here) when that
+    record has no HP.  read_ps: the pack's PS per kept read (device int32).  -> (key int64 [M], rec int32 [M, 8]) device tensors.
+    A name with more than MATE_RING_CAP kept alignments is refused (NC_ERR_UNSUPPORTED): the kernels walk a ring that far and no further."""
+    if getattr(dp, "mates", None) is None or dp.reads is None or dp.events is None:
+        return None
+    key, rec4 = dp.mates
+    M = int(key.numel())
+    if M == 0:
+        return None
+    K = int(dp.reads["n_reads"])
+    r = torch.searchsorted(dp.reads["slot_off"][:K].contiguous(), key.contiguous())       # the member's index among the kept reads (slots are unique)
+    if int((r >= K).any()) or not bool((dp.reads["slot_off"][r] == key).all()):
+        raise _lib.NanoCallerHipError("indel_mate_table: the table of shared names is not this pack's")
+    rec4 = rec4.view(-1, 4).cpu().numpy()
+    hap = dp.events["read_hap"][r].cpu().numpy().astype(np.int32)
+    ps = read_ps[r].cpu().numpy().astype(np.int32)
+    idx = np.arange(M, dtype=np.int64)
+    nxt = rec4[:, 2].astype(np.int64)
+    if M < 2 or nxt.min() < 0 or nxt.max() >= M:
+        raise _lib.NanoCallerHipError("indel_mate_table: the table of shared names is not this pack's")
+    g, cur = idx.copy(), nxt.copy()                                 # the name's first member: the smallest index on the member's ring
+    for _ in range(MATE_RING_CAP - 1):                              # (cur: one hop further per step, held once it is back at the member)
+        g = np.minimum(g, cur)
+        cur = np.where(cur != idx, nxt[cur], cur)
+    if (cur != idx).any():
+        err = _lib.NanoCallerHipError("indel_mate_table: a read name with more than %d kept alignments (the first: alignment %d of the kept ones)"
+                                      % (MATE_RING_CAP, int(r[int(np.flatnonzero(cur != idx)[0])])))
+        err.status = _lib.NC_ERR_UNSUPPORTED
+        raise err
+    bits = np.zeros(M, np.int32)
+    np.bitwise_or.at(bits, g, np.where((hap == 1) | (hap == 2), 1 << (hap - 1).clip(0, 1), 0).astype(np.int32))
+    last = np.zeros(M, np.int64)
+    np.maximum.at(last, g, idx)
+    rec = np.zeros((M, 8), np.int32)
+    rec[:, :3] = rec4[:, :3]
+    rec[:, 3] = r.cpu().numpy()
+    rec[:, 4] = bits[g]
+    rec[:, 5] = np.where(hap[last[g]] != 0, ps[last[g]], 0)
+    return key.contiguous(), torch.from_numpy(rec).to(key.device)
+
+
+_DEV_INGEST = {}              # one contig at a time: (BAM, contig, FASTA, flag filter, device, by name or not, file identity) -> (pack, nc_indel_reads, contig dict, indel_mate_table or None)
+
+
+def _device_ingest_contig(dct, sam_path, chrom, supp, device, by_name=False):
     """The contig's read pack WITH the indel sections, made on the device from the BAM file itself (device_bam.py: inflate, record walk, codes,
     events, inserted bases and tails in HBM) -- what decoded_contig + device_pack + device_indel_reads assemble on host threads.  None when the
     input cannot take that route (no .bai, too large, NC_DEVICE_INGEST=0 / dct['device_ingest'] = False): the host route follows."""
     if not dct.get("device_ingest", os.environ.get("NC_DEVICE_INGEST", "1") != "0") or not isinstance(sam_path, str) or not os.path.exists(sam_path):
         return None
     st = os.stat(sam_path)
-    key = (sam_path, chrom, dct["fasta_path"], supp, device, st.st_size, st.st_mtime_ns)
+    key = (sam_path, chrom, dct["fasta_path"], supp, device, bool(by_name), st.st_size, st.st_mtime_ns)
     if key not in _DEV_INGEST:
         from .bam import read_fasta_bytes
         from .device_bam import DeviceIngestUnavailable, open_device_bam
@@ -677,21 +733,26 @@ def _device_ingest_contig(dct, sam_path, chrom, supp, device):
         except DeviceIngestUnavailable:
             return None
         fasta_b = read_fasta_bytes(dct["fasta_path"], chrom)
-        dp = dbam.pack(dbam.prepare(chrom, fasta_b, supplementary=supp, haplotags=getattr(sam_path, "tags", None)), indel=True, tail_cap=TAIL_CAP)
-        _DEV_INGEST[key] = (dp, indel_reads_struct(dp), dict(fasta=fasta_b.decode("ascii"), fasta_b=fasta_b, device_ingest=True))
+        dp = dbam.pack(dbam.prepare(chrom, fasta_b, supplementary=supp, haplotags=getattr(sam_path, "tags", None), by_name=bool(by_name)), indel=True,
+                       tail_cap=TAIL_CAP)
+        _DEV_INGEST[key] = (dp, indel_reads_struct(dp), dict(fasta=fasta_b.decode("ascii"), fasta_b=fasta_b, device_ingest=True),
+                            indel_mate_table(dp, dp.indel["read_ps"]) if by_name else None)
     return _DEV_INGEST[key]
 
 
-def _indel_pack_for(dct, chunks, device):
-    """(engine, read pack with the indel sections, nc_indel_reads struct, contig dict, exclusion mask or None) of the chunks' BAM and contig: made on the
-    device from the BAM file itself where that route is open (_device_ingest_contig), else from the host decode"""
+def _indel_pack_for(dct, chunks, device, by_name=False):
+    """(engine, read pack with the indel sections, nc_indel_reads struct, contig dict, exclusion mask or None, table of shared names or None) of the
+    chunks' BAM and contig: made on the device from the BAM file itself where that route is open (_device_ingest_contig), else from the host decode.
+    by_name (the device pipeline without impute_indel_phase): kept alignments that share a read name are not refused, and the last item is their
+    table for nc_indel_set_mates (None without by_name or when no name is shared).  The device-ingested packs of the two settings are cached apart;
+    the host decode's pack is one and the same (it always carries bit 3 and the name rings: by_name only lifts the refusal)."""
     chrom, sam_path = chunks[0]["chrom"], chunks[0]["sam_path"]
     supp = bool(dct.get("supplementary"))
     eng = get_engine(device)
     eng.use_torch_stream()
-    di = _device_ingest_contig(dct, sam_path, chrom, supp, device)
+    di = _device_ingest_contig(dct, sam_path, chrom, supp, device, by_name)
     if di is not None:
-        dp, reads_c, ctg = di
+        dp, reads_c, ctg, mates = di
     else:
         ctg = decoded_contig(sam_path, chrom, dct["fasta_path"])
         flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if supp else 0x800)
@@ -699,8 +760,14 @@ def _indel_pack_for(dct, chunks, device):
             from .pack import pileup_depth_cap
             dec = ctg["dec"]
             ctg["keep"][flag] = pileup_depth_cap(dec["read_start"], dec["read_end"], np.ascontiguousarray((dec["read_flag"] & flag) == 0, np.uint8))
-        dp = device_pack(sam_path, dct.get("fasta_path"), chrom, supp, None, device)[0]
+        dp = device_pack(sam_path, dct.get("fasta_path"), chrom, supp, None, device, by_name=by_name)[0]
         reads_c = device_indel_reads(ctg, flag, dp, device)
+        mates = None
+        if by_name and getattr(dp, "mates", None) is not None:
+            mk = ("dev_mates", flag, device)
+            if mk not in ctg or ctg[mk][0] is not dp:
+                ctg[mk] = (dp, indel_mate_table(dp, ctg[("dev_reads", flag, device)][1]["read_ps"]))
+            mates = ctg[mk][1]
     excl = None
     excl_rows = _exclude_rows(dct, chrom)
     if excl_rows:
@@ -708,14 +775,14 @@ def _indel_pack_for(dct, chunks, device):
         for (a, b) in excl_rows:
             m[max(0, a - dp.tile_pos0):max(0, b - dp.tile_pos0)] = 1
         excl = torch.from_numpy(m).to(eng.device)
-    return eng, dp, reads_c, ctg, excl
+    return eng, dp, reads_c, ctg, excl, mates
 
 
 def imputed_chunk_mask(dct, chunks, device):
     """impute_indel_phase (generate_indel_pileups.py:278-304) on the device pipeline: which chunks hold a column that meets the rule's COLUMN-level
     predicate (:278-284; K7's col_type 2 on the resident pack).  A chunk without one takes no imputed anchor, and its `variants` are those of the flag
     off -- it runs on the device pipeline; the others (their read grouping needs the pileup strings, :285-304) take the host-assembled route."""
-    eng, dp, _, _, excl = _indel_pack_for(dct, chunks, device)
+    eng, dp, _, _, excl, _ = _indel_pack_for(dct, chunks, device)
     cols = eng.indel_scan_batch(dp, [(c["start"], c["end"]) for c in chunks], mincov=dct["mincov"], win_size=dct["win_size"],
                                 small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"], excl=excl, haploid=False, impute=True)
     return [bool((ct == 2).any()) for ct in cols]
@@ -724,10 +791,14 @@ def imputed_chunk_mask(dct, chunks, device):
 def indel_sites_for_chunks(dct, chunks, device, haploid, fetch=True):
     """The device pipeline for chunks (ascending) of one BAM and contig -> (result dict of indel_sites_device, contig dict)"""
     window_after = 260 if dct["seq"] == "pacbio" else 160
-    eng, dp, reads_c, ctg, excl = _indel_pack_for(dct, chunks, device)
+    # shared read names are keyed by name here (nc_indel_set_mates), except with impute_indel_phase (diploid), whose read grouping is per alignment:
+    # that combination keeps the refusal
+    by_name = haploid or not dct.get("impute_indel_phase")
+    eng, dp, reads_c, ctg, excl, mates = _indel_pack_for(dct, chunks, device, by_name=by_name)
     r = indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), [(c["start"], c["end"]) for c in chunks], mincov=dct["mincov"], maxcov=dct["maxcov"],
                            win_size=dct["win_size"], small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"],
-                           window_after=window_after, haploid=haploid, excl=excl, fetch=fetch, impute=bool(dct.get("impute_indel_phase")))
+                           window_after=window_after, haploid=haploid, excl=excl, fetch=fetch, impute=bool(dct.get("impute_indel_phase")),
+                           mates=mates)
     return r, ctg
 
 

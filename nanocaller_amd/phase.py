@@ -148,7 +148,7 @@ def _realign_inputs(sam_path, fasta_path, chrom, supplementary, device):
                                       "the reads' query windows from (the column rule is not substituted)" % (sam_path,))
     from . import generate_indel_pileups as gip
     dct = dict(fasta_path=fasta_path, supplementary=bool(supplementary))
-    eng, dp, reads_c, ctg, _ = gip._indel_pack_for(dct, [dict(chrom=chrom, sam_path=sam_path)], device)
+    eng, dp, reads_c, ctg, _, _ = gip._indel_pack_for(dct, [dict(chrom=chrom, sam_path=sam_path)], device)
     if ctg.get("device_ingest"):
         ix = dp.indel
     else:

@@ -5,6 +5,7 @@
     python3 tools/isa_diff.py OLD -- NEW1 NEW2 ...         # several files a side (a unit that was split): the union of their functions
     python3 tools/isa_diff.py --rev HEAD --into a.hip,b.hip nanocaller_amd/csrc/nc_pipe.hip      # FILE at REV against the units it was split into
     python3 tools/isa_diff.py --rev HEAD nanocaller_amd/csrc/nc_cnn_h3.hip ...   # each file at REV against the working tree
+    python3 tools/isa_diff.py --ignore-kernarg-size --rev HEAD FILE              # ... an appended, unread kernel argument does not count
 
 A .hip file is compiled with `hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only`; with --rev the sources of REV
 (nanocaller_amd/csrc and include, from `git archive`) are compiled in a temporary directory.  Each listing is split into
@@ -90,9 +91,14 @@ def union(paths):
     return out
 
 
+IGNORE_KERNARG = False
+
+
 def compare(old_s, new_s, label):
     """old_s / new_s: a listing or a list of listings"""
     a, b = union([old_s] if isinstance(old_s, str) else old_s), union([new_s] if isinstance(new_s, str) else new_s)
+    if IGNORE_KERNARG:                                                   # (an argument appended that the kernel never loads: the instructions decide)
+        a, b = ({n: [ln for ln in body if not ln.startswith(".amdhsa_kernarg_size")] for n, body in d.items()} for d in (a, b))
     bad = renamed = 0
     gone, new = set(a) - set(b), set(b) - set(a)
     for n in sorted(new):
@@ -124,8 +130,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--rev", help="compare each FILE at this git revision against the working tree")
     ap.add_argument("--into", help="with --rev: comma-separated working-tree files that replace FILE (default: FILE itself)")
+    ap.add_argument("--ignore-kernarg-size", action="store_true", help="leave the .amdhsa_kernarg_size line out of the comparison")
     ap.add_argument("files", nargs="+")
     args = ap.parse_args()
+    global IGNORE_KERNARG
+    IGNORE_KERNARG = args.ignore_kernarg_size
     bad = 0
     with tempfile.TemporaryDirectory() as td:
         if args.rev:
