@@ -49,9 +49,6 @@ struct nc_weights {
     float x_limit = 0.0f;      // largest |input value| for which the L1 norms of conv1-3 prove that no activation reaches the fp16 clamp
 };
 
-// words per tile entry of the K7 cursor table (k_entry_cursors, nc_indel.hip) for spt 1024-column blocks per tile
-#define NC_ENT_CUR_PITCH(spt) (2 * (spt) + 3)
-
 struct nc_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -64,7 +61,6 @@ struct nc_ctx {
     bool huff_lds_set = false;              // k_huff: the same
     bool deflate_lds_set = false;           // k_deflate (nc_bamwrite.hip): the same
     DevBuf deflate_tok;                     // k_deflate's token slots: 65,536 per workgroup
-    size_t k7_budget = 0;                   // bytes of K7 workspace per group of chunks (set from this context's device at its first plan)
     // alignments that share a read name (nc_snp_set_mates): borrowed device pointers, read by the next nc_snp_featurize calls
     int32_t n_mates = 0;
     const int64_t *mate_key = nullptr;
@@ -73,7 +69,6 @@ struct nc_ctx {
     int32_t n_imates = 0;
     const int64_t *imate_key = nullptr;
     const int32_t *imate_rec = nullptr;
-    bool k7_budget_shrunk = false;          // the budget was cut to half of what was free at some plan: restored when memory allows again
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms[6] = {0, 0, 0, 0, 0, 0};   // 0 scan, 1 featurize, 2 cnn stage, 3 indel, 4 trunk kernel total, 5 trunk launches
     hipEvent_t kev[128] = {nullptr};          // per-launch event pairs of the trunk kernel (timing mode)
@@ -97,10 +92,14 @@ struct nc_ctx {
     DevBuf cnn_a, cnn_b, cnn_c;                           // CNN intermediates
     DevBuf chunk_depth;                                   // double per chunk
     DevBuf nbr_idx;                                       // coarse index over nbr_pos
-    DevBuf indel_ws;                                      // indel window-scan workspace
-    DevBuf indel_ent_read;                                // read index of every tile entry + its event cursors per 1024-column block (k_entry_cursors)
-    const void *indel_ent_of = nullptr;                   // the tile index (tile_ent) those tables were last made for, NULL: none (pass 1 ran in another form)
-    int indel_ent_spt = 0;                                // 1024-column blocks per tile of that index
+    struct {                                              // K7, the indel window scan (nc_indel.hip and its two forms' units)
+        size_t budget = 0;                                // bytes of workspace per group of chunks (set from this context's device at its first plan)
+        bool budget_shrunk = false;                       // the budget was cut to half of what was free at some plan: restored when memory allows again
+        DevBuf ws;                                        // the workspace
+        DevBuf ent_read;                                  // read index of every tile entry + its event cursors per 1024-column block (k_read_cursors + k_entry_rows)
+        const void *ent_of = nullptr;                     // the tile index (tile_ent) those tables were last made for, NULL: none (pass 1 ran in the accumulate form)
+        int ent_spt = 0;                                  // 1024-column blocks per tile of that index
+    } k7;
     DevBuf msa_reads, msa_read_off, msa_read_set, msa_refs, msa_ref_off;   // device star alignment (nc_msa.hip): inputs,
     DevBuf msa_dup;                                        // duplicate map + list of alignments to compute (nc_star_msa_tensor_dup)
     DevBuf msa_rows_hf, msa_hcol, msa_tb, msa_trace, msa_cols, msa_out;    // DP rows / last column / traceback bytes / alignments / columns / rows
@@ -229,44 +228,3 @@ struct NcTimer {
 // implemented in the kernel translation units
 int nc_selftest_device(nc_ctx *ctx);
 void nc_pipe_destroy(nc_ctx *ctx);          // nc_pipe.hip
-
-// K7 (nc_indel.hip): one chunk of a batched window scan
-struct IndelChunk {
-    int32_t lo, hi, ncol, nd;
-    int64_t ws;          // byte offset of depth[3][ncol] | rank[ncol+1] | diff[8][nd] | (impute) cnt[3][ncol] in the workspace
-    int64_t coloff;      // offset of this chunk's col_type in the concatenated output
-    int32_t tile0, blk0; // first tile of the chunk on the pack's grid, first k_hap_depth_b block of the chunk
-};
-// Alignments that share a read name, for the indel kernels (nc_indel_set_mates; the <.., MATES = true> forms of k_hap_depth_b, k_event_tiles, k_sets).
-// The reference keys its hap sets, phase_dict, the per-column event sets and pass 2's read dicts by NAME (generate_indel_pileups.py:180-188,218-235,
-// 310-338).  key [n] = byte offset of the alignment's slot in the pack's codes, ascending (= file order); rec [n][8] int32 = start, end, table index of
-// the name's next alignment (a ring in file order), the alignment's index among the kept reads | the name's haplotype mask (bit 0: a record of the
-// name has HP 1, bit 1: HP 2), phase_dict[name] (PS of the name's last record, 0 when that record has no HP), 0, 0.
-struct IndelMates {
-    const int64_t *key;
-    const int32_t *rec;
-    int32_t n;
-};
-#if defined(__HIPCC__)
-struct IndelMate { int32_t start, end, next, read, hap, ps; };
-__device__ __forceinline__ IndelMate imate_get(const IndelMates &m, int i)
-{
-    const int4 a = reinterpret_cast<const int4 *>(m.rec)[2 * i];
-    const int2 b = reinterpret_cast<const int2 *>(m.rec)[4 * i + 2];
-    return IndelMate{a.x, a.y, a.z, a.w, b.x, b.y};
-}
-// the table index of the alignment whose slot starts at byte `key`; -1: none (an entry flagged without a row: a table of another pack)
-__device__ __forceinline__ int imate_find(const IndelMates &m, int64_t key)
-{
-    int lo = 0, hi = m.n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (m.key[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo < m.n && m.key[lo] == key ? lo : -1;
-}
-#endif
-
-// K7 for the device pipeline's plan (nc_pipe.hip): a group of chunks enqueued, col_type left on the device; the argument checks of the scan
-int nc_indel_scan_group_launch(nc_ctx *ctx, const nc_readpack *pack, const nc_indel_events *ev, const uint8_t *excl_dev, int32_t n_chunks,
-                               const int32_t *starts, const int32_t *ends, const nc_indel_scan_params *prm, int32_t *consumed,
-                               std::vector<IndelChunk> &ck, const IndelChunk **ck_dev_out, const int8_t **ctype_out, const int64_t *slot_off_dev, int32_t *err_bits_dev,
-                               const int32_t *rd_start_dev, const int32_t *rd_end_dev, bool reuse_tables, const IndelMates *mates = nullptr);
-int nc_indel_check(nc_ctx *ctx, const nc_readpack *pack, const nc_indel_events *ev, const nc_indel_scan_params *prm, const char *who);

@@ -11,6 +11,7 @@
 //   nc_pipe.hip          nc_pipe_state, the nc_indel_sites_* entry points, the group driver
 #pragma once
 #include "nc_common.h"
+#include "nc_indel.h"
 
 constexpr int PICK_CAP = 12288;        // anchors of one chunk held in LDS by k_pick (a 100 kb chunk has at most 9,092), one packed word each: 48 KB, three waves per CU
 constexpr int IMP_CAP = 512;           // reads of one column that impute_group can group (a deeper column raises the capacity bit)
@@ -68,7 +69,7 @@ struct SetArgs {
     int32_t *site_pos, *site_chunk, *site_type, *site_phase, *site_al0, *site_nr, *site_n2;
     int32_t *al_read, *al_site;
     uint8_t *al_member;
-    // K7's per-entry tables (k_entry_cursors; NULL when pass 1 ran without them): the read of every tile entry, and its first event at or after every
+    // K7's per-entry tables (k_read_cursors + k_entry_rows; NULL when pass 1 ran without them): the read of every tile entry, and its first event at or after every
     // 1024-column block of the tile (less 64 columns) -> the read without a search, and for k_windows the short stretch of the read's events around the anchor
     const int32_t *ent_read, *ent_cur, *ev_off;
     int32_t spt;

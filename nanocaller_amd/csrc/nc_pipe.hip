@@ -139,14 +139,13 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     imp.ev_off = reads->ev_off; imp.ev_pos = reads->ev_pos; imp.ev_len = reads->ev_len; imp.ins_off = reads->ins_off; imp.ins_bases = reads->ins_bases;
     imp.mincov = prm->mincov;
     int32_t c0 = 0;
-    std::vector<IndelChunk> ck;
+    IndelGroupOut k7;
     while (c0 < n_chunks) {
-        int32_t used = 0;
-        const IndelChunk *ck_dev = nullptr;
-        const int8_t *ctype = nullptr;
-        NC_TRY(nc_indel_scan_group_launch(ctx, pack, &ev, excl_dev, n_chunks - c0, starts + c0, ends + c0, prm, &used, ck, &ck_dev, &ctype,
-                                          ev.n_reads == reads->n_reads ? reads->slot_off : nullptr, err, reads->rd_start, reads->rd_end, c0 > 0, &mates));
-        for (int32_t k = 0; k < used; k++) pcs[(size_t)(c0 + k)].coloff = ck[(size_t)k].coloff;
+        const IndelPipeIn k7in = {reads->slot_off, reads->rd_start, reads->rd_end, err, c0 > 0, mates};
+        NC_TRY(nc_indel_scan_group_launch(ctx, pack, &ev, excl_dev, n_chunks - c0, starts + c0, ends + c0, prm, &k7in, &k7));
+        const int32_t used = k7.consumed;
+        const int8_t *ctype = k7.ctype;
+        for (int32_t k = 0; k < used; k++) pcs[(size_t)(c0 + k)].coloff = k7.ck[(size_t)k].coloff;
         NC_TRY(nc_h2d_pieces(ctx, (PipeChunk *)s->pc.p + c0, pcs.data() + c0, (size_t)used * sizeof(PipeChunk), ctx->stream));
         if (impute) {                                                 // the read grouping of every col_type-2 column: 3 (an anchor) or -1
             int32_t maxcol = 1;
@@ -192,9 +191,9 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     sa.ref_code = ref_code_dev; sa.ref_pos0 = ref_pos0; sa.ref_len = ref_len; sa.chrom_len = chrom_len;
     sa.window_after = window_after; sa.maxcov = maxcov; sa.mincov = prm->mincov; sa.haploid = s->haploid;
     sa.slot_off = reads->slot_off; sa.read_ps = reads->read_ps; sa.n_reads = reads->n_reads;
-    const bool have_ent = ctx->indel_ent_of == (const void *)pack->tile_ent && ctx->indel_ent_read.p;
+    const bool have_ent = ctx->k7.ent_of == (const void *)pack->tile_ent && ctx->k7.ent_read.p;
     if (have_ent) {
-        sa.ent_read = (const int32_t *)ctx->indel_ent_read.p; sa.ent_cur = sa.ent_read + pack->n_entries; sa.ev_off = reads->ev_off; sa.spt = ctx->indel_ent_spt;
+        sa.ent_read = (const int32_t *)ctx->k7.ent_read.p; sa.ent_cur = sa.ent_read + pack->n_entries; sa.ev_off = reads->ev_off; sa.spt = ctx->k7.ent_spt;
     }
     sa.n_anchor = na; sa.anc_pos = (const int32_t *)s->anc_pos.p; sa.anc_chunk = (const int32_t *)s->anc_chunk.p; sa.anc_type = (const int8_t *)s->anc_type.p;
     sa.kept = (int32_t *)s->kept.p; sa.nuniq = (int32_t *)s->nuniq.p;

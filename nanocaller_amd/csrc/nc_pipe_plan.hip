@@ -1,4 +1,4 @@
-// Device indel pipeline, the plan (nc_indel_sites_plan): from K7's column types (nc_indel.hip; col_type stays in HBM) to the sites and their read sets.
+// Device indel pipeline, the plan (nc_indel_sites_plan): from K7's column types (nc_indel.hip and its units; col_type stays in HBM) to the sites and their read sets.
 //   k_impute_flags  dct['impute_indel_phase']: every col_type-2 column -> 3 (an anchor by the read grouping) or -1
 //   k_pick          one wave per chunk: the order-dependent anchor selection `if v_pos <= prev: continue` (:249,266-275) with the
 //                   dict semantics of `variants[anchor] = type`, then the pass-2 range test (:306)

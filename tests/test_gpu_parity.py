@@ -630,6 +630,35 @@ def test_indel_scan_batch_equals_per_chunk_calls(eng, haploid):
     assert n > 300
 
 
+def test_indel_scan_batch_is_the_same_on_every_tile_size(eng):
+    """the stand-alone scan (accumulate form) on packs of 1024-, 2048- and 4096-column tiles (k_hap_depth_b<64 / 128 / 256>, chosen by the launcher): the
+    same per-column decisions, diploid, haploid and with impute_indel_phase.  The 2048 form is the one the reference's captures pin"""
+    import torch
+    from nanocaller_amd.pack import pack_world
+    world = load_world("indel")
+    # one ascending list: a one-column chunk, two that overlap, one over column 12,288 (a tile boundary of every size), one with an excluded stretch,
+    # one that reaches past the last read and past every pack's tile grid
+    chunks = [(3_000, 3_000), (5_000, 9_500), (8_200, 12_000), (12_100, 12_500), (20_000, 33_000), (58_000, world.length + 2_000)]
+    assert all(b[0] >= a[0] and b[1] >= a[1] for a, b in zip(chunks, chunks[1:]))
+    got = {}
+    for T in (1024, 2048, 4096):
+        dp = eng.upload(pack_world(world, tile_size=T))
+        assert dp.tile_size == T and (12_100 - dp.tile_pos0) // T < (12_500 - dp.tile_pos0) // T
+        assert chunks[0][0] >= dp.tile_pos0 and chunks[-1][1] > dp.tile_pos0 + dp.n_tiles * T - 1 > int(world.read_end.max())
+        # the exclusion mask on the pack's own grid (index 0 = tile_pos0), as long as the last chunk's columns
+        excl = torch.zeros(max(dp.n_tiles * T, chunks[-1][1] + 1 - dp.tile_pos0), dtype=torch.uint8, device="cuda")
+        excl[30_000 - dp.tile_pos0:31_500 - dp.tile_pos0] = 1
+        for name, kw in (("diploid", dict()), ("haploid", dict(haploid=True)), ("impute", dict(impute=True))):
+            got[T, name] = eng.indel_scan_batch(dp, chunks, excl=excl, mincov=4, win_size=40, small_win_size=4, ins_t=0.4, del_t=0.6, **kw)
+    for name in ("diploid", "haploid", "impute"):
+        ref = got[2048, name]
+        assert [len(g) for g in ref] == [b - a + 1 for a, b in chunks]
+        assert sum(int((g >= 0).sum()) for g in ref) > 0 and not np.any(ref[4][30_000 - 20_000:31_500 - 20_000] >= 0), name
+        for T in (1024, 4096):
+            for (a, b), g, r in zip(chunks, got[T, name], ref):
+                assert np.array_equal(g, r), (name, T, a, b)
+
+
 def test_indel_scan_chunk_list_matches_reference_pass1(eng):
     """the chunk-list form of scan_indel_candidates (one set of launches for all chunks) against the reference's captured
     `variants` of every chunk"""

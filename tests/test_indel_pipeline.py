@@ -738,6 +738,36 @@ def test_tiled_event_windows_equal_the_atomic_form(monkeypatch):
             assert np.array_equal(np.asarray(cut[key]), np.asarray(new[key])), (key, variant.keys())
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("tile_size", [1024, 4096])
+def test_tiled_event_windows_equal_the_atomic_form_off_the_default_tile_size(monkeypatch, tile_size):
+    """the same comparison on packs of 1024- and 4096-column tiles (k_hap_depth_b<64> / <256>, one / four blocks of k_event_tiles per tile): the
+    launcher picks the kernels' tile-size forms, and every other test of the device pipeline runs on 2048-column tiles"""
+    from nanocaller_amd.engine import get_engine
+    from nanocaller_amd.synth_device import make_indel_device_workload
+    eng = get_engine(0)
+    L = 200_000
+    pack, reads_c, info = make_indel_device_workload(eng, L, depth=30.0, seed=4711, tile_size=tile_size)
+    assert pack.tile_size == tile_size
+    # chunks that do not sit on the tile grid: one shorter than a workgroup's 1024 columns, the next over many tile boundaries
+    cuts = [1, 70_123, 70_900, 131_555, L]
+    chunks = [(a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+    assert all((a - pack.tile_pos0) % tile_size and (b + 1 - pack.tile_pos0) % tile_size for a, b in chunks)
+    assert (70_900 - pack.tile_pos0) // tile_size < (131_555 - pack.tile_pos0) // tile_size
+    kw = dict(mincov=4, maxcov=160, win_size=40, small_win_size=4, ins_t=0.4, del_t=0.6, window_after=160)
+    for variant in (dict(), dict(haploid=True)):
+        monkeypatch.delenv("NC_K7_EVENT_ATOMICS", raising=False)
+        new = gip.indel_sites_device(eng, pack, reads_c, L, chunks, **kw, **variant)
+        monkeypatch.setenv("NC_K7_EVENT_ATOMICS", "1")
+        old = gip.indel_sites_device(eng, pack, reads_c, L, chunks, **kw, **variant)
+        monkeypatch.delenv("NC_K7_EVENT_ATOMICS")
+        # (one het indel planted per 5,000 bases: about 40 here)
+        assert new["n"] == old["n"] and new["n"] >= 20, (variant.keys(), new["n"], old["n"])
+        for key in ("pos", "chunk", "type", "phase", "ref_len", "alt_len"):
+            assert np.array_equal(np.asarray(new[key]), np.asarray(old[key])), (key, variant.keys())
+        assert bool((new["x"] == old["x"]).all())
+
+
 def _window_dump(tmp_path, tag):
     """the per-alignment arrays NC_PIPE_DUMP left: rows cut to their lengths"""
     d = {n: np.fromfile(str(tmp_path / (tag + "." + n)), dt) for n, dt in (("n1", np.int32), ("band_lo", np.int8), ("al_read", np.int32), ("al_site", np.int32), ("win", np.uint8))}

@@ -4,6 +4,7 @@
     python3 tools/isa_diff.py OLD NEW                      # two .s listings, or two .hip files (compiled here)
     python3 tools/isa_diff.py OLD -- NEW1 NEW2 ...         # several files a side (a unit that was split): the union of their functions
     python3 tools/isa_diff.py --rev HEAD --into a.hip,b.hip nanocaller_amd/csrc/nc_pipe.hip      # FILE at REV against the units it was split into
+    python3 tools/isa_diff.py old/nc_indel.hip old/nc_msa.hip -- nc_indel.hip nc_indel_tiles.hip nc_indel_accum.hip nc_msa.hip   # code that moved between units too
     python3 tools/isa_diff.py --rev HEAD nanocaller_amd/csrc/nc_cnn_h3.hip ...   # each file at REV against the working tree
     python3 tools/isa_diff.py --ignore-kernarg-size --rev HEAD FILE              # ... an appended, unread kernel argument does not count
 
