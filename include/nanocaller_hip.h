@@ -866,7 +866,14 @@ int nc_synth_indel_reads(nc_ctx *ctx, int64_t L, uint64_t seed, double p_sub, do
  * nc_haplotag_run: read_group [n_reads] (host) = name group 0 .. n_groups-1 of every read; scores of one name are summed -> HP / PS.
  * nc_snp_phase_view: host views of the handle's arrays (valid until the next call on the handle or nc_snp_phase_free).
  *   read_side: -1 not accepted, else the read's part (0 = HP 1); site_block: -1 outside blocks; site_h: allele carried by HP 1;
- *   site_ps: 0 when unphased; group_hp 0 (untagged) / 1 / 2, group_ps 0 when untagged; ms: gather, selection, DP, haplotag wall times. */
+ *   site_ps: 0 when unphased; group_hp 0 (untagged) / 1 / 2, group_ps 0 when untagged; ms: gather, selection, DP, haplotag wall times.
+ * nc_snp_phase_solve_gt: nc_snp_phase_solve on sites whose genotypes are not trusted (WhatsHap's --distrust-genotypes with
+ *   --include-homozygous, restated in DESIGN.md).  site_gt [n_sites] (host): the called class of every site, 0 = het, 1 / 2 = homozygous
+ *   for the first / second allele; gt_cost in [1, 1024]: the price G of leaving the called class.  A column costs the cheapest of het
+ *   (min(c0, c1)), every read on the first allele (popc(M1)) and every read on the second (popc(M0)), each plus G unless it is the called
+ *   class; ties go to the called class, then het, first, second.  site_phased then also needs the outcome het.
+ * nc_snp_phase_genotypes: *site_gt = the outcome class per site [n_sites] after nc_snp_phase_solve_gt (a site outside the blocks keeps its
+ *   call), NULL after the plain solve; valid as nc_snp_phase_view's arrays are. */
 typedef struct nc_phase nc_phase;
 typedef struct {
     int32_t n_reads, n_sites, n_blocks, n_groups;
@@ -895,6 +902,8 @@ int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov);
 int nc_haplotag_run(nc_ctx *ctx, nc_phase *ph, int32_t n_groups, const int32_t *read_group);
 int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out);
 int nc_snp_phase_free(nc_phase *ph);
+int nc_snp_phase_solve_gt(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost);
+int nc_snp_phase_genotypes(const nc_phase *ph, const uint8_t **site_gt);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,7 @@ struct nc_phase {
     std::vector<int8_t> side;
     std::vector<int32_t> site_block, site_ps, block_first, block_last, block_ps;
     std::vector<uint8_t> site_h, site_phased, group_hp;
+    std::vector<uint8_t> site_gt;          // nc_snp_phase_solve_gt only: the outcome per site (0 het, 1 / 2 homozygous first / second allele)
     std::vector<int64_t> block_cost;
     std::vector<int32_t> group_ps;
     float ms[4] = {0, 0, 0, 0};

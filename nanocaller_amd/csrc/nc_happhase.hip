@@ -7,23 +7,40 @@
 //   k_hp_gather<true>   per read: the (site, allele) CSR entries
 //   (nc_hprealign.hip)  instead of k_hp_gather, opt-in: the alleles by local realignment of the read against both haplotypes
 //   host                read selection (max_cov), blocks, slot assignment, per-column masks, backtrace offsets
-//   k_hp_dp             one workgroup per block: the 2^15 partition costs in LDS (uint16, relative to the column minimum),
+//   k_hp_dp<false>      one workgroup per block: the 2^15 partition costs in LDS (uint16, relative to the column minimum),
 //                       leaving slots minimised out, backtrace in HBM, traceback by the same workgroup
+//   k_hp_dp<true>       opt-in (nc_snp_phase_solve_gt): the same walk with a column cost that may also call the site homozygous
+//                       for either allele, at a price for leaving the called genotype; the traceback records each column's outcome
 //   k_hp_tag            one thread per read-name group: per-block scores -> HP / PS
 #include "nc_happhase.h"
 
 #include <algorithm>
 #include <chrono>
 #include <climits>
+#include <type_traits>
 #include <vector>
 
 namespace {
 
 constexpr int HP_SLOTS = 15;
 constexpr int HP_STATES = 1 << HP_SLOTS;
+constexpr int HP_GT_COST_MAX = 1024;       // (a column's cost stays far inside the DP's 16-bit relative range)
 
 struct HpCol {            // one column of a block: the active slots, those continuing from the previous column, the allele masks
     uint16_t act, keep, m0, m1;
+};
+
+struct HpColGt {          // the genotype-aware form's column: the same, and the site's called class (0 het, 1 / 2 homozygous first / second allele)
+    uint16_t act, keep, m0, m1, gt, pad;
+};
+
+// the genotype-aware column cost: het(B) = min(e0, e1) + hadd, against the two constants homA / homB of the column
+struct HpGtCost {
+    uint32_t hadd, homA, homB;
+    __device__ __forceinline__ HpGtCost(uint32_t m0, uint32_t m1, uint32_t gt, uint32_t G)
+        : hadd(gt == 0 ? 0u : G), homA(__popc(m1) + (gt == 1 ? 0u : G)), homB(__popc(m0) + (gt == 2 ? 0u : G))
+    {
+    }
 };
 
 __device__ __forceinline__ uint32_t hp_pdep(uint32_t t, uint32_t mask)
@@ -82,10 +99,13 @@ __global__ __launch_bounds__(256) void k_hp_gather(const uint8_t *__restrict__ c
 // One workgroup per block [bfirst, blast] of columns (= sites).  D(j, B) for the subsets B of the active slots lives in LDS as
 // uint16 relative to the column minimum (the minima are summed into the block's cost); P(b) for the subsets of the continuing
 // slots, the backtrace (smallest minimising bits of the leaving slots) per (column, continuing subset) in HBM at bt_off[column].
-__global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ cols, const int32_t *__restrict__ bfirst,
+// GT: the genotype-aware form (its column carries the called class; gt_cost = the price G of leaving it; colg[column] = the outcome, classed
+// as the called class is).  The plain form reads neither argument.
+template <bool GT>
+__global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<GT, HpColGt, HpCol> *__restrict__ cols, const int32_t *__restrict__ bfirst,
                                                        const int32_t *__restrict__ blast, const int64_t *__restrict__ bt_off, uint16_t *__restrict__ bt,
                                                        uint16_t *__restrict__ colB, uint8_t *__restrict__ colh, int64_t *__restrict__ bcost,
-                                                       int32_t *__restrict__ overflow)
+                                                       int32_t *__restrict__ overflow, uint8_t *__restrict__ colg, uint32_t gt_cost)
 {
     __shared__ uint16_t D[HP_STATES];
     __shared__ uint16_t P[HP_STATES];
@@ -96,8 +116,14 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ 
     int64_t total = 0;
     uint32_t prevA = 0;
     for (int32_t j = c0; j <= c1; j++) {
-        const HpCol c = cols[j];
+        const auto c = cols[j];
         const uint32_t A = c.act, K = c.keep, m0 = c.m0, m1 = c.m1;
+        uint32_t hadd = 0, hom = 0;                                      // (GT) het's surcharge, the cheaper homozygous outcome
+        if constexpr (GT) {
+            const HpGtCost g(m0, m1, c.gt, gt_cost);
+            hadd = g.hadd;
+            hom = min(g.homA, g.homB);
+        }
         if (j > c0) {
             const uint32_t Lm = prevA & ~K;
             const int nk = __popc(K), nl = __popc(Lm);
@@ -141,7 +167,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ 
         for (int32_t t = tid; t < NA; t += HP_THREADS) {
             const uint32_t B = hp_pdep(t, A);
             const uint32_t e0 = __popc(m1 & ~B) + __popc(m0 & B), e1 = __popc(m0 & ~B) + __popc(m1 & B);
-            mn = min(mn, (first ? 0u : (uint32_t)P[B & K]) + min(e0, e1));
+            mn = min(mn, (first ? 0u : (uint32_t)P[B & K]) + (GT ? min(min(e0, e1) + hadd, hom) : min(e0, e1)));
         }
         mn = hp_wave_min(mn);
         if (lane == 0 && mn != ~0u) atomicMin(&smin, mn);
@@ -150,7 +176,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ 
         for (int32_t t = tid; t < NA; t += HP_THREADS) {
             const uint32_t B = hp_pdep(t, A);
             const uint32_t e0 = __popc(m1 & ~B) + __popc(m0 & B), e1 = __popc(m0 & ~B) + __popc(m1 & B);
-            const uint32_t v = (first ? 0u : (uint32_t)P[B & K]) + min(e0, e1) - cmin;
+            const uint32_t v = (first ? 0u : (uint32_t)P[B & K]) + (GT ? min(min(e0, e1) + hadd, hom) : min(e0, e1)) - cmin;
             if (v > 0xFFFFu) atomicOr(overflow, 1);
             D[B] = (uint16_t)min(v, 0xFFFFu);
         }
@@ -176,10 +202,18 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ 
     if (tid == 0) {
         uint32_t B = smin & 0xFFFF;
         for (int32_t j = c1; j >= c0; j--) {
-            const HpCol c = cols[j];
+            const auto c = cols[j];
             const uint32_t e0 = __popc(c.m1 & ~B) + __popc(c.m0 & B), e1 = __popc(c.m0 & ~B) + __popc(c.m1 & B);
             colB[j] = (uint16_t)B;
             colh[j] = e0 <= e1 ? 0 : 1;
+            if constexpr (GT) {
+                // the smallest (cost, pref): pref 0 for the called class, else 1 het, 2 homozygous first, 3 homozygous second
+                const HpGtCost g(c.m0, c.m1, c.gt, gt_cost);
+                const uint32_t cost[3] = {min(e0, e1) + g.hadd, g.homA, g.homB};
+                uint32_t best = ~0u;
+                for (uint32_t o = 0; o < 3; o++) best = min(best, (cost[o] << 4) | ((o == c.gt ? 0u : o + 1) << 2) | o);
+                colg[j] = (uint8_t)(best & 3);
+            }
             if (j > c0) {
                 const uint32_t bk = B & c.keep;
                 B = bk | bt[bt_off[j] + hp_pext(bk, c.keep)];
@@ -378,9 +412,9 @@ int nc_snp_phase_load(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32
     return NC_OK;
 }
 
-int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
+// site_gt: null for the plain solve; else the called class of every site, and gt_cost the price of leaving it (the genotype-aware form)
+static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost)
 {
-    if (!ctx || !ph || max_cov < 1 || max_cov > HP_SLOTS) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_solve: max_cov must lie in [1, %d]", HP_SLOTS);
     const double t0 = hp_now_ms();
     const int32_t R = ph->n_reads, S = ph->n_sites;
     const std::vector<int64_t> &off = ph->off;
@@ -420,6 +454,8 @@ int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
     ph->site_h.assign(S, 0);
     ph->site_phased.assign(S, 0);
     ph->site_ps.assign(S, 0);
+    ph->site_gt.clear();
+    if (site_gt) ph->site_gt.assign(site_gt, site_gt + S);              // outside the blocks the outcome is the call
     ph->side.assign(R, -1);
     ph->block_first.clear();
     ph->block_last.clear();
@@ -482,17 +518,27 @@ int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
     ph->ms[1] = (float)(hp_now_ms() - t0);
     const double t1 = hp_now_ms();
     std::vector<uint16_t> colB(S + 1, 0);
-    std::vector<uint8_t> colh(S + 1, 0);
+    std::vector<uint8_t> colh(S + 1, 0), colg(S + 1, 0);
     ph->block_cost.assign(nblk, 0);
     int32_t overflow = 0;
     if (nblk) {
         HpScratch sc;
         HpCol *d_cols = nullptr;
+        HpColGt *d_gcols = nullptr;
+        uint8_t *d_colg = nullptr;
         int32_t *d_bf = nullptr, *d_bl = nullptr, *d_ovf = nullptr;
         int64_t *d_bto = nullptr, *d_cost = nullptr;
         uint16_t *d_bt = nullptr, *d_colB = nullptr;
         uint8_t *d_colh = nullptr;
-        NC_TRY(sc.get(ctx, &d_cols, S + 1));
+        std::vector<HpColGt> gcols;
+        if (site_gt) {
+            gcols.assign(S + 1, HpColGt{0, 0, 0, 0, 0, 0});
+            for (int32_t s = 0; s < S; s++) gcols[s] = HpColGt{cols[s].act, cols[s].keep, cols[s].m0, cols[s].m1, site_gt[s], 0};
+            NC_TRY(sc.get(ctx, &d_gcols, S + 1));
+            NC_TRY(sc.get(ctx, &d_colg, S + 1));
+        } else {
+            NC_TRY(sc.get(ctx, &d_cols, S + 1));
+        }
         NC_TRY(sc.get(ctx, &d_bf, nblk));
         NC_TRY(sc.get(ctx, &d_bl, nblk));
         NC_TRY(sc.get(ctx, &d_ovf, 1));
@@ -501,21 +547,31 @@ int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
         NC_TRY(sc.get(ctx, &d_bt, bt_total + 1));
         NC_TRY(sc.get(ctx, &d_colB, S + 1));
         NC_TRY(sc.get(ctx, &d_colh, S + 1));
-        NC_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (S + 1) * sizeof(HpCol), hipMemcpyHostToDevice, ctx->stream));
+        if (site_gt) NC_HIP(ctx, hipMemcpyAsync(d_gcols, gcols.data(), (S + 1) * sizeof(HpColGt), hipMemcpyHostToDevice, ctx->stream));
+        else NC_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (S + 1) * sizeof(HpCol), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bf, ph->block_first.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bl, ph->block_last.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bto, bt_off.data(), (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemsetAsync(d_ovf, 0, sizeof(int32_t), ctx->stream));
-        k_hp_dp<<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf);
+        if (site_gt)
+            k_hp_dp<true><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_gcols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_colg, (uint32_t)gt_cost);
+        else
+            k_hp_dp<false><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, nullptr, 0);
         NC_HIP(ctx, hipGetLastError());
         NC_HIP(ctx, hipMemcpyAsync(colB.data(), d_colB, (S + 1) * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(colh.data(), d_colh, S + 1, hipMemcpyDeviceToHost, ctx->stream));
+        if (site_gt) NC_HIP(ctx, hipMemcpyAsync(colg.data(), d_colg, S + 1, hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(ph->block_cost.data(), d_cost, nblk * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(&overflow, d_ovf, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (overflow) return nc_fail(ctx, NC_ERR_CAPACITY, "nc_snp_phase_solve: a partition cost exceeds 65535 above its column's minimum");
     for (int32_t s = 0; s < S; s++) ph->site_h[s] = ph->site_block[s] >= 0 ? colh[s] : 0;
+    if (site_gt)                                                        // a site is phased when it has an accepted allele and comes out het
+        for (int32_t s = 0; s < S; s++) {
+            if (ph->site_block[s] >= 0) ph->site_gt[s] = colg[s];
+            if (ph->site_gt[s] != 0) ph->site_phased[s] = 0;
+        }
     for (int32_t bi = 0; bi < nblk; bi++) {
         int32_t ps = 0;
         for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi] && !ps; c++)
@@ -529,6 +585,22 @@ int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
     ph->ms[2] = (float)(hp_now_ms() - t1);
     ph->solved = true;
     return NC_OK;
+}
+
+int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
+{
+    if (!ctx || !ph || max_cov < 1 || max_cov > HP_SLOTS) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_solve: max_cov must lie in [1, %d]", HP_SLOTS);
+    return hp_solve(ctx, ph, max_cov, nullptr, 0);
+}
+
+int nc_snp_phase_solve_gt(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost)
+{
+    if (!ctx || !ph || max_cov < 1 || max_cov > HP_SLOTS) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_solve_gt: max_cov must lie in [1, %d]", HP_SLOTS);
+    if ((ph->n_sites && !site_gt) || gt_cost < 1 || gt_cost > HP_GT_COST_MAX)
+        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_solve_gt: site_gt missing or gt_cost outside [1, %d]", HP_GT_COST_MAX);
+    for (int32_t s = 0; s < ph->n_sites; s++)
+        if (site_gt[s] > 2) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_solve_gt: site %d: class %d is not 0 (het), 1 or 2 (homozygous)", s, site_gt[s]);
+    return hp_solve(ctx, ph, max_cov, site_gt, gt_cost);
 }
 
 int nc_haplotag_run(nc_ctx *ctx, nc_phase *ph, int32_t n_groups, const int32_t *read_group)
@@ -608,6 +680,13 @@ int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out)
     out->group_hp = ph->group_hp.data();
     out->group_ps = ph->group_ps.data();
     for (int k = 0; k < 4; k++) out->ms[k] = ph->ms[k];
+    return NC_OK;
+}
+
+int nc_snp_phase_genotypes(const nc_phase *ph, const uint8_t **site_gt)
+{
+    if (!ph || !site_gt) return NC_ERR_ARG;
+    *site_gt = ph->solved && !ph->site_gt.empty() ? ph->site_gt.data() : nullptr;
     return NC_OK;
 }
 

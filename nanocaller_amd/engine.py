@@ -380,13 +380,16 @@ class Engine:
         self._check(self.L.nc_indel_forward(self.ctx, kind, n, _ptr(x), _ptr(probs)), "nc_indel_forward")
         return probs
 
-    def snp_phase(self, site_pos, site_alleles, read_group, n_groups, *, max_cov=15, reads=None, csr=None, realign=None) -> dict:
+    def snp_phase(self, site_pos, site_alleles, read_group, n_groups, *, max_cov=15, reads=None, csr=None, realign=None, site_gt=None,
+                  distrust_cost=1) -> dict:
         """Read-based phasing + haplotags (nc_snp_phase_*, nc_haplotag_run) -> dict of host arrays (see nc_phase_arrays).
         reads: (codes, rd_start, rd_end, slot_off) device tensors of a resident pack's kept reads (alleles gathered on the device);
         csr: (entry_off int64, entry_site int32, entry_allele uint8) host arrays instead;
         realign: (codes, IndelReadsC, n_events, n_ins_bases, ref_code) -- the pack's codes, its read table with the events and the inserted
         bases, and the contig's reference codes [length] (device uint8, position p at p - 1, 4 = not a base): alleles by local
-        realignment (nc_snp_phase_realign)."""
+        realignment (nc_snp_phase_realign).
+        site_gt: the called class per site (uint8: 0 het, 1 / 2 homozygous for the first / second allele) -- the genotypes are not trusted
+        (nc_snp_phase_solve_gt with the price `distrust_cost` of leaving a call) and the result gains `site_gt`, the outcome per site."""
         L = self.L
         pos = np.ascontiguousarray(site_pos, np.int32)
         h = C.c_void_p()
@@ -409,7 +412,13 @@ class Engine:
             self._check(L.nc_snp_phase_load(self.ctx, off.size - 1, pos.size, _lib.npp(pos), _lib.npp(off), _lib.npp(site), _lib.npp(allele),
                                             C.byref(h)), "nc_snp_phase_load")
         try:
-            self._check(L.nc_snp_phase_solve(self.ctx, h, int(max_cov)), "nc_snp_phase_solve")
+            if site_gt is None:
+                self._check(L.nc_snp_phase_solve(self.ctx, h, int(max_cov)), "nc_snp_phase_solve")
+            else:
+                gt = np.ascontiguousarray(site_gt, np.uint8)
+                if gt.shape != pos.shape:
+                    raise ValueError("snp_phase: site_gt holds %d classes for %d sites" % (gt.size, pos.size))
+                self._check(L.nc_snp_phase_solve_gt(self.ctx, h, int(max_cov), _lib.npp(gt), int(distrust_cost)), "nc_snp_phase_solve_gt")
             grp = np.ascontiguousarray(read_group, np.int32)
             self._check(L.nc_haplotag_run(self.ctx, h, int(n_groups), _lib.npp(grp)), "nc_haplotag_run")
             v = _lib.PhaseArraysC()
@@ -418,12 +427,17 @@ class Engine:
             def a(ptr, n, dt):
                 return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), (n,)).copy() if n and ptr else np.zeros(0, dt)
             R, S, nb, ng = v.n_reads, v.n_sites, v.n_blocks, v.n_groups
+            extra = {}
+            if site_gt is not None:
+                g = C.c_void_p()
+                L.nc_snp_phase_genotypes(h, C.byref(g))
+                extra = dict(site_gt=a(g, S, np.uint8))
             return dict(entry_off=a(v.entry_off, R + 1, np.int64), entry_site=a(v.entry_site, v.n_entries, np.int32),
                         entry_allele=a(v.entry_allele, v.n_entries, np.uint8), side=a(v.read_side, R, np.int8),
                         site_block=a(v.site_block, S, np.int32), site_h=a(v.site_h, S, np.uint8), site_phased=a(v.site_phased, S, np.uint8).astype(bool),
                         site_ps=a(v.site_ps, S, np.int32), block_first=a(v.block_first, nb, np.int32), block_last=a(v.block_last, nb, np.int32),
                         block_ps=a(v.block_ps, nb, np.int32), block_cost=a(v.block_cost, nb, np.int64), group_hp=a(v.group_hp, ng, np.uint8),
-                        group_ps=a(v.group_ps, ng, np.int32), ms=dict(zip(("gather", "select", "dp", "haplotag"), list(v.ms))))
+                        group_ps=a(v.group_ps, ng, np.int32), ms=dict(zip(("gather", "select", "dp", "haplotag"), list(v.ms))), **extra)
         finally:
             L.nc_snp_phase_free(h)
 

@@ -295,7 +295,9 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
     With the built-in phaser selected (params['phaser'] = 'device', or NC_PHASER=device without that key; phase.py) the confident
     SNPs are phased on `device` from the contig's resident reads, the haplotags go to <contig>.haplotags.npz and the contig's
     indel chunks carry chunk['haplotags'] = that file beside chunk['sam_path'] = params['sam_path'].  params['phase_realign'] (or
-    NC_PHASE_REALIGN=1 without that key) makes that phaser detect the reads' alleles by local realignment (phase.phase_contig(realign=True))."""
+    NC_PHASE_REALIGN=1 without that key) makes that phaser detect the reads' alleles by local realignment (phase.phase_contig(realign=True));
+    params['phase_distrust'] (or NC_PHASE_DISTRUST=1 without that key) lets it change genotypes and take homozygous calls, as `whatshap phase
+    --distrust-genotypes --include-homozygous` does (phase.phase_contig(distrust=True)), and the records that come out 0/0 are dropped."""
     import os
 
     from . import vcfio
@@ -320,10 +322,12 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
         phased = False
         haplotags = None
         if device_phaser_selected(params):
-            from .phase import phase_contig, phase_realign_selected, save_haplotags
+            from .phase import phase_contig, phase_distrust_selected, phase_realign_selected, save_haplotags
             realign = dict(realign=True) if phase_realign_selected(params) else {}      # (off: the call as it always was)
-            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device, **realign)
-            vcfio.write_sorted_vcf(out_vcf, _with_phase_format(header), res.records, [contig])
+            distrust = dict(distrust=True) if phase_distrust_selected(params) else {}
+            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device, **realign, **distrust)
+            kept = without_hom_ref(res.records) if distrust else res.records    # -e 'GT="0\\0"' (:239), as on the WhatsHap branch
+            vcfio.write_sorted_vcf(out_vcf, _with_phase_format(header), kept, [contig])
             haplotags = os.path.join(phase_dir, '%s.haplotags.npz' % contig)
             save_haplotags(haplotags, res.haplotags)
             phased = True
@@ -364,6 +368,11 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
                 chunk['haplotags'] = haplotags
             job_Q.put(('indel', chunk))
         indel_dict.pop(contig, None)
+
+
+def without_hom_ref(records):
+    """the records whose GT is not 0/0 or 0|0: what `bcftools view -e 'GT="0\\0"'` keeps of a phaser's output that may change genotypes"""
+    return [ln for ln in records if ln.rstrip('\n').split('\t')[9].split(':')[0] not in ('0/0', '0|0')]
 
 
 PS_FORMAT_LINE = '##FORMAT=<ID=PS,Number=1,Type=Integer,Description="Phase set identifier">\n'

@@ -7,7 +7,9 @@ decoded twice) and returns the phased records, the blocks and a haplotag table: 
 the device ingest's record meta carries), HP and PS.  The indel pass takes HP / PS from such a table instead of the BAM's own tags
 when a chunk carries `haplotags` (`TaggedBam`).  Opt-in: params['phaser'] = 'device', or NC_PHASER=device when params has no
 'phaser' key (`device_phaser_selected`).  Behind it, params['phase_realign'] / NC_PHASE_REALIGN=1 (`phase_realign_selected`) selects the
-alleles by local realignment (WhatsHap's `--reference` mode restated) instead of the pileup column's code.
+alleles by local realignment (WhatsHap's `--reference` mode restated) instead of the pileup column's code; params['phase_distrust'] /
+NC_PHASE_DISTRUST=1 (`phase_distrust_selected`) lets the phaser change genotypes and take homozygous calls (WhatsHap's `--distrust-genotypes
+--include-homozygous` restated: `phase_contig(distrust=True)`).
 """
 from __future__ import annotations
 
@@ -46,6 +48,14 @@ def phase_realign_selected(params) -> bool:
     return os.environ.get("NC_PHASE_REALIGN") == "1"
 
 
+def phase_distrust_selected(params) -> bool:
+    """params['phase_distrust'] truthy; without that key, the environment's NC_PHASE_DISTRUST == '1' (the device phaser may leave a site's called
+    genotype at a price and takes the homozygous-ALT calls too: `phase_contig(distrust=True)`)"""
+    if "phase_distrust" in params:
+        return bool(params["phase_distrust"])
+    return os.environ.get("NC_PHASE_DISTRUST") == "1"
+
+
 def name_hash(names) -> np.ndarray:
     """FNV-1a (64 bit) of every read name with its terminating NUL: the hash of the BAM record's read_name field, as the device
     ingest computes it (nc_ingest.hip, meta rows M_HASH_LO / M_HASH_HI)"""
@@ -73,13 +83,12 @@ class PhaseResult:
     records: list                      # VCF record lines, phased ones rewritten (GT with '|', FORMAT + ':PS')
     blocks: list                       # (first site position, last site position, PS, MEC cost) per block
     haplotags: dict                    # hash uint64 [n] ascending, hp uint8 [n], ps int32 [n]: tagged read names only
-    sites: dict = field(default_factory=dict)    # pos, record index, h, phased, ps per het site
+    sites: dict = field(default_factory=dict)    # pos, record index, h, phased, ps, called class gt_in and outcome gt_out per site
     reads: dict = field(default_factory=dict)    # kept reads: index into the World, name hash, group, side, hp, ps
     ms: dict = field(default_factory=dict)
 
 
-def het_sites(snp_records, phase_qual_score):
-    """the records the phaser takes: QUAL >= phase_qual_score, GT 0/1 or 1/2, single-base alleles -> (record index, pos, alleles [n, 2], kind)"""
+def _sites(snp_records, phase_qual_score, homozygous):
     q = float(phase_qual_score)
     idx, pos, al, kind = [], [], [], []
     last = 0
@@ -93,6 +102,8 @@ def het_sites(snp_records, phase_qual_score):
             a = (f[3], alts[0])
         elif gt == "1/2" and len(alts) == 2:
             a = (alts[0], alts[1])
+        elif homozygous and gt == "1/1" and len(alts) == 1:
+            a = (f[3], alts[0])
         else:
             continue
         if a[0] not in _CODE or a[1] not in _CODE or int(f[1]) <= last:
@@ -105,6 +116,18 @@ def het_sites(snp_records, phase_qual_score):
     return (np.array(idx, np.int64), np.array(pos, np.int32), np.array(al, np.uint8).reshape(-1, 2), kind)
 
 
+def het_sites(snp_records, phase_qual_score):
+    """the records the phaser takes: QUAL >= phase_qual_score, GT 0/1 or 1/2, single-base alleles -> (record index, pos, alleles [n, 2], kind)"""
+    return _sites(snp_records, phase_qual_score, False)
+
+
+def distrust_sites(snp_records, phase_qual_score):
+    """the records the phaser takes when it distrusts genotypes: het_sites' and GT 1/1 with one single-base ALT (alleles REF, ALT)
+    -> (record index, pos, alleles [n, 2], kind, gt uint8 [n]: the called class, 0 het, 2 homozygous for the second allele)"""
+    idx, pos, al, kind = _sites(snp_records, phase_qual_score, True)
+    return idx, pos, al, kind, np.array([2 if k == "1/1" else 0 for k in kind], np.uint8)
+
+
 def phased_record(line, h, ps):
     """one record with its GT phased (0/1 -> 0|1 when h = 0, 1|0 when h = 1; 1/2 -> 1|2 / 2|1) and PS appended"""
     f = line.rstrip("\n").split("\t")
@@ -113,6 +136,23 @@ def phased_record(line, h, ps):
     smp[0] = ("%s|%s" % (a, b)) if h == 0 else ("%s|%s" % (b, a))
     f[8] += ":PS"
     f[9] = ":".join(smp) + ":%d" % ps
+    return "\t".join(f) + "\n"
+
+
+def distrust_record(line, kind, outcome, h, phased, ps):
+    """one record of a site of `distrust_sites` with the phaser's outcome written into its GT.  kind: the called GT; outcome 0 het (phased: GT
+    with '|' by h and PS appended, a called 1/1 as 0|1 / 1|0), 1 / 2 homozygous for the site's first / second allele (0/1 -> 0/0 / 1/1,
+    1/2 -> 1/1 / 2/2, 1/1 -> 0/0 / 1/1).  Every other byte of the record stays."""
+    a, b = ("1", "2") if kind == "1/2" else ("0", "1")
+    if outcome == 0 and phased:
+        return phased_record(line if kind != "1/1" else _with_gt(line, "0/1"), h, ps)
+    gt = "%s/%s" % ((a, b) if outcome == 0 else (a, a) if outcome == 1 else (b, b))
+    return line if gt == kind else _with_gt(line, gt)
+
+
+def _with_gt(line, gt):
+    f = line.rstrip("\n").split("\t")
+    f[9] = ":".join([gt] + f[9].split(":")[1:])
     return "\t".join(f) + "\n"
 
 
@@ -162,18 +202,26 @@ def _realign_inputs(sam_path, fasta_path, chrom, supplementary, device):
     return dp, (dp.codes, reads_c, dp.events["ev_pos"].numel(), ix["ins_bases"].numel(), ctg[key])
 
 
-def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, supplementary=False, max_cov=15, device=0, realign=False) -> PhaseResult:
+def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, supplementary=False, max_cov=15, device=0, realign=False, distrust=False,
+                 distrust_cost=1) -> PhaseResult:
     """Phase the het SNP calls `snp_records` (VCF lines of contig `chrom`) from the reads of `sam_path` (a BAM path, a World or a
     registered key) and haplotag the reads.  -> PhaseResult
     realign: a read's allele at a site comes from a local realignment of its bases against the reference window with either allele (DESIGN.md
-    "Read-based phasing", the allele detectors) instead of the code in the site's column; needs a BAM file (the reads' inserted bases)."""
+    "Read-based phasing", the allele detectors) instead of the code in the site's column; needs a BAM file (the reads' inserted bases).
+    distrust: the genotypes are not trusted (DESIGN.md "Read-based phasing", step 6b): the sites are `distrust_sites`', a site may come out het or
+    homozygous for either allele, leaving its call costs `distrust_cost` allele errors, and the records' GT follow the outcome."""
     import torch
 
     from .engine import get_engine
     from .generate_SNP_pileups import _resolve, device_pack
     eng = get_engine(device)
     eng.use_torch_stream()
-    rec_idx, pos, alleles, _ = het_sites(snp_records, phase_qual_score)
+    if distrust:
+        rec_idx, pos, alleles, kind, gt_in = distrust_sites(snp_records, phase_qual_score)
+        solve = dict(site_gt=gt_in, distrust_cost=distrust_cost)
+    else:
+        rec_idx, pos, alleles, kind = het_sites(snp_records, phase_qual_score)
+        gt_in, solve = np.zeros(pos.size, np.uint8), {}
     ra = None
     if realign:
         dp, ra = _realign_inputs(sam_path, fasta_path, chrom, supplementary, device)
@@ -201,18 +249,23 @@ def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, sup
     if realign:
         if dp.reads is None or ra[1].n_reads != kept.size:
             raise RuntimeError("phase_contig: the indel read table holds %d reads, the flag filter keeps %d" % (ra[1].n_reads, kept.size))
-        r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, realign=ra)
+        r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, realign=ra, **solve)
     else:
-        r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, reads=reads)
+        r = eng.snp_phase(pos, alleles, group.astype(np.int32), len(uniq), max_cov=max_cov, reads=reads, **solve)
     out = list(snp_records)
-    for k in np.flatnonzero(r["site_phased"]).tolist():
-        out[int(rec_idx[k])] = phased_record(snp_records[int(rec_idx[k])], int(r["site_h"][k]), int(r["site_ps"][k]))
+    gt_out = r["site_gt"] if distrust else gt_in
+    if distrust:
+        for k, i in enumerate(rec_idx.tolist()):
+            out[i] = distrust_record(snp_records[i], kind[k], int(gt_out[k]), int(r["site_h"][k]), bool(r["site_phased"][k]), int(r["site_ps"][k]))
+    else:
+        for k in np.flatnonzero(r["site_phased"]).tolist():
+            out[int(rec_idx[k])] = phased_record(snp_records[int(rec_idx[k])], int(r["site_h"][k]), int(r["site_ps"][k]))
     blocks = [(int(pos[f]), int(pos[l_]), int(ps), int(c)) for f, l_, ps, c in zip(r["block_first"], r["block_last"], r["block_ps"], r["block_cost"])]
     tagged = r["group_hp"] != 0
     tags = dict(hash=np.ascontiguousarray(uniq[tagged] if names is not None else np.zeros(0, np.uint64)),
                 hp=np.ascontiguousarray(r["group_hp"][tagged] if names is not None else np.zeros(0, np.uint8)),
                 ps=np.ascontiguousarray(r["group_ps"][tagged] if names is not None else np.zeros(0, np.int32)))
-    sites = dict(pos=pos, record=rec_idx, h=r["site_h"], phased=r["site_phased"], ps=r["site_ps"], block=r["site_block"])
+    sites = dict(pos=pos, record=rec_idx, h=r["site_h"], phased=r["site_phased"], ps=r["site_ps"], block=r["site_block"], gt_in=gt_in, gt_out=gt_out)
     reads_out = dict(index=kept, hash=hashes, group=group, side=r["side"], hp=r["group_hp"][group], ps=r["group_ps"][group],
                      entry_off=r["entry_off"], entry_site=r["entry_site"], entry_allele=r["entry_allele"])
     return PhaseResult(records=out, blocks=blocks, haplotags=tags, sites=sites, reads=reads_out, ms=r["ms"])

@@ -1,7 +1,9 @@
 """Wall time of the read-based phaser on a chr20-sized synthetic ONT contig (64.4 Mb, 30x, generated in HBM by nc_synth_indel_*):
 allele gather, read selection + blocks + slots (host), the MEC DP, haplotagging.  The het sites are the generator's own (its truth,
 recomputed from the same seed); every read is its own name.  --realign: the alleles by local realignment (nc_snp_phase_realign) instead of
-the column gather.  Prints one JSON line.  Usage: python tools/bench_phase.py [--length L] [--reps N] [--realign | --compare N]"""
+the column gather.  --distrust N: the genotype-aware DP (nc_snp_phase_solve_gt) against the plain one on the same het-only site list, and on the
+list with the homozygous SNP sites added as 1/1 calls.  Prints one JSON line.
+Usage: python tools/bench_phase.py [--length L] [--reps N] [--realign | --compare N | --distrust N] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -25,6 +27,10 @@ def main():
     ap.add_argument("--seed", type=int, default=812)
     ap.add_argument("--realign", action="store_true")
     ap.add_argument("--compare", type=int, default=0, help="N interleaved runs of the column gather and of the realignment, medians and their ratio")
+    ap.add_argument("--distrust", type=int, default=0, help="N interleaved runs of the plain solve, the genotype-aware solve on the same het-only sites, "
+                    "and the genotype-aware solve with the homozygous sites added: medians, and the DP's ratio to the plain form")
+    ap.add_argument("--distrust-cost", type=int, default=1)
+    ap.add_argument("--out", default=None, help="with --distrust: also write the JSON to this file")
     a = ap.parse_args()
     eng = get_engine(0)
     eng.use_torch_stream()
@@ -48,6 +54,45 @@ def main():
     kw = dict(reads=reads)
     if a.realign:                                                       # reference codes with position p at index p - 1
         kw = dict(realign=(pack.codes, reads_c, info["n_events"], info["n_ins_bases"], ref[1:].contiguous()))
+    if a.distrust:
+        # the same gather, three solves: plain / genotype-aware on the het sites (every class 0), genotype-aware with the truth's homozygous SNP
+        # sites added as 1/1 calls (alleles REF, ALT; class 2).  The plain form is the yardstick.
+        hom = np.flatnonzero((hb[0] == hb[1]) & (hb[0] != r) & (r < 4) & (hb[0] < 4))
+        hom = hom[hom >= 1].astype(np.int32)
+        both = np.concatenate([het, hom])
+        o = np.argsort(both, kind="stable")
+        pos2 = both[o]
+        al2 = np.concatenate([alleles, np.stack([r[hom], hb[0][hom]], 1).astype(np.uint8)])[o]
+        gt2 = np.concatenate([np.zeros(het.size, np.uint8), np.full(hom.size, 2, np.uint8)])[o]
+        forms = dict(plain=(het, alleles, {}), distrust=(het, alleles, dict(site_gt=np.zeros(het.size, np.uint8), distrust_cost=a.distrust_cost)),
+                     distrust_with_hom=(pos2, al2, dict(site_gt=gt2, distrust_cost=a.distrust_cost)))
+        eng.snp_phase(het, alleles, group, R, reads=reads)
+        walls, stages, last = {k: [] for k in forms}, {k: [] for k in forms}, {}
+        for _ in range(a.distrust):
+            for k, (p_, al_, kw_) in forms.items():
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                last[k] = eng.snp_phase(p_, al_, group, R, reads=reads, **kw_)
+                walls[k].append(time.perf_counter() - t)
+                stages[k].append(last[k]["ms"])
+        med = lambda v: float(np.median(v))                              # noqa: E731
+        dp = {k: med([m["dp"] for m in stages[k]]) for k in forms}
+        out = dict(metric="phase_chr20_sized_distrust_dp_over_plain", value=round(dp["distrust"] / dp["plain"], 4),
+                   with_hom_dp_over_plain=round(dp["distrust_with_hom"] / dp["plain"], 4), length=L, depth=a.depth, reads=R, het_sites=int(het.size),
+                   hom_sites=int(hom.size), distrust_cost=a.distrust_cost, runs=a.distrust)
+        for k in forms:
+            res = last[k]
+            out[k] = dict(wall_s=round(med(walls[k]), 4), walls_s=[round(x, 4) for x in walls[k]], sites=int(forms[k][0].size),
+                          entries=int(res["entry_site"].size), phased_sites=int(res["site_phased"].sum()), blocks=int(res["block_first"].size),
+                          mec_cost=int(res["block_cost"].sum()), tagged_reads=int((res["group_hp"] > 0).sum()),
+                          stage_ms={s_: round(med([m[s_] for m in stages[k]]), 3) for s_ in stages[k][0]})
+            if "site_gt" in res:
+                out[k]["outcomes_left_call"] = int((res["site_gt"] != forms[k][2]["site_gt"]).sum())
+        print(json.dumps(out))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.compare:
         # both allele detectors on the same contig, interleaved, median of `compare` runs each (the column gather is the yardstick)
         kws = dict(column=dict(reads=reads), realign=dict(realign=(pack.codes, reads_c, info["n_events"], info["n_ins_bases"], ref[1:].contiguous())))
