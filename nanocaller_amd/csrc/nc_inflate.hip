@@ -41,7 +41,8 @@ struct InflateArgs {
     const int32_t *isize;       // the length its trailer announces
     int32_t n;
     int32_t *status;            // 0 ok; 1 bad block type / stored length; 2 bad code lengths; 3 bad symbol / distance; 4 output overrun; 5 input
-                                // overrun; 6 length differs from ISIZE; 7 (nc_bgzf_crc_device) CRC-32 differs from the trailer's
+                                // overrun (bits behind the payload's end were consumed: that outranks whatever they decoded to); 6 length
+                                // differs from ISIZE; 7 (nc_bgzf_crc_device) CRC-32 differs from the trailer's
 };
 
 struct __attribute__((packed, aligned(4))) U4w { uint32_t x, y, z, w; };   // four dwords at a 4-byte aligned address
@@ -398,6 +399,10 @@ __global__ __launch_bounds__(LPW) void k_huff(InflateArgs a, uint32_t *tok, int3
         if (err || last) fin = true;
     }
     if (live) {
+        // bits taken from behind the payload's end (32 rd - 8 skew loaded, bc of them still in the buffer): the stream is cut short, and whatever
+        // was decoded from the bytes that follow it -- the next member's, or the zeros past w_end -- says nothing, be it an error of another kind
+        // or none.  (refill's own check only ends a loop that would run on: it fires two dwords late, the bit buffer's depth)
+        if (32 * rd - 8 * skew - bc > 8 * clen) err = 5;
         if (!err && op != isize) err = 6;
         ntok[b] = nt;
         a.status[b] = err;

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import bamio
+from test_inflate_device import _run as _inflate_device
 
 OPS = "MIDNSHP=X"
 
@@ -253,6 +254,11 @@ def test_deflate_member_classes(eng):
             assert zlib.decompress(p, -15) == m, name
             assert int(c) == zlib.crc32(m), name
             assert len(p) <= len(m) + 5
+        out, ooff, st = _inflate_device(pays, [len(m) for m in members])     # the writer's blocks through the reader's tables: both ours
+        assert not st.any(), name
+        for k, m in enumerate(members):
+            assert out[ooff[k]:ooff[k] + len(m)].tobytes() == m, name
+            assert out[ooff[k] + len(m):ooff[k] + len(m) + 3].tolist() == [0xEE] * 3, name
         ratio[name] = sum(map(len, pays)) / max(1, sum(_zlib1(m) for m in members))
     print("payload / zlib level 1:", {k: round(v, 3) for k, v in ratio.items()})
     pays, _ = _deflate(eng, classes["rand"])

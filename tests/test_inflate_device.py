@@ -1,10 +1,14 @@
 """DEFLATE on the device (csrc/nc_inflate.hip, one lane per BGZF member) against zlib: every block type and the streams zlib's strategies make,
-members at unaligned offsets, the members of the spec-assembled BAM fixture, and damaged inputs (reported, never a crash)."""
+members at unaligned offsets, the members of the spec-assembled BAM fixture, damaged inputs (reported, never a crash) -- and the legal streams
+zlib's compressor never writes, with the illegal ones next to them, from the bit-level writer of tests/deflate_craft.py (each proven on zlib's
+decompressor by tests/test_deflate_craft_ref.py)."""
 import os
 import zlib
 
 import numpy as np
 import pytest
+
+import deflate_craft as C
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -15,7 +19,7 @@ def _deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, mem=8):
     return c.compress(data) + c.flush()
 
 
-def _run(payloads, sizes):
+def _run(payloads, sizes, phases=(3,)):
     import torch
     from nanocaller_amd.engine import get_engine
     eng = get_engine(0)
@@ -39,9 +43,11 @@ def _run(payloads, sizes):
     d_tok = torch.empty(((len(payloads) + 63) // 64) << 22, dtype=torch.int32, device=dev)
     d_ntok = torch.zeros(len(payloads), dtype=torch.int32, device=dev)
     eng.use_torch_stream()
-    rc = eng.L.nc_inflate_device(eng.ctx, len(payloads), d_comp.data_ptr(), d_coff.data_ptr(), d_clen.data_ptr(), d_out.data_ptr(), d_ooff.data_ptr(),
-                                 d_isize.data_ptr(), d_st.data_ptr(), d_tok.data_ptr(), d_ntok.data_ptr())
-    assert rc == 0
+    args = (len(payloads), d_comp.data_ptr(), d_coff.data_ptr(), d_clen.data_ptr(), d_out.data_ptr(), d_ooff.data_ptr(), d_isize.data_ptr(), d_st.data_ptr(),
+            d_tok.data_ptr(), d_ntok.data_ptr())
+    for ph in phases:                                                                              # (3: the one call; 1 then 2: the two launches apart, as device_bam.py makes them)
+        rc = eng.L.nc_inflate_device(eng.ctx, *args) if ph == 3 else eng.L.nc_inflate_device_phase(eng.ctx, ph, *args)
+        assert rc == 0
     torch.cuda.synchronize()
     return d_out.cpu().numpy(), ooff, d_st.cpu().numpy()
 
@@ -185,3 +191,60 @@ def test_device_crc32_equals_zlibs_and_reports_a_damaged_member():
     bad_trailer = [(int(zlib.crc32(d)) ^ 0x00010000).to_bytes(4, "little") + len(d).to_bytes(4, "little") for d in datas]
     st = _crc_status(pay, datas, bad_trailer)
     assert (st == 7).all()
+
+
+PHASES = pytest.mark.parametrize("phases", [(3,), (1, 2)], ids=["one_call", "huffman_then_matches"])
+
+
+@PHASES
+@pytest.mark.parametrize("launch", list(C.N_LEGAL))
+def test_crafted_legal_streams_inflate_to_their_tokens(launch, phases):
+    """The legal DEFLATE zlib's compressor does not write, one launch per group of tests/deflate_craft.py (what each stream holds is asserted on the
+    CPU by tests/test_deflate_craft_ref.py): status 0, the bytes of `expand`, the three guard bytes behind every output intact -- through
+    nc_inflate_device and through nc_inflate_device_phase(1) then (2), the production route's two launches.
+      deep_codes              15-bit codes in both alphabets behind the 8- / 5-bit first-level tables (slow_from, walk_start, the ninth-bit mask hi[])
+      worst_rate_*            124 matches of 48 bits back to back: the per-lane stream window (tick / refill) at its least slack; alone in its
+                              workgroup, and as one of 16 lanes of which 15 finish at once
+      two_literals            the second literal of a step (`two`): op + 2 == isize, an odd size, a successor that is the end of block, a length
+                              symbol, or a literal the table misses -- dynamic and fixed
+      headers                 nlen 257 / 286, ndist 1 (length 0, and length 1 for each of the 30 symbols) / 30, 5 / 8 / 19 code length code lengths (4 cannot
+                              be legal: no length could be non-zero; it is among the illegal streams), 16 x 6 / 17 x 10 / 18 x 138, a 16-run from
+                              the literal into the distance lengths, zeros over 257-285, a second block with fewer lengths than the first (the nibbles)
+      lengths_distances       every length at distance 1 and beyond 258, 258 as 284 + 31, every distance symbol's edges, distance == op around
+                              k_lz's ring and flush sizes (distance 32,768 read back from HBM at its first byte), matches chained inside a step
+      stored                  take(bc & 7) at every bit offset, LEN 0 / 1 / 65,535, 65,536 tokens from two stored blocks, all three types in one member
+      sizes                   65,535 / 65,536 bytes as literals, as matches, and as that many single-literal tokens (9-bit literals never pair): the
+                              token workspace's capacity; literal / 3-byte match alternating
+      random_codes            256 members of seeded random complete codes (depth <= 15) and random tokens, half with run-length coded lengths
+      map_300 / _129 / _17    k_lz's block -> member permutation beyond 128 members and off its 16 / 128 boundaries: distinct contents everywhere
+    Not among them, on purpose: an INCOMPLETE literal / length or distance set of several symbols whose unused codes never occur.  The kernel
+    accepts it (huff_build's comment), zlib refuses it; neither list has such a stream."""
+    cases = C.legal_launches()[launch]
+    assert len(cases) == C.N_LEGAL[launch]
+    out, ooff, st = _run([c.z for c in cases], [len(c.want) for c in cases], phases)
+    assert st.tolist() == [0] * len(cases), [(c.name, int(s)) for c, s in zip(cases, st) if s][:10]
+    for k, c in enumerate(cases):
+        n = len(c.want)
+        assert out[ooff[k]:ooff[k] + n].tobytes() == c.want, c.name
+        assert out[ooff[k] + n:ooff[k] + n + 3].tolist() == [0xEE] * 3, c.name
+
+
+@PHASES
+def test_crafted_illegal_streams_get_their_documented_status(phases):
+    """every stream zlib refuses (and the sound ones of another length than announced) ends in the status InflateArgs documents for it -- exactly
+    --, writes nothing past its announced size, and the good members before and behind it come out right.  Status 5 is every member whose
+    decoding consumed bits behind its payload's end, whatever those bits were (here: a few random bytes and the next member)."""
+    ill = C.illegal_cases()
+    assert len(ill) == C.N_ILLEGAL
+    good = [C.small_member(3000 + i) for i in range(len(ill) + 1)]
+    pay, sizes = [good[0].z], [len(good[0].want)]
+    for (_, z, n, _), g in zip(ill, good[1:]):
+        pay += [z, g.z]
+        sizes += [n, len(g.want)]
+    out, ooff, st = _run(pay, sizes, phases)
+    got = {name: int(st[2 * k + 1]) for k, (name, _, _, _) in enumerate(ill)}
+    assert got == {name: want for name, _, _, want in ill}
+    for k, g in enumerate(good):
+        assert st[2 * k] == 0 and out[ooff[2 * k]:ooff[2 * k] + len(g.want)].tobytes() == g.want, k
+    for k, n in enumerate(sizes):
+        assert out[ooff[k] + n:ooff[k] + n + 3].tolist() == [0xEE] * 3, k
