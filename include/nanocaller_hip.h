@@ -905,6 +905,23 @@ int nc_snp_phase_free(nc_phase *ph);
 int nc_snp_phase_solve_gt(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost);
 int nc_snp_phase_genotypes(const nc_phase *ph, const uint8_t **site_gt);
 
+/* The reference FASTA on the device (csrc/nc_fasta.hip): one contig of a FASTA file image in HBM -- the file as it stands, or a bgzipped file's
+ * members inflated by nc_inflate_device -- to the forms the callers read.  d_raw[0, raw_len) = the image, `first` = offset of the contig's
+ * first base in it, length / linebases / linewidth = its .fai columns: position p (1-based) is the byte at
+ * first + ((p - 1) / linebases) * linewidth + (p - 1) % linebases.  Outputs (dev, 16-byte aligned, each may be NULL):
+ *   d_letters [length]  the bytes as they stand, case preserved (what pysam.FastaFile.fetch returns);
+ *   d_scan [scan_len]   entry p - scan_pos0 = A0 G1 T2 C3 for an UPPER-case letter at a position p in [ga, gb], 4 everywhere else (soft-masked
+ *                       bases are not scanned, generate_SNP_pileups.py:137): the SNP scan's reference codes on its tile grid;
+ *   d_blind [length]    A0 G1 T2 C3 in either case, else 4.
+ * The file is checked against the .fai where it is read: d_status (one int32, written here) gets bit 0 when a terminator slot of a full line that
+ * another line of the contig follows does not hold \n (linewidth - linebases == 1) or \r\n (== 2), bit 1 for a base byte outside 0x21..0x7e,
+ * bit 2 when first + span exceeds raw_len (span = ((length - 1) / linebases) * linewidth + (length - 1) % linebases + 1; refused before the
+ * launch, and guarded in the kernel: no byte outside [0, raw_len) is read).  NC_ERR_ARG then ("the .fai does not describe this file"), also for
+ * linebases < 1 or linewidth - linebases outside {1, 2}.  Runs on the context's stream and returns when the outputs and the status are complete. */
+int nc_fasta_decode(nc_ctx *ctx, const uint8_t *d_raw, int64_t raw_len, int64_t first, int64_t length, int64_t linebases, int64_t linewidth,
+                    uint8_t *d_letters, uint8_t *d_scan, int64_t scan_pos0, int64_t scan_len, int64_t ga, int64_t gb, uint8_t *d_blind,
+                    int32_t *d_status);
+
 #ifdef __cplusplus
 }
 #endif

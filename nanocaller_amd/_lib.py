@@ -47,6 +47,7 @@ EXPORTS = [
     "nc_snp_phase_gather", "nc_snp_phase_load", "nc_snp_phase_solve", "nc_haplotag_run", "nc_snp_phase_view", "nc_snp_phase_free",
     "nc_snp_phase_realign", "nc_snp_phase_solve_gt", "nc_snp_phase_genotypes",
     "nc_bam_retag_sizes", "nc_bam_retag", "nc_bgzf_deflate_device", "nc_bgzf_crc32_device", "nc_bgzf_assemble_device",
+    "nc_fasta_decode",
 ]
 
 
@@ -273,6 +274,7 @@ def lib():
         L.nc_bgzf_deflate_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.nc_bgzf_crc32_device.argtypes = [vp, i32, vp, vp, vp, vp]
         L.nc_bgzf_assemble_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.nc_fasta_decode.argtypes = [vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, i64, vp, vp]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

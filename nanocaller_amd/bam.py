@@ -228,7 +228,10 @@ def read_fasta(path, chrom):
 
 
 def read_fasta_bytes(path, chrom):
-    """read_fasta without the decode: the contig's letters as bytes"""
+    """read_fasta without the decode: the contig's letters as bytes (a path that ends in .gz: a bgzip-compressed FASTA, fasta.py)"""
+    if path.endswith(".gz"):
+        from . import fasta
+        return fasta.read_fasta_bytes(path, chrom)
     fai = path + ".fai"
     if os.path.exists(fai):
         for line in open(fai):

@@ -490,7 +490,8 @@ class DeviceBam:
 
     # ------------------------------------------------------------------ one contig: the host's decisions
     def prepare(self, chrom, ref, supplementary=False, exclude=None, span=None, tile_size=2048, haplotags=None, by_name=False):
-        """host half (numpy + native, no GPU call: may run on a worker thread).  ref: the contig's sequence.  haplotags: path of a haplotag
+        """host half (numpy + native, no GPU call: may run on a worker thread).  ref: the contig's sequence (str / bytes), or a
+        device_fasta.DeviceContig: then no letters are staged and pack() takes the scan's reference codes from it.  haplotags: path of a haplotag
         table (phase.save_haplotags) whose HP / PS replace the records' own tags, by read-name hash.  -> dict for pack()
         by_name (the SNP route): kept alignments that share a read name are not refused but keyed by name as the host route keys them
         (pack.name_groups -> mate_table: bit 3 and the name's strand in the tile entries, `mates` in the result).  When, and only when, name
@@ -548,8 +549,9 @@ class DeviceBam:
                 mates = mate_table(nxt, keep, start, end)
         # tile index + slot layout (nc_pack_plan / nc_pack_fill, index only: what wire.build_wire does)
         L = _lib.lib()
-        ref_bytes = np.frombuffer(ref.encode("ascii") if isinstance(ref, str) else ref, np.uint8)
-        Lref = int(ref_bytes.shape[0])
+        ref_contig = ref if hasattr(ref, "scan_codes") else None        # a device_fasta.DeviceContig: the letters are in HBM already
+        ref_bytes = np.zeros(0, np.uint8) if ref_contig is not None else np.frombuffer(ref.encode("ascii") if isinstance(ref, str) else ref, np.uint8)
+        Lref = int(ref_contig.length) if ref_contig is not None else int(ref_bytes.shape[0])
         pos_lo = 1 if span is None else max(1, int(span[0]))
         pos_hi = max(pos_lo, Lref if span is None else min(Lref, int(span[1])))
         codes_len, n_ent = C.c_int64(), C.c_int64()
@@ -575,13 +577,12 @@ class DeviceBam:
         ncig = mk[M_NCIG].astype(np.int64) | np.where(mk[M_HASSEQ] != 0, 0, 1 << 31)
         # everything the device half uploads, back to back in ONE page-locked buffer (a pageable source makes the copy wait for the GPU to
         # finish what is queued before it -- the previous contig's CNN -- and the launching thread with it)
-        Lref_b = int(ref_bytes.shape[0])
-        ga, gb = max(1, tile_pos0.value), min(Lref_b, tile_pos0.value + n_tiles.value * tile_size - 1)
+        ga, gb = max(1, tile_pos0.value), min(Lref, tile_pos0.value + n_tiles.value * tile_size - 1)
         parts = dict(rec=np.ascontiguousarray(self.rec_off[a + idx[kk]]), slot=slot, cigd=np.ascontiguousarray(mk[M_CIGD]),
                      ncig=ncig.astype(np.uint32).view(np.int32), start=np.ascontiguousarray(ks), rd_end=np.ascontiguousarray(ke),
                      slot_off=np.concatenate([slot, [int(size.sum())]]).astype(np.int64), read_hap=np.ascontiguousarray(hap[kk]),
                      read_ps=np.ascontiguousarray(ps[kk], np.int32), read_flag=np.ascontiguousarray((mk[M_LSEQ] == 0).astype(np.uint8)), tile_off=tile_off,
-                     tile_ent=tile_ent.view(np.uint8).reshape(-1), ref_letters=ref_bytes[ga - 1:gb] if gb >= ga else ref_bytes[:0])
+                     tile_ent=tile_ent.view(np.uint8).reshape(-1), ref_letters=ref_bytes[ga - 1:gb] if gb >= ga and ref_contig is None else ref_bytes[:0])
         if mates is not None:
             parts.update(mate_key=mates[0], mate_rec=np.ascontiguousarray(mates[1]).reshape(-1))
         sections, total_b = {}, 0
@@ -593,7 +594,7 @@ class DeviceBam:
         for k, v in parts.items():
             o = sections[k][0]
             host[o:o + v.nbytes] = v.view(np.uint8).reshape(-1)
-        return dict(chrom=chrom, n_kept=int(kk.size), staged=staged, sections=sections, ref_span=(ga, gb), exclude=list(exclude or ()),
+        return dict(chrom=chrom, n_kept=int(kk.size), staged=staged, sections=sections, ref_span=(ga, gb), ref_contig=ref_contig, exclude=list(exclude or ()),
                     codes_len=int(codes_len.value), tile_size=tile_size,
                     tile_pos0=int(tile_pos0.value), n_tiles=int(n_tiles.value), n_entries=int(n_ent.value), pos_lo=pos_lo, pos_hi=pos_hi,
                     n_reads=n, read_start=start, read_end=end, read_flag=flag, keep=keep, mates=mates)
@@ -680,10 +681,20 @@ class DeviceBam:
         # the scan's reference codes on the tile grid, from the contig's letters (wire.ref_wire_from_string + nc_wire_expand's rule, in HBM: the
         # 9 MB table passes of a contig kept a worker thread -- and the interpreter lock the launching thread needs -- busy for milliseconds)
         ref_len, t0 = prep["n_tiles"] * prep["tile_size"], prep["tile_pos0"]
-        ref_code = torch.full((ref_len,), 4, dtype=torch.uint8, device=dev)
         ga, gb = prep["ref_span"]
-        if gb >= ga:
-            ref_code[ga - t0:gb - t0 + 1] = self._ref_lut()[sec("ref_letters").to(torch.int32)]
+        if prep.get("ref_contig") is not None:                           # the same codes straight from the FASTA image in HBM (nc_fasta_decode)
+            try:
+                ref_code = prep["ref_contig"].scan_codes(t0, ref_len, ga, gb)
+            except DeviceIngestUnavailable:                              # no room for the image: the host reader's letters, as below
+                from .bam import read_fasta_bytes
+                letters = np.frombuffer(read_fasta_bytes(prep["ref_contig"].owner.path, prep["chrom"]), np.uint8)[max(0, ga - 1):max(0, gb)]
+                ref_code = torch.full((ref_len,), 4, dtype=torch.uint8, device=dev)
+                if gb >= ga:
+                    ref_code[ga - t0:gb - t0 + 1] = self._ref_lut()[torch.from_numpy(letters.copy()).to(dev).to(torch.int32)]
+        else:
+            ref_code = torch.full((ref_len,), 4, dtype=torch.uint8, device=dev)
+            if gb >= ga:
+                ref_code[ga - t0:gb - t0 + 1] = self._ref_lut()[sec("ref_letters").to(torch.int32)]
         for (a, b) in prep["exclude"]:                                   # tree.overlaps(pos): a <= pos < b (generate_SNP_pileups.py:116-119,161)
             lo, hi = max(1, int(a)) - t0, max(1, int(b)) - t0
             if hi > max(lo, 0):
@@ -821,3 +832,5 @@ def release(path=None, buffers=False):
     if buffers:
         _RAW_POOL.clear()
         _WORK_POOL.clear()
+        from . import device_fasta
+        device_fasta.release()                                           # the FASTA images and contigs kept in HBM go with the other pools

@@ -468,6 +468,18 @@ class Engine:
         self._check(self.L.nc_bgzf_assemble_device(self.ctx, int(clen.numel()), _ptr(pay), _ptr(poff), _ptr(clen), _ptr(crc), _ptr(isize), _ptr(foff),
                                                    _ptr(file)), "nc_bgzf_assemble_device")
 
+    def fasta_decode(self, raw, first, length, linebases, linewidth, *, letters=None, scan=None, scan_pos0=1, ga=1, gb=None, blind=None, status=None,
+                     raw_len=None):
+        """one contig of the FASTA file image `raw` (uint8 device tensor; `first`, `length`, `linebases`, `linewidth`: its .fai columns) to
+        `letters` [length], `scan` (the scan's codes, entry p - scan_pos0 for p in [ga, gb], 4 elsewhere) and `blind` [length], each a uint8 device
+        tensor or None (nc_fasta_decode, on the context's stream; returns when they are complete).  A file the .fai does not describe raises."""
+        if status is None:
+            status = torch.empty(1, dtype=torch.int32, device=self.device)
+        rc = self.L.nc_fasta_decode(self.ctx, _ptr(raw), int(raw.numel() if raw_len is None else raw_len), int(first), int(length), int(linebases),
+                                    int(linewidth), _ptr(letters), _ptr(scan), int(scan_pos0), 0 if scan is None else int(scan.numel()), int(ga),
+                                    int(length if gb is None else gb), _ptr(blind), _ptr(status))
+        self._check(rc, "nc_fasta_decode")
+
     def indel_scan(self, dp: DevicePack, start, end, *, mincov, win_size, small_win_size, ins_t, del_t, excl=None, haploid=False, impute=False):
         """K7 -> int8 [end-start+1] per-column decision (-1 none, 0 long-window rule, 1 small-window rule, 2 impute_indel_phase
         candidate when impute=True)."""

@@ -225,9 +225,9 @@ def device_ingest_pack(dct, chrom, device=0, span=None):
     key = (sam_path, fasta_path, chrom, supp, excl, device, "device ingest, by name", st.st_size, st.st_mtime_ns) + ((span,) if span else ())
 
     def make():
-        from .bam import read_fasta_bytes
+        from .device_fasta import reference_for
         get_engine(device).use_torch_stream()
-        prep = dbam.prepare(chrom, read_fasta_bytes(fasta_path, chrom), supplementary=supp, exclude=excl, span=span, by_name=True,
+        prep = dbam.prepare(chrom, reference_for(fasta_path, chrom, device, dct), supplementary=supp, exclude=excl, span=span, by_name=True,
                             haplotags=getattr(sam_path, "tags", None))
         return (dbam.pack(prep), None)
     return _PACKS.get(key, make)[0]

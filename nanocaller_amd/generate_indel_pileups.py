@@ -724,18 +724,29 @@ def _device_ingest_contig(dct, sam_path, chrom, supp, device, by_name=False):
     st = os.stat(sam_path)
     key = (sam_path, chrom, dct["fasta_path"], supp, device, bool(by_name), st.st_size, st.st_mtime_ns)
     if key not in _DEV_INGEST:
-        from .bam import read_fasta_bytes
         from .device_bam import DeviceIngestUnavailable, open_device_bam
+        from .device_fasta import reference_for
         from .wire import indel_reads_struct
         _DEV_INGEST.clear()
         try:
             dbam = open_device_bam(sam_path, device, contigs=[chrom])
         except DeviceIngestUnavailable:
             return None
-        fasta_b = read_fasta_bytes(dct["fasta_path"], chrom)
-        dp = dbam.pack(dbam.prepare(chrom, fasta_b, supplementary=supp, haplotags=getattr(sam_path, "tags", None), by_name=bool(by_name)), indel=True,
+        # the letters as bytes, or (a bgzipped FASTA; a plain one with dct['device_fasta'] / NC_DEVICE_FASTA=1) the contig in HBM: the pack's
+        # reference codes come from there, and the host's copy of the letters -- the windows' reference text -- is one D2H
+        ref = reference_for(dct["fasta_path"], chrom, device, dct)
+        dp = dbam.pack(dbam.prepare(chrom, ref, supplementary=supp, haplotags=getattr(sam_path, "tags", None), by_name=bool(by_name)), indel=True,
                        tail_cap=TAIL_CAP)
-        _DEV_INGEST[key] = (dp, indel_reads_struct(dp), dict(fasta=fasta_b.decode("ascii"), fasta_b=fasta_b, device_ingest=True),
+        ref_contig = ref if hasattr(ref, "scan_codes") else None
+        if ref_contig is not None:
+            try:
+                fasta_b = ref_contig.host_letters()
+            except DeviceIngestUnavailable:
+                from .bam import read_fasta_bytes
+                fasta_b, ref_contig = read_fasta_bytes(dct["fasta_path"], chrom), None
+        else:
+            fasta_b = ref
+        _DEV_INGEST[key] = (dp, indel_reads_struct(dp), dict(fasta=fasta_b.decode("ascii"), fasta_b=fasta_b, device_ingest=True, ref_contig=ref_contig),
                             indel_mate_table(dp, dp.indel["read_ps"]) if by_name else None)
     return _DEV_INGEST[key]
 

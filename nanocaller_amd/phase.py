@@ -198,7 +198,8 @@ def _realign_inputs(sam_path, fasta_path, chrom, supplementary, device):
         raise _lib.NanoCallerHipError("phase_contig(realign=True): the pack of %r, contig %s, carries no indel events / inserted bases" % (sam_path, chrom))
     key = ("phase_ref_code", device)
     if key not in ctg:
-        ctg[key] = torch.from_numpy(_ref_codes(ctg["fasta"])).to(eng.device)
+        # (a reference that took the device route, device_fasta.py: the same codes were made in HBM beside the letters)
+        ctg[key] = ctg["ref_contig"].blind_codes if ctg.get("ref_contig") is not None else torch.from_numpy(_ref_codes(ctg["fasta"])).to(eng.device)
     return dp, (dp.codes, reads_c, dp.events["ev_pos"].numel(), ix["ins_bases"].numel(), ctg[key])
 
 

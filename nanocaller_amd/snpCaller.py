@@ -329,14 +329,15 @@ def _prepare_device(dbam, params, chrom, grp, ref=None):
     """host half of a group's ingest on the device route (device_bam.py), on a worker thread: the contig's reference sequence, which of its
     alignments the pileup keeps, the tile index -- from the per-record fields the device extracted when the file was loaded.  Alignments that
     share a read name are keyed by name (by_name=True: when name hashes repeat, one small launch on the context's own stream confirms the names)"""
-    from .bam import read_fasta_bytes
+    from .device_fasta import reference_for
     from .generate_SNP_pileups import _exclude_rows
     # (contig_span's rule, on the lengths the loader already holds: no second open of the BAM)
     length = dbam.ref_lengths[dbam.ref_names.index(chrom)] if chrom in dbam.ref_names else 0
     lo = max(1, min(c['start'] for c in grp) - _lib.FLANK)
     hi = min(length, max(c['end'] for c in grp) + _lib.FLANK)
     span = None if (hi - lo + 1) >= 0.9 * length else (lo, hi)
-    ref = ref.result() if ref is not None else read_fasta_bytes(params['fasta_path'], chrom)
+    # (the letters as bytes, or -- a bgzipped FASTA, or a plain one with params['device_fasta'] / NC_DEVICE_FASTA=1 -- the contig on its way to HBM)
+    ref = ref.result() if ref is not None else reference_for(params['fasta_path'], chrom, dbam.device, params)
     return dbam.prepare(chrom, ref, supplementary=bool(params.get('supplementary')), exclude=_exclude_rows(params, chrom), span=span, by_name=True)
 
 
@@ -415,8 +416,8 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
         # (alignments that share a read name -- a split read's records under dct['supplementary'], paired mates -- are keyed by NAME on both routes:
         # pack.name_groups, fed by nc_decoded_name_groups on the host route and by nc_bam_name_groups here)
         if piped and keys and params.get('device_ingest', os.environ.get('NC_DEVICE_INGEST', '1') != '0') and params.get('fasta_path'):
-            from .bam import read_fasta_bytes
             from .device_bam import DeviceIngestUnavailable, open_device_bam, plan_shares
+            from .device_fasta import reference_for
             try:
                 lim = os.environ.get('NC_DEVICE_INGEST_SHARE_GB')
                 order = list(dict.fromkeys(k[0] for k in keys))
@@ -453,10 +454,11 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
                 get_engine(device).sync()
                 _release_device_bam(params['sam_path'])
             if run_dev[i] is not None:
-                # the first contigs' reference letters are read while the file is loaded (the loader mostly waits: for its reader threads, for the GPU)
+                # the first contigs' reference letters are read while the file is loaded (the loader mostly waits: for its reader threads, for the GPU);
+                # on the device route of the FASTA (device_fasta.py) that is the read of their byte ranges and their upload, on the upload stream
                 ref_pool = ThreadPoolExecutor(max_workers=2)
                 for k in keys[i:min(run_end[i], i + 3)]:
-                    refs.setdefault(k[0], ref_pool.submit(read_fasta_bytes, params['fasta_path'], k[0]))
+                    refs.setdefault(k[0], ref_pool.submit(reference_for, params['fasta_path'], k[0], device, params))
                 try:
                     dbam = open_device_bam(params['sam_path'], device, contigs=list(run_dev[i]))
                 except DeviceIngestUnavailable:
@@ -512,6 +514,8 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
             from .device_bam import release as release_device_bam
             dbam = None
             release_device_bam(params['sam_path'])
+            from .device_fasta import release as release_device_fasta
+            release_device_fasta(params['fasta_path'])                   # (the last contig's FASTA image, where the reference took the device route)
 
 
 # ------------------------------------------------------------------ BGZF (so no bgzip binary is needed)
