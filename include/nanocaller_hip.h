@@ -873,7 +873,22 @@ int nc_synth_indel_reads(nc_ctx *ctx, int64_t L, uint64_t seed, double p_sub, do
  *   (min(c0, c1)), every read on the first allele (popc(M1)) and every read on the second (popc(M0)), each plus G unless it is the called
  *   class; ties go to the called class, then het, first, second.  site_phased then also needs the outcome het.
  * nc_snp_phase_genotypes: *site_gt = the outcome class per site [n_sites] after nc_snp_phase_solve_gt (a site outside the blocks keeps its
- *   call), NULL after the plain solve; valid as nc_snp_phase_view's arrays are. */
+ *   call), NULL after the plain solve; valid as nc_snp_phase_view's arrays are.
+ * The weighted model (DESIGN.md "Read-based phasing", step 6c; opt-in): every entry carries a weight 0..93, the price of flipping its allele, and
+ *   every read a flag whether read selection may accept it.  After either setter below nc_snp_phase_solve, nc_snp_phase_solve_gt and
+ *   nc_haplotag_run run the weighted forms on the handle: a column costs min(c0, c1) with c0 / c1 the weight sums in place of the counts
+ *   (homozygous outcomes: the weight sums of M1 / M0), a read with read_ok 0 is never accepted (side -1) but still tagged, and a name's block
+ *   score adds +-weight.  Weights all 1 with every read allowed give the plain forms' arrays.
+ * nc_snp_phase_set_weights: entry_weight [n_entries] and read_ok [n_reads] from the host; NULL = all 1 (either).  NC_ERR_ARG for a weight above
+ *   93 or a flag above 1.
+ * nc_snp_phase_weights_from_bam: the weights from the BAM records of the handle's reads: d_raw [raw_len] (dev) = the inflated record stream
+ *   (nc_inflate_device), d_rec_off [n_reads] (dev) = where every read's record (its block_size field) starts.  entry weight = min(w_max, quality of
+ *   the query base the CIGAR aligns to the site), under a D / N operation the last query base's before it; default_weight where there is no such
+ *   base or no quality (0xff), both in [0, 93].  read_ok = MAPQ >= mapq_min (in [0, 255]).  The CIGAR is the record's, or the CG tag's behind the
+ *   placeholder, as nc_bam_meta takes it.  Every offset is checked against block_size and raw_len; a record that does not hold what its header
+ *   claims returns NC_ERR_ARG (the status bits in nc_last_error) and leaves the handle unweighted.
+ * nc_snp_phase_weights: host views (NULL before a setter; each pointer may be NULL): entry_weight [n_entries], read_mapq [n_reads] (0 after
+ *   nc_snp_phase_set_weights), read_ok [n_reads]; valid as nc_snp_phase_view's arrays are. */
 typedef struct nc_phase nc_phase;
 typedef struct {
     int32_t n_reads, n_sites, n_blocks, n_groups;
@@ -904,6 +919,10 @@ int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out);
 int nc_snp_phase_free(nc_phase *ph);
 int nc_snp_phase_solve_gt(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost);
 int nc_snp_phase_genotypes(const nc_phase *ph, const uint8_t **site_gt);
+int nc_snp_phase_set_weights(nc_ctx *ctx, nc_phase *ph, const uint8_t *entry_weight, const uint8_t *read_ok);
+int nc_snp_phase_weights_from_bam(nc_ctx *ctx, nc_phase *ph, const uint8_t *d_raw, int64_t raw_len, const int64_t *d_rec_off, int32_t mapq_min,
+                                  int32_t default_weight, int32_t w_max);
+int nc_snp_phase_weights(const nc_phase *ph, const uint8_t **entry_weight, const uint8_t **read_mapq, const uint8_t **read_ok);
 
 /* The reference FASTA on the device (csrc/nc_fasta.hip): one contig of a FASTA file image in HBM -- the file as it stands, or a bgzipped file's
  * members inflated by nc_inflate_device -- to the forms the callers read.  d_raw[0, raw_len) = the image, `first` = offset of the contig's

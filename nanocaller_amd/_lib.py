@@ -46,6 +46,7 @@ EXPORTS = [
     "nc_indel_sites_fetch", "nc_indel_sites_fetch_alt", "nc_indel_sites_stage_ms", "nc_indel_sites_band_stats", "nc_indel_sites_band", "nc_indel_events_pack", "nc_indel_events_expand", "nc_inflate_device", "nc_inflate_device_phase", "nc_bgzf_crc_device", "nc_bgzf_members", "nc_bgzf_scan", "nc_bam_walk", "nc_bam_meta", "nc_bam_codes", "nc_bam_indel_reads", "nc_bam_name_groups", "nc_indel_sites_scoring", "nc_indel_vcf_format", "nc_synth_indel_truth", "nc_synth_indel_reads", "nc_cnn_x_limit", "nc_cnn_range_watch", "nc_snp_trunk_info",
     "nc_snp_phase_gather", "nc_snp_phase_load", "nc_snp_phase_solve", "nc_haplotag_run", "nc_snp_phase_view", "nc_snp_phase_free",
     "nc_snp_phase_realign", "nc_snp_phase_solve_gt", "nc_snp_phase_genotypes",
+    "nc_snp_phase_set_weights", "nc_snp_phase_weights_from_bam", "nc_snp_phase_weights",
     "nc_bam_retag_sizes", "nc_bam_retag", "nc_bgzf_deflate_device", "nc_bgzf_crc32_device", "nc_bgzf_assemble_device",
     "nc_fasta_decode",
 ]
@@ -265,6 +266,9 @@ def lib():
         L.nc_snp_phase_solve.argtypes = [vp, vp, i32]
         L.nc_snp_phase_solve_gt.argtypes = [vp, vp, i32, vp, i32]
         L.nc_snp_phase_genotypes.argtypes = [vp, C.POINTER(vp)]
+        L.nc_snp_phase_set_weights.argtypes = [vp, vp, vp, vp]
+        L.nc_snp_phase_weights_from_bam.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32]
+        L.nc_snp_phase_weights.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.nc_snp_phase_realign.argtypes = [vp, vp, i64, C.POINTER(IndelReadsC), i64, i64, vp, i32, i32, vp, vp, C.POINTER(vp)]
         L.nc_haplotag_run.argtypes = [vp, vp, i32, vp]
         L.nc_snp_phase_view.argtypes = [vp, C.POINTER(PhaseArraysC)]

@@ -66,6 +66,11 @@ struct nc_phase {
     std::vector<uint8_t> site_gt;          // nc_snp_phase_solve_gt only: the outcome per site (0 het, 1 / 2 homozygous first / second allele)
     std::vector<int64_t> block_cost;
     std::vector<int32_t> group_ps;
+    // the weighted model (nc_snp_phase_set_weights / nc_snp_phase_weights_from_bam): per entry its weight 0..93, per read its MAPQ (0 when the
+    // weights came from the host) and whether read selection may accept it; d_w = the weights beside d_site / d_al
+    std::vector<uint8_t> ew, rmapq, rok;
+    uint8_t *d_w = nullptr;
+    bool weighted = false;
     float ms[4] = {0, 0, 0, 0};
     bool solved = false;
 };

@@ -12,6 +12,10 @@
 //   k_hp_dp<true>       opt-in (nc_snp_phase_solve_gt): the same walk with a column cost that may also call the site homozygous
 //                       for either allele, at a price for leaving the called genotype; the traceback records each column's outcome
 //   k_hp_tag            one thread per read-name group: per-block scores -> HP / PS
+//   k_hp_quals          opt-in (nc_snp_phase_weights_from_bam): one wave per kept read walks its BAM record's CIGAR in the inflated record stream
+//                       -> the read's MAPQ and, per CSR entry, the quality of the query base aligned to the site
+//   k_hp_dp<*, true>    the weighted model (DESIGN.md "Read-based phasing", step 6c): an entry's flip costs its weight instead of 1; the
+//   k_hp_tag<true>      column's signed weight sums come from two tables in LDS, the haplotag score adds +-weight
 #include "nc_happhase.h"
 
 #include <algorithm>
@@ -25,6 +29,8 @@ namespace {
 constexpr int HP_SLOTS = 15;
 constexpr int HP_STATES = 1 << HP_SLOTS;
 constexpr int HP_GT_COST_MAX = 1024;       // (a column's cost stays far inside the DP's 16-bit relative range)
+constexpr int HP_W_MAX = 93;               // the largest entry weight (a BAM quality is a Phred value 0..93)
+constexpr int HP_WTAB = 256 + 128;         // the weighted column's two tables: subsets of slots 0..7, of slots 8..14
 
 struct HpCol {            // one column of a block: the active slots, those continuing from the previous column, the allele masks
     uint16_t act, keep, m0, m1;
@@ -42,6 +48,30 @@ struct HpGtCost {
     {
     }
 };
+
+// the weighted form's LDS tables (only its instantiations allocate them): T[x] = sum of d over the slots of x, d[s] = +w on the m1 slots,
+// -w on the m0 slots; entries 0..255 for the slots 0..7, 256..383 for the slots 8..14
+template <bool W>
+__device__ __forceinline__ int16_t *hp_wtab()
+{
+    if constexpr (W) {
+        __shared__ int16_t T[HP_WTAB];
+        return T;
+    } else {
+        return nullptr;
+    }
+}
+
+// the weighted e0 = W(m1 & ~B) + W(m0 & B) and e1 = W(m0 & ~B) + W(m1 & B) from the column's slot weights (the traceback's one thread)
+__device__ __forceinline__ void hp_w_costs(const uint8_t *w, uint32_t m0, uint32_t m1, uint32_t B, uint32_t &e0, uint32_t &e1)
+{
+    e0 = e1 = 0;
+    for (int s = 0; s < HP_SLOTS; s++) {
+        const uint32_t b = 1u << s, v = w[s];
+        if (m0 & b) (B & b ? e0 : e1) += v;
+        if (m1 & b) (B & b ? e1 : e0) += v;
+    }
+}
 
 __device__ __forceinline__ uint32_t hp_pdep(uint32_t t, uint32_t mask)
 {
@@ -101,12 +131,15 @@ __global__ __launch_bounds__(256) void k_hp_gather(const uint8_t *__restrict__ c
 // slots, the backtrace (smallest minimising bits of the leaving slots) per (column, continuing subset) in HBM at bt_off[column].
 // GT: the genotype-aware form (its column carries the called class; gt_cost = the price G of leaving it; colg[column] = the outcome, classed
 // as the called class is).  The plain form reads neither argument.
-template <bool GT>
+// W: the weighted form (colw[16 * column + slot] = the weight of the slot's allele at the column; unit costs read no weight).
+template <bool GT, bool W>
 __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<GT, HpColGt, HpCol> *__restrict__ cols, const int32_t *__restrict__ bfirst,
                                                        const int32_t *__restrict__ blast, const int64_t *__restrict__ bt_off, uint16_t *__restrict__ bt,
                                                        uint16_t *__restrict__ colB, uint8_t *__restrict__ colh, int64_t *__restrict__ bcost,
-                                                       int32_t *__restrict__ overflow, uint8_t *__restrict__ colg, uint32_t gt_cost)
+                                                       int32_t *__restrict__ overflow, uint8_t *__restrict__ colg, uint32_t gt_cost,
+                                                       const uint8_t *__restrict__ colw)
 {
+    int16_t *const T = hp_wtab<W>();
     __shared__ uint16_t D[HP_STATES];
     __shared__ uint16_t P[HP_STATES];
     __shared__ uint32_t red[HP_THREADS];
@@ -119,10 +152,29 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
         const auto c = cols[j];
         const uint32_t A = c.act, K = c.keep, m0 = c.m0, m1 = c.m1;
         uint32_t hadd = 0, hom = 0;                                      // (GT) het's surcharge, the cheaper homozygous outcome
-        if constexpr (GT) {
+        uint32_t Wm0 = 0, Wm1 = 0;                                       // (W) the weights of the m0 / m1 slots
+        if constexpr (W) {
+            const uint8_t *w = colw + 16 * (int64_t)j;
+            for (int s = 0; s < HP_SLOTS; s++) {
+                Wm0 += (m0 >> s) & 1 ? w[s] : 0;
+                Wm1 += (m1 >> s) & 1 ? w[s] : 0;
+            }
+            if (tid < HP_WTAB) {                                         // (the previous column's readers are behind the loop's last barrier)
+                const uint32_t x = tid < 256 ? (uint32_t)tid : (uint32_t)(tid - 256) << 8;
+                int32_t t = 0;
+                for (int s = 0; s < HP_SLOTS; s++)
+                    if ((x >> s) & 1) t += (m1 >> s) & 1 ? (int32_t)w[s] : ((m0 >> s) & 1 ? -(int32_t)w[s] : 0);
+                T[tid] = (int16_t)t;
+            }
+        }
+        if constexpr (GT && !W) {
             const HpGtCost g(m0, m1, c.gt, gt_cost);
             hadd = g.hadd;
             hom = min(g.homA, g.homB);
+        }
+        if constexpr (GT && W) {
+            hadd = c.gt == 0 ? 0u : gt_cost;
+            hom = min(Wm1 + (c.gt == 1 ? 0u : gt_cost), Wm0 + (c.gt == 2 ? 0u : gt_cost));
         }
         if (j > c0) {
             const uint32_t Lm = prevA & ~K;
@@ -166,7 +218,15 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
         uint32_t mn = ~0u;
         for (int32_t t = tid; t < NA; t += HP_THREADS) {
             const uint32_t B = hp_pdep(t, A);
-            const uint32_t e0 = __popc(m1 & ~B) + __popc(m0 & B), e1 = __popc(m0 & ~B) + __popc(m1 & B);
+            uint32_t e0, e1;
+            if constexpr (W) {                                           // e1 = W(m0) + T(B), e0 = W(m1) - T(B)
+                const int32_t tb = T[B & 255] + T[256 + (B >> 8)];
+                e1 = (uint32_t)((int32_t)Wm0 + tb);
+                e0 = (uint32_t)((int32_t)Wm1 - tb);
+            } else {
+                e0 = __popc(m1 & ~B) + __popc(m0 & B);
+                e1 = __popc(m0 & ~B) + __popc(m1 & B);
+            }
             mn = min(mn, (first ? 0u : (uint32_t)P[B & K]) + (GT ? min(min(e0, e1) + hadd, hom) : min(e0, e1)));
         }
         mn = hp_wave_min(mn);
@@ -175,7 +235,15 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
         const uint32_t cmin = smin;
         for (int32_t t = tid; t < NA; t += HP_THREADS) {
             const uint32_t B = hp_pdep(t, A);
-            const uint32_t e0 = __popc(m1 & ~B) + __popc(m0 & B), e1 = __popc(m0 & ~B) + __popc(m1 & B);
+            uint32_t e0, e1;
+            if constexpr (W) {                                           // e1 = W(m0) + T(B), e0 = W(m1) - T(B)
+                const int32_t tb = T[B & 255] + T[256 + (B >> 8)];
+                e1 = (uint32_t)((int32_t)Wm0 + tb);
+                e0 = (uint32_t)((int32_t)Wm1 - tb);
+            } else {
+                e0 = __popc(m1 & ~B) + __popc(m0 & B);
+                e1 = __popc(m0 & ~B) + __popc(m1 & B);
+            }
             const uint32_t v = (first ? 0u : (uint32_t)P[B & K]) + (GT ? min(min(e0, e1) + hadd, hom) : min(e0, e1)) - cmin;
             if (v > 0xFFFFu) atomicOr(overflow, 1);
             D[B] = (uint16_t)min(v, 0xFFFFu);
@@ -203,12 +271,23 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
         uint32_t B = smin & 0xFFFF;
         for (int32_t j = c1; j >= c0; j--) {
             const auto c = cols[j];
-            const uint32_t e0 = __popc(c.m1 & ~B) + __popc(c.m0 & B), e1 = __popc(c.m0 & ~B) + __popc(c.m1 & B);
+            uint32_t e0, e1;
+            if constexpr (W) hp_w_costs(colw + 16 * (int64_t)j, c.m0, c.m1, B, e0, e1);
+            else {
+                e0 = __popc(c.m1 & ~B) + __popc(c.m0 & B);
+                e1 = __popc(c.m0 & ~B) + __popc(c.m1 & B);
+            }
             colB[j] = (uint16_t)B;
             colh[j] = e0 <= e1 ? 0 : 1;
             if constexpr (GT) {
                 // the smallest (cost, pref): pref 0 for the called class, else 1 het, 2 homozygous first, 3 homozygous second
-                const HpGtCost g(c.m0, c.m1, c.gt, gt_cost);
+                HpGtCost g(c.m0, c.m1, c.gt, gt_cost);
+                if constexpr (W) {                                       // homA = W(m1) (+G), homB = W(m0) (+G)
+                    uint32_t w1, w0;
+                    hp_w_costs(colw + 16 * (int64_t)j, c.m0, c.m1, 0, w1, w0);
+                    g.homA = w1 + (c.gt == 1 ? 0u : gt_cost);
+                    g.homB = w0 + (c.gt == 2 ? 0u : gt_cost);
+                }
                 const uint32_t cost[3] = {min(e0, e1) + g.hadd, g.homA, g.homB};
                 uint32_t best = ~0u;
                 for (uint32_t o = 0; o < 3; o++) best = min(best, (cost[o] << 4) | ((o == c.gt ? 0u : o + 1) << 2) | o);
@@ -224,7 +303,9 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
 }
 
 // sblk: block of a PHASED site, -1 otherwise (sites are contiguous per block: a read's entries of one block form one run)
-__device__ void hp_block_score(int32_t r, int32_t b, const int64_t *off, const int32_t *esite, const uint8_t *eal, const int32_t *sblk,
+// W: an entry scores its weight ew[e] instead of 1
+template <bool W>
+__device__ void hp_block_score(int32_t r, int32_t b, const int64_t *off, const int32_t *esite, const uint8_t *eal, const uint8_t *ew, const int32_t *sblk,
                                const uint8_t *sh, const int32_t *bfirst, const int32_t *blast, int32_t &n, int32_t &s)
 {
     const int64_t e0 = off[r], e1 = off[r + 1];
@@ -238,13 +319,15 @@ __device__ void hp_block_score(int32_t r, int32_t b, const int64_t *off, const i
         const int32_t site = esite[e];
         if (sblk[site] != b) continue;
         n++;
-        s += eal[e] == sh[site] ? 1 : -1;
+        const int32_t v = W ? (int32_t)ew[e] : 1;
+        s += eal[e] == sh[site] ? v : -v;
     }
 }
 
+template <bool W>
 __global__ __launch_bounds__(256) void k_hp_tag(int32_t n_groups, const int32_t *__restrict__ goff, const int32_t *__restrict__ greads,
                                                 const int64_t *__restrict__ off, const int32_t *__restrict__ esite, const uint8_t *__restrict__ eal,
-                                                const int32_t *__restrict__ sblk, const uint8_t *__restrict__ sh, const int32_t *__restrict__ bfirst,
+                                                const uint8_t *__restrict__ ew, const int32_t *__restrict__ sblk, const uint8_t *__restrict__ sh, const int32_t *__restrict__ bfirst,
                                                 const int32_t *__restrict__ blast, const int32_t *__restrict__ bps, uint8_t *__restrict__ ghp,
                                                 int32_t *__restrict__ gps)
 {
@@ -263,12 +346,12 @@ __global__ __launch_bounds__(256) void k_hp_tag(int32_t n_groups, const int32_t 
             bool seen = false;                                          // scored already from an earlier alignment of the name
             for (int32_t ib = goff[g]; ib < ia && !seen; ib++) {
                 int32_t n = 0, s = 0;
-                hp_block_score(greads[ib], b, off, esite, eal, sblk, sh, bfirst, blast, n, s);
+                hp_block_score<W>(greads[ib], b, off, esite, eal, ew, sblk, sh, bfirst, blast, n, s);
                 seen = n > 0;
             }
             if (seen) continue;
             int32_t n = 0, s = 0;
-            for (int32_t ib = goff[g]; ib < goff[g + 1]; ib++) hp_block_score(greads[ib], b, off, esite, eal, sblk, sh, bfirst, blast, n, s);
+            for (int32_t ib = goff[g]; ib < goff[g + 1]; ib++) hp_block_score<W>(greads[ib], b, off, esite, eal, ew, sblk, sh, bfirst, blast, n, s);
             if (n > best_n || (n == best_n && bps[b] < best_ps)) {
                 best_n = n;
                 best_s = s;
@@ -281,6 +364,137 @@ __global__ __launch_bounds__(256) void k_hp_tag(int32_t n_groups, const int32_t 
     gps[g] = hp ? best_ps : 0;
 }
 
+// ---- MAPQ and base qualities from the device ingest's inflated record stream (nc_ingest.hip made the pack from the same records)
+__device__ __forceinline__ uint32_t hq_ldu32(const uint8_t *p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+constexpr int HQ_WPB = 4;                                               // waves (reads) per workgroup
+enum { HQ_BAD_RECORD = 1, HQ_BAD_FIELDS = 4 };                          // status bits: the record leaves the stream / its fields leave block_size (k_meta's bit)
+
+// One wave per kept read r (record at raw + rec[r]; entries off[r] .. off[r + 1] in site order).  The CIGAR -- the record's own, or the CG tag's
+// behind the placeholder <l_seq>S<n>N, k_meta's rule -- goes by in chunks of 64 operations, one per lane; prefix sums give every operation its
+// reference and query start, and the lane looks up the read's entries whose site lies in its reference run: under M / = / X the aligned query
+// base's quality, under D / N the last query base's before the operation.  ew = min(quality, w_max); default_weight where there is no base or no
+// quality (0xff), and for an entry outside the alignment.  Everything read is checked against block_size, the stream's length and l_seq.
+__global__ __launch_bounds__(64 * HQ_WPB) void k_hp_quals(const uint8_t *__restrict__ raw, int64_t raw_len, int32_t n_reads, const int64_t *__restrict__ rec,
+                                                          const int64_t *__restrict__ off, const int32_t *__restrict__ esite, const int32_t *__restrict__ spos,
+                                                          int32_t mapq_min, int32_t default_weight, int32_t w_max, uint8_t *__restrict__ ew,
+                                                          uint8_t *__restrict__ mapq, uint8_t *__restrict__ rok, int32_t *__restrict__ status)
+{
+    const int lane = threadIdx.x & 63;
+    const int32_t r = blockIdx.x * HQ_WPB + (threadIdx.x >> 6);
+    if (r >= n_reads) return;
+    const int64_t e0 = off[r], e1 = off[r + 1], o = rec[r];
+    int bad = (o < 0 || o + 36 > raw_len) ? HQ_BAD_RECORD : 0;
+    int64_t bs = 0;
+    if (!bad) {
+        bs = (int32_t)hq_ldu32(raw + o);
+        if (bs < 32 || o + 4 + bs > raw_len) bad = HQ_BAD_RECORD;
+    }
+    const uint8_t *p = raw + (bad ? 0 : o + 4);                          // the record body: p[0, bs)
+    int64_t l_name = 0, n_cig = 0, l_seq = 0, pos = 0;
+    int mq = 0;
+    if (!bad) {
+        pos = (int32_t)hq_ldu32(p + 4);
+        l_name = p[8];
+        mq = p[9];
+        n_cig = p[12] | (p[13] << 8);
+        l_seq = (int32_t)hq_ldu32(p + 16);
+        if (l_seq < 0 || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs) bad = HQ_BAD_FIELDS;
+    }
+    if (bad) {
+        if (lane == 0) {
+            atomicOr(status, bad);
+            mapq[r] = 0;
+            rok[r] = 0;
+        }
+        for (int64_t e = e0 + lane; e < e1; e += 64) ew[e] = (uint8_t)default_weight;
+        return;
+    }
+    int64_t cigo = 32 + l_name, nc = n_cig;                              // the CIGAR: p[cigo, cigo + 4 nc)
+    const int64_t qualo = cigo + 4 * n_cig + (l_seq + 1) / 2, auxo = qualo + l_seq;
+    if (n_cig == 2) {
+        const uint32_t c0 = hq_ldu32(p + cigo), c1 = hq_ldu32(p + cigo + 4);
+        if ((c0 & 15) == 4 && (int64_t)(c0 >> 4) == l_seq && (c1 & 15) == 3) {
+            // the placeholder: the real CIGAR is the CG:B,I tag's (every lane walks the tags alike)
+            for (int64_t a = auxo; a + 3 <= bs;) {
+                const char t0 = (char)p[a], t1 = (char)p[a + 1], ty = (char)p[a + 2];
+                a += 3;
+                switch (ty) {
+                case 'c': case 'C': case 'A': a += 1; break;
+                case 's': case 'S': a += 2; break;
+                case 'i': case 'I': case 'f': a += 4; break;
+                case 'Z': case 'H':
+                    while (a < bs && p[a]) a++;
+                    a++;
+                    break;
+                case 'B': {
+                    if (a + 5 > bs) {
+                        a = bs;
+                        break;
+                    }
+                    const char st = (char)p[a];
+                    const int64_t cnt = hq_ldu32(p + a + 1);
+                    const int es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
+                    if (t0 == 'C' && t1 == 'G' && st == 'I' && a + 5 + cnt * 4 <= bs) {
+                        cigo = a + 5;
+                        nc = cnt;
+                    }
+                    a += 5 + cnt * es;
+                    break;
+                }
+                default: a = bs; break;
+                }
+            }
+        }
+    }
+    const int64_t s1 = pos + 1;                                          // the 1-based position of the alignment's first reference base
+    int64_t rp = 0, qp = 0;
+#pragma unroll 1
+    for (int64_t k0 = 0; k0 < nc; k0 += 64) {
+        const int64_t k = k0 + lane;
+        const uint32_t c = k < nc ? hq_ldu32(p + cigo + 4 * k) : 15u;
+        const int op = c & 15;
+        const int32_t len = (int32_t)(c >> 4);
+        const bool m = op == 0 || op == 7 || op == 8, gap = op == 2 || op == 3;
+        const int32_t radv = (m || gap) ? len : 0, qadv = (m || op == 1 || op == 4) ? len : 0;     // (hard clips and pads consume nothing)
+        const int64_t ri = (int64_t)nc_wave_incl_scan(radv & 0xFFFF) + ((int64_t)nc_wave_incl_scan(radv >> 16) << 16);
+        const int64_t qi = (int64_t)nc_wave_incl_scan(qadv & 0xFFFF) + ((int64_t)nc_wave_incl_scan(qadv >> 16) << 16);
+        if (radv > 0) {
+            const int64_t a = s1 + rp + ri - radv, b = a + radv, q0 = qp + qi - qadv;
+            int64_t lo = e0, hi = e1;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (spos[esite[mid]] < a) lo = mid + 1;
+                else hi = mid;
+            }
+            for (int64_t e = lo; e < e1; e++) {
+                const int64_t sp = spos[esite[e]];
+                if (sp >= b) break;
+                const int64_t q = m ? q0 + (sp - a) : q0 - 1;
+                int32_t w = default_weight;
+                if (q >= 0 && q < l_seq) {
+                    const int32_t v = p[qualo + q];
+                    if (v != 0xff) w = min(v, w_max);
+                }
+                ew[e] = (uint8_t)w;
+            }
+        }
+        rp += __shfl(ri, 63);
+        qp += __shfl(qi, 63);
+    }
+    for (int64_t e = e0 + lane; e < e1; e += 64) {                       // entries the alignment does not reach
+        const int64_t sp = spos[esite[e]];
+        if (sp < s1 || sp >= s1 + rp) ew[e] = (uint8_t)default_weight;
+    }
+    if (lane == 0) {
+        mapq[r] = (uint8_t)mq;
+        rok[r] = mq >= mapq_min ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 static void hp_free_dev(nc_phase *ph)
@@ -288,6 +502,8 @@ static void hp_free_dev(nc_phase *ph)
     if (ph->d_off) (void)hipFree(ph->d_off);
     if (ph->d_site) (void)hipFree(ph->d_site);
     if (ph->d_al) (void)hipFree(ph->d_al);
+    if (ph->d_w) (void)hipFree(ph->d_w);
+    ph->d_w = nullptr;
     ph->d_off = nullptr;
     ph->d_site = nullptr;
     ph->d_al = nullptr;
@@ -305,6 +521,16 @@ static int hp_upload_csr(nc_phase *ph)
         NC_HIP(ctx, hipMemcpyAsync(ph->d_site, ph->esite.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(ph->d_al, ph->eal.data(), ne, hipMemcpyHostToDevice, ctx->stream));
     }
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NC_OK;
+}
+
+// the weighted model's entry weights beside the CSR in HBM (k_hp_tag<true> reads them)
+static int hp_upload_weights(nc_phase *ph)
+{
+    nc_ctx *ctx = ph->ctx;
+    if (!ph->d_w) NC_HIP(ctx, hipMalloc(&ph->d_w, ph->ew.size() + 16));
+    if (!ph->ew.empty()) NC_HIP(ctx, hipMemcpyAsync(ph->d_w, ph->ew.data(), ph->ew.size(), hipMemcpyHostToDevice, ctx->stream));
     NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NC_OK;
 }
@@ -421,8 +647,9 @@ static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *s
     const std::vector<int32_t> &es = ph->esite;
     // read selection: most informative sites first, then the first site, then the read index
     std::vector<int32_t> order;
+    const bool weighted = ph->weighted;                                 // (a read the MAPQ floor refuses is never accepted)
     for (int32_t r = 0; r < R; r++)
-        if (off[r + 1] - off[r] >= 2) order.push_back(r);
+        if (off[r + 1] - off[r] >= 2 && (!weighted || ph->rok[r])) order.push_back(r);
     std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
         const int64_t na = off[a + 1] - off[a], nb = off[b + 1] - off[b];
         if (na != nb) return na > nb;
@@ -508,6 +735,13 @@ static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *s
             ph->site_phased[c] = 1;
         }
     }
+    std::vector<uint8_t> colw;                                          // weighted: the weight of every column's slots
+    if (weighted) {
+        colw.assign(16 * (size_t)(S + 1), 0);
+        for (int32_t r = 0; r < R; r++)
+            if (acc[r])
+                for (int64_t e = off[r]; e < off[r + 1]; e++) colw[16 * (size_t)es[e] + slot[r]] = ph->ew[e];
+    }
     std::vector<int64_t> bt_off(S + 1, 0);
     int64_t bt_total = 0;
     for (int32_t bi = 0; bi < nblk; bi++)
@@ -529,7 +763,7 @@ static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *s
         int32_t *d_bf = nullptr, *d_bl = nullptr, *d_ovf = nullptr;
         int64_t *d_bto = nullptr, *d_cost = nullptr;
         uint16_t *d_bt = nullptr, *d_colB = nullptr;
-        uint8_t *d_colh = nullptr;
+        uint8_t *d_colh = nullptr, *d_colw = nullptr;
         std::vector<HpColGt> gcols;
         if (site_gt) {
             gcols.assign(S + 1, HpColGt{0, 0, 0, 0, 0, 0});
@@ -553,10 +787,18 @@ static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *s
         NC_HIP(ctx, hipMemcpyAsync(d_bl, ph->block_last.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bto, bt_off.data(), (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemsetAsync(d_ovf, 0, sizeof(int32_t), ctx->stream));
-        if (site_gt)
-            k_hp_dp<true><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_gcols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_colg, (uint32_t)gt_cost);
+        if (weighted) {
+            NC_TRY(sc.get(ctx, &d_colw, colw.size()));
+            NC_HIP(ctx, hipMemcpyAsync(d_colw, colw.data(), colw.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (site_gt && weighted)
+            k_hp_dp<true, true><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_gcols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_colg, (uint32_t)gt_cost, d_colw);
+        else if (weighted)
+            k_hp_dp<false, true><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, nullptr, 0, d_colw);
+        else if (site_gt)
+            k_hp_dp<true, false><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_gcols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_colg, (uint32_t)gt_cost, nullptr);
         else
-            k_hp_dp<false><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, nullptr, 0);
+            k_hp_dp<false, false><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, nullptr, 0, nullptr);
         NC_HIP(ctx, hipGetLastError());
         NC_HIP(ctx, hipMemcpyAsync(colB.data(), d_colB, (S + 1) * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(colh.data(), d_colh, S + 1, hipMemcpyDeviceToHost, ctx->stream));
@@ -627,6 +869,7 @@ int nc_haplotag_run(nc_ctx *ctx, nc_phase *ph, int32_t n_groups, const int32_t *
     ph->group_ps.assign(n_groups, 0);
     if (n_groups && nblk) {
         if (!ph->d_off) NC_TRY(hp_upload_csr(ph));
+        if (ph->weighted && !ph->d_w) NC_TRY(hp_upload_weights(ph));
         HpScratch sc;
         int32_t *d_goff = nullptr, *d_gr = nullptr, *d_sblk = nullptr, *d_bf = nullptr, *d_bl = nullptr, *d_bps = nullptr, *d_gps = nullptr;
         uint8_t *d_sh = nullptr, *d_ghp = nullptr;
@@ -646,8 +889,12 @@ int nc_haplotag_run(nc_ctx *ctx, nc_phase *ph, int32_t n_groups, const int32_t *
         NC_HIP(ctx, hipMemcpyAsync(d_bf, ph->block_first.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bl, ph->block_last.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bps, ph->block_ps.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        k_hp_tag<<<(n_groups + 255) / 256, 256, 0, ctx->stream>>>(n_groups, d_goff, d_gr, ph->d_off, ph->d_site, ph->d_al, d_sblk, d_sh, d_bf, d_bl, d_bps,
-                                                                 d_ghp, d_gps);
+        if (ph->weighted)
+            k_hp_tag<true><<<(n_groups + 255) / 256, 256, 0, ctx->stream>>>(n_groups, d_goff, d_gr, ph->d_off, ph->d_site, ph->d_al, ph->d_w, d_sblk, d_sh, d_bf,
+                                                                           d_bl, d_bps, d_ghp, d_gps);
+        else
+            k_hp_tag<false><<<(n_groups + 255) / 256, 256, 0, ctx->stream>>>(n_groups, d_goff, d_gr, ph->d_off, ph->d_site, ph->d_al, nullptr, d_sblk, d_sh, d_bf,
+                                                                            d_bl, d_bps, d_ghp, d_gps);
         NC_HIP(ctx, hipGetLastError());
         NC_HIP(ctx, hipMemcpyAsync(ph->group_hp.data(), d_ghp, n_groups, hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(ph->group_ps.data(), d_gps, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -687,6 +934,78 @@ int nc_snp_phase_genotypes(const nc_phase *ph, const uint8_t **site_gt)
 {
     if (!ph || !site_gt) return NC_ERR_ARG;
     *site_gt = ph->solved && !ph->site_gt.empty() ? ph->site_gt.data() : nullptr;
+    return NC_OK;
+}
+
+int nc_snp_phase_set_weights(nc_ctx *ctx, nc_phase *ph, const uint8_t *entry_weight, const uint8_t *read_ok)
+{
+    if (!ctx || !ph) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_set_weights: bad argument");
+    const int64_t ne = ph->off[ph->n_reads];
+    for (int64_t e = 0; entry_weight && e < ne; e++)
+        if (entry_weight[e] > HP_W_MAX) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_set_weights: entry %lld: weight %d above %d", (long long)e, entry_weight[e], HP_W_MAX);
+    for (int32_t r = 0; read_ok && r < ph->n_reads; r++)
+        if (read_ok[r] > 1) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_set_weights: read %d: read_ok must be 0 or 1", r);
+    if (entry_weight) ph->ew.assign(entry_weight, entry_weight + ne);
+    else ph->ew.assign(ne, 1);
+    if (read_ok) ph->rok.assign(read_ok, read_ok + ph->n_reads);
+    else ph->rok.assign(ph->n_reads, 1);
+    ph->rmapq.assign(ph->n_reads, 0);
+    ph->weighted = true;
+    ph->solved = false;
+    return hp_upload_weights(ph);
+}
+
+int nc_snp_phase_weights_from_bam(nc_ctx *ctx, nc_phase *ph, const uint8_t *d_raw, int64_t raw_len, const int64_t *d_rec_off, int32_t mapq_min,
+                                  int32_t default_weight, int32_t w_max)
+{
+    if (!ctx || !ph || raw_len < 0 || (ph->n_reads && (!d_raw || !d_rec_off)))
+        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_weights_from_bam: bad argument");
+    if (mapq_min < 0 || mapq_min > 255 || default_weight < 0 || default_weight > HP_W_MAX || w_max < 0 || w_max > HP_W_MAX)
+        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_weights_from_bam: mapq_min outside [0, 255], or default_weight / w_max outside [0, %d]", HP_W_MAX);
+    const int32_t R = ph->n_reads, S = ph->n_sites;
+    const int64_t ne = ph->off[R];
+    std::vector<uint8_t> ew(ne, 0), mq(R, 0), ok(R, 0);
+    int32_t status = 0;
+    if (!ph->d_off) NC_TRY(hp_upload_csr(ph));
+    if (!ph->d_w) NC_HIP(ctx, hipMalloc(&ph->d_w, ne + 16));
+    if (R) {
+        HpScratch sc;
+        int32_t *d_spos = nullptr, *d_status = nullptr;
+        uint8_t *d_mq = nullptr, *d_ok = nullptr;
+        NC_TRY(sc.get(ctx, &d_spos, S + 1));
+        NC_TRY(sc.get(ctx, &d_status, 1));
+        NC_TRY(sc.get(ctx, &d_mq, R));
+        NC_TRY(sc.get(ctx, &d_ok, R));
+        if (S) NC_HIP(ctx, hipMemcpyAsync(d_spos, ph->site_pos.data(), S * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream));
+        k_hp_quals<<<(R + HQ_WPB - 1) / HQ_WPB, 64 * HQ_WPB, 0, ctx->stream>>>(d_raw, raw_len, R, d_rec_off, ph->d_off, ph->d_site, d_spos, mapq_min, default_weight,
+                                                                             w_max, ph->d_w, d_mq, d_ok, d_status);
+        NC_HIP(ctx, hipGetLastError());
+        if (ne) NC_HIP(ctx, hipMemcpyAsync(ew.data(), ph->d_w, ne, hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(mq.data(), d_mq, R, hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(ok.data(), d_ok, R, hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(&status, d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (status) {
+        ph->weighted = false;
+        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_weights_from_bam: records that %s (status %d)",
+                       status & HQ_BAD_RECORD ? "leave the record stream" : "do not hold the fields their header claims", status);
+    }
+    ph->ew.swap(ew);
+    ph->rmapq.swap(mq);
+    ph->rok.swap(ok);
+    ph->weighted = true;
+    ph->solved = false;
+    return NC_OK;
+}
+
+int nc_snp_phase_weights(const nc_phase *ph, const uint8_t **entry_weight, const uint8_t **read_mapq, const uint8_t **read_ok)
+{
+    if (!ph) return NC_ERR_ARG;
+    if (entry_weight) *entry_weight = ph->weighted ? ph->ew.data() : nullptr;
+    if (read_mapq) *read_mapq = ph->weighted ? ph->rmapq.data() : nullptr;
+    if (read_ok) *read_ok = ph->weighted ? ph->rok.data() : nullptr;
     return NC_OK;
 }
 

@@ -701,6 +701,7 @@ class DeviceBam:
                 ref_code[max(lo, 0):min(hi, ref_len)] = 4
         dp = DevicePack(codes=codes, tile_off=sec("tile_off"), tile_ent=sec("tile_ent"), ref_code=ref_code, tile_size=prep["tile_size"],
                         tile_pos0=prep["tile_pos0"], n_tiles=prep["n_tiles"], n_entries=prep["n_entries"], pos_lo=prep["pos_lo"], pos_hi=prep["pos_hi"])
+        dp.records = (self, sec("rec"))
         if prep.get("mates") is not None:                                # prepare(by_name=True): the featuriser's table of the shared names (nc_snp_set_mates)
             dp.mates = (sec("mate_key"), sec("mate_rec").view(-1, 4))
         if indel:

@@ -38,6 +38,8 @@ class DevicePack:
     reads: dict | None = None     # device tensors rd_start / rd_end / slot_off of the kept reads (device pass 2: tile entry -> read)
     indel: dict | None = None     # device tensors ins_off / ins_bases / tail_off / tail_bases / read_ps / read_flag (device pass 2)
     mates: tuple | None = None    # (key int64 [M], rec int32 [M, 4]) device tensors: alignments that share read names (nc_snp_set_mates)
+    records: tuple | None = None  # (DeviceBam, int64 device tensor): a pack the device ingest made -- the owner of the inflated record stream and
+                                  # the kept reads' record offsets in it, in pack order (the weighted phaser reads MAPQ and qualities there)
 
     def c_struct(self) -> _lib.ReadPackC:
         return _lib.ReadPackC(codes_len=self.codes.numel(), codes=self.codes.data_ptr(), tile_size=self.tile_size,
@@ -381,7 +383,7 @@ class Engine:
         return probs
 
     def snp_phase(self, site_pos, site_alleles, read_group, n_groups, *, max_cov=15, reads=None, csr=None, realign=None, site_gt=None,
-                  distrust_cost=1) -> dict:
+                  distrust_cost=1, weights=None, bam_quals=None) -> dict:
         """Read-based phasing + haplotags (nc_snp_phase_*, nc_haplotag_run) -> dict of host arrays (see nc_phase_arrays).
         reads: (codes, rd_start, rd_end, slot_off) device tensors of a resident pack's kept reads (alleles gathered on the device);
         csr: (entry_off int64, entry_site int32, entry_allele uint8) host arrays instead;
@@ -389,7 +391,13 @@ class Engine:
         bases, and the contig's reference codes [length] (device uint8, position p at p - 1, 4 = not a base): alleles by local
         realignment (nc_snp_phase_realign).
         site_gt: the called class per site (uint8: 0 het, 1 / 2 homozygous for the first / second allele) -- the genotypes are not trusted
-        (nc_snp_phase_solve_gt with the price `distrust_cost` of leaving a call) and the result gains `site_gt`, the outcome per site."""
+        (nc_snp_phase_solve_gt with the price `distrust_cost` of leaving a call) and the result gains `site_gt`, the outcome per site.
+        The weighted model (an allele's flip costs its weight, reads may be barred from selection), either of
+        weights: (entry_weight uint8 [n_entries] in 0..93, read_ok uint8 [n_reads]) host arrays, either None = all 1 (nc_snp_phase_set_weights);
+        bam_quals: (raw, rec_off, mapq_min, default_weight, w_max) -- the device ingest's inflated record stream (uint8 device tensor), the kept
+        reads' record offsets in the reads' order (int64 device tensor): base qualities capped at w_max as weights, read_ok = MAPQ >= mapq_min
+        (nc_snp_phase_weights_from_bam).
+        The result then gains `entry_weight`, `read_mapq` and `read_ok`."""
         L = self.L
         pos = np.ascontiguousarray(site_pos, np.int32)
         h = C.c_void_p()
@@ -412,6 +420,26 @@ class Engine:
             self._check(L.nc_snp_phase_load(self.ctx, off.size - 1, pos.size, _lib.npp(pos), _lib.npp(off), _lib.npp(site), _lib.npp(allele),
                                             C.byref(h)), "nc_snp_phase_load")
         try:
+            if weights is not None and bam_quals is not None:
+                raise ValueError("snp_phase: weights= and bam_quals= are two sources of the same weights")
+            if weights is not None:
+                ew, ok = (None if a is None else np.ascontiguousarray(a, np.uint8) for a in weights)
+                v = _lib.PhaseArraysC()
+                L.nc_snp_phase_view(h, C.byref(v))
+                if (ew is not None and ew.size != v.n_entries) or (ok is not None and ok.size != v.n_reads):
+                    raise ValueError("snp_phase: weights= holds %s weights / %s flags for %d entries / %d reads"
+                                     % (None if ew is None else ew.size, None if ok is None else ok.size, v.n_entries, v.n_reads))
+                self._check(L.nc_snp_phase_set_weights(self.ctx, h, None if ew is None else _lib.npp(ew), None if ok is None else _lib.npp(ok)),
+                            "nc_snp_phase_set_weights")
+            if bam_quals is not None:
+                raw, rec_off, mapq_min, default_weight, w_max = bam_quals
+                v = _lib.PhaseArraysC()
+                L.nc_snp_phase_view(h, C.byref(v))
+                if rec_off.dtype != torch.int64 or rec_off.numel() != v.n_reads or raw.dtype != torch.uint8:
+                    raise ValueError("snp_phase: bam_quals= needs a uint8 record stream and %d int64 record offsets, one per read" % v.n_reads)
+                torch.cuda.current_stream(self.device).synchronize()
+                self._check(L.nc_snp_phase_weights_from_bam(self.ctx, h, _ptr(raw), int(raw.numel()), _ptr(rec_off), int(mapq_min), int(default_weight),
+                                                            int(w_max)), "nc_snp_phase_weights_from_bam")
             if site_gt is None:
                 self._check(L.nc_snp_phase_solve(self.ctx, h, int(max_cov)), "nc_snp_phase_solve")
             else:
@@ -432,6 +460,10 @@ class Engine:
                 g = C.c_void_p()
                 L.nc_snp_phase_genotypes(h, C.byref(g))
                 extra = dict(site_gt=a(g, S, np.uint8))
+            if weights is not None or bam_quals is not None:
+                pw, pm, po = C.c_void_p(), C.c_void_p(), C.c_void_p()
+                L.nc_snp_phase_weights(h, C.byref(pw), C.byref(pm), C.byref(po))
+                extra.update(entry_weight=a(pw, v.n_entries, np.uint8), read_mapq=a(pm, R, np.uint8), read_ok=a(po, R, np.uint8))
             return dict(entry_off=a(v.entry_off, R + 1, np.int64), entry_site=a(v.entry_site, v.n_entries, np.int32),
                         entry_allele=a(v.entry_allele, v.n_entries, np.uint8), side=a(v.read_side, R, np.int8),
                         site_block=a(v.site_block, S, np.int32), site_h=a(v.site_h, S, np.uint8), site_phased=a(v.site_phased, S, np.uint8).astype(bool),

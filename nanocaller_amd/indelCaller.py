@@ -297,7 +297,10 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
     indel chunks carry chunk['haplotags'] = that file beside chunk['sam_path'] = params['sam_path'].  params['phase_realign'] (or
     NC_PHASE_REALIGN=1 without that key) makes that phaser detect the reads' alleles by local realignment (phase.phase_contig(realign=True));
     params['phase_distrust'] (or NC_PHASE_DISTRUST=1 without that key) lets it change genotypes and take homozygous calls, as `whatshap phase
-    --distrust-genotypes --include-homozygous` does (phase.phase_contig(distrust=True)), and the records that come out 0/0 are dropped."""
+    --distrust-genotypes --include-homozygous` does (phase.phase_contig(distrust=True)), and the records that come out 0/0 are dropped;
+    params['phase_weighted'] (or NC_PHASE_WEIGHTED=1 without that key) makes it weigh every allele by its base quality and leave reads with
+    MAPQ below params['phase_mapq'] (default 20) out of the MEC (phase.phase_contig(weighted=True): the contig must take the device ingest route,
+    anything else raises)."""
     import os
 
     from . import vcfio
@@ -322,10 +325,14 @@ def phase_run(contig_dict, params, indel_dict, job_Q, counter_Q, phased_snp_file
         phased = False
         haplotags = None
         if device_phaser_selected(params):
-            from .phase import phase_contig, phase_distrust_selected, phase_realign_selected, save_haplotags
+            from .phase import phase_contig, phase_distrust_selected, phase_realign_selected, phase_weighted_selected, save_haplotags
             realign = dict(realign=True) if phase_realign_selected(params) else {}      # (off: the call as it always was)
             distrust = dict(distrust=True) if phase_distrust_selected(params) else {}
-            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device, **realign, **distrust)
+            weighted = {}
+            if phase_weighted_selected(params):
+                weighted = dict(weighted=True, **(dict(mapq_min=int(params['phase_mapq'])) if params.get('phase_mapq') is not None else {}))
+            res = phase_contig(sam_path, params['fasta_path'], contig, hi, q, bool(params.get('supplementary')), device=device, **realign, **distrust,
+                               **weighted)
             kept = without_hom_ref(res.records) if distrust else res.records    # -e 'GT="0\\0"' (:239), as on the WhatsHap branch
             vcfio.write_sorted_vcf(out_vcf, _with_phase_format(header), kept, [contig])
             haplotags = os.path.join(phase_dir, '%s.haplotags.npz' % contig)

@@ -9,7 +9,9 @@ when a chunk carries `haplotags` (`TaggedBam`).  Opt-in: params['phaser'] = 'dev
 'phaser' key (`device_phaser_selected`).  Behind it, params['phase_realign'] / NC_PHASE_REALIGN=1 (`phase_realign_selected`) selects the
 alleles by local realignment (WhatsHap's `--reference` mode restated) instead of the pileup column's code; params['phase_distrust'] /
 NC_PHASE_DISTRUST=1 (`phase_distrust_selected`) lets the phaser change genotypes and take homozygous calls (WhatsHap's `--distrust-genotypes
---include-homozygous` restated: `phase_contig(distrust=True)`).
+--include-homozygous` restated: `phase_contig(distrust=True)`); params['phase_weighted'] / NC_PHASE_WEIGHTED=1 (`phase_weighted_selected`) weighs every
+allele by its base quality and leaves reads below a MAPQ floor out of the MEC (WhatsHap's weighted MEC restated: `phase_contig(weighted=True)`;
+the qualities and MAPQs are read from the device ingest's record stream, so the contig has to take that route).
 """
 from __future__ import annotations
 
@@ -54,6 +56,14 @@ def phase_distrust_selected(params) -> bool:
     if "phase_distrust" in params:
         return bool(params["phase_distrust"])
     return os.environ.get("NC_PHASE_DISTRUST") == "1"
+
+
+def phase_weighted_selected(params) -> bool:
+    """params['phase_weighted'] truthy; without that key, the environment's NC_PHASE_WEIGHTED == '1' (the device phaser weighs alleles by base
+    quality and keeps reads below the MAPQ floor params['phase_mapq'] (default 20) out of the MEC: `phase_contig(weighted=True)`)"""
+    if "phase_weighted" in params:
+        return bool(params["phase_weighted"])
+    return os.environ.get("NC_PHASE_WEIGHTED") == "1"
 
 
 def name_hash(names) -> np.ndarray:
@@ -203,20 +213,51 @@ def _realign_inputs(sam_path, fasta_path, chrom, supplementary, device):
     return dp, (dp.codes, reads_c, dp.events["ev_pos"].numel(), ix["ins_bases"].numel(), ctg[key])
 
 
+def _ingest_records(sam_path, fasta_path, chrom, supplementary, device):
+    """the contig's pack as the device ingest makes it, with the record stream it was made from -> (pack, (raw uint8 device tensor, the kept
+    reads' record offsets in pack order)).  The weighted model reads MAPQ and base qualities there and nowhere else: an input that does not take
+    that route is refused, unit costs are not substituted."""
+    from . import _lib
+    from . import generate_indel_pileups as gip
+    why = None
+    if not (isinstance(sam_path, str) and os.path.exists(sam_path)) or not fasta_path:
+        why = "the alignments %r are not a BAM file with its FASTA (a World or a registered key carries no record bytes)" % (sam_path,)
+    else:
+        di = gip._device_ingest_contig(dict(fasta_path=fasta_path, supplementary=bool(supplementary)), sam_path, chrom, bool(supplementary), device)
+        if di is None:
+            why = ("%s does not take the device ingest route (NC_DEVICE_INGEST=0, no .bai / .csi beside it, or too large for HBM)" % sam_path)
+        elif getattr(di[0], "records", None) is None:
+            why = "the pack of %s, contig %s, does not carry its record stream" % (sam_path, chrom)
+    if why:
+        raise _lib.NanoCallerHipError("phase_contig(weighted=True): %s; MAPQ and base qualities exist only in the device ingest's record stream "
+                                      "(unit costs are not substituted)" % why)
+    dbam, rec_off = di[0].records
+    return di[0], (dbam.raw[:dbam.raw_len], rec_off)
+
+
 def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, supplementary=False, max_cov=15, device=0, realign=False, distrust=False,
-                 distrust_cost=1) -> PhaseResult:
+                 distrust_cost=None, weighted=False, mapq_min=20, default_weight=30, w_max=93) -> PhaseResult:
     """Phase the het SNP calls `snp_records` (VCF lines of contig `chrom`) from the reads of `sam_path` (a BAM path, a World or a
     registered key) and haplotag the reads.  -> PhaseResult
     realign: a read's allele at a site comes from a local realignment of its bases against the reference window with either allele (DESIGN.md
     "Read-based phasing", the allele detectors) instead of the code in the site's column; needs a BAM file (the reads' inserted bases).
     distrust: the genotypes are not trusted (DESIGN.md "Read-based phasing", step 6b): the sites are `distrust_sites`', a site may come out het or
-    homozygous for either allele, leaving its call costs `distrust_cost` allele errors, and the records' GT follow the outcome."""
+    homozygous for either allele, leaving its call costs `distrust_cost` allele errors (default 1; in weighted mode `default_weight`, one
+    allele of default quality), and the records' GT follow the outcome.
+    weighted: the weighted model (DESIGN.md "Read-based phasing", step 6c): an allele's flip costs min(its base quality, w_max) -- `default_weight`
+    where the record has no quality --, reads with MAPQ < `mapq_min` are left out of the MEC and still tagged.  The qualities come from the device
+    ingest's record stream: a World, a registered key, NC_DEVICE_INGEST=0 or a BAM without index raises NanoCallerHipError."""
     import torch
 
     from .engine import get_engine
     from .generate_SNP_pileups import _resolve, device_pack
     eng = get_engine(device)
     eng.use_torch_stream()
+    wdp = quals = None
+    if weighted:
+        wdp, quals = _ingest_records(sam_path, fasta_path, chrom, supplementary, device)
+    if distrust_cost is None:
+        distrust_cost = max(1, int(default_weight)) if weighted else 1
     if distrust:
         rec_idx, pos, alleles, kind, gt_in = distrust_sites(snp_records, phase_qual_score)
         solve = dict(site_gt=gt_in, distrust_cost=distrust_cost)
@@ -228,7 +269,11 @@ def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, sup
         dp, ra = _realign_inputs(sam_path, fasta_path, chrom, supplementary, device)
     world = _resolve(sam_path, chrom, fasta_path)
     if not realign:
-        dp = device_pack(sam_path, fasta_path, chrom, bool(supplementary), None, device, by_name=True)[0]
+        dp = wdp if weighted else device_pack(sam_path, fasta_path, chrom, bool(supplementary), None, device, by_name=True)[0]
+    if weighted:
+        if dp is not wdp:
+            raise RuntimeError("phase_contig: the alleles and the qualities come from two packs")
+        solve = dict(solve, bam_quals=quals + (int(mapq_min), int(default_weight), int(w_max)))
     kept, rs, re_, slot = kept_reads(world, supplementary)
     if dp.reads is not None:
         if dp.reads["n_reads"] != kept.size:
@@ -269,6 +314,8 @@ def phase_contig(sam_path, fasta_path, chrom, snp_records, phase_qual_score, sup
     sites = dict(pos=pos, record=rec_idx, h=r["site_h"], phased=r["site_phased"], ps=r["site_ps"], block=r["site_block"], gt_in=gt_in, gt_out=gt_out)
     reads_out = dict(index=kept, hash=hashes, group=group, side=r["side"], hp=r["group_hp"][group], ps=r["group_ps"][group],
                      entry_off=r["entry_off"], entry_site=r["entry_site"], entry_allele=r["entry_allele"])
+    if weighted:
+        reads_out.update(entry_weight=r["entry_weight"], mapq=r["read_mapq"], ok=r["read_ok"])
     return PhaseResult(records=out, blocks=blocks, haplotags=tags, sites=sites, reads=reads_out, ms=r["ms"])
 
 

@@ -2,8 +2,10 @@
 allele gather, read selection + blocks + slots (host), the MEC DP, haplotagging.  The het sites are the generator's own (its truth,
 recomputed from the same seed); every read is its own name.  --realign: the alleles by local realignment (nc_snp_phase_realign) instead of
 the column gather.  --distrust N: the genotype-aware DP (nc_snp_phase_solve_gt) against the plain one on the same het-only site list, and on the
-list with the homozygous SNP sites added as 1/1 calls.  Prints one JSON line.
-Usage: python tools/bench_phase.py [--length L] [--reps N] [--realign | --compare N | --distrust N] [--out FILE]"""
+list with the homozygous SNP sites added as 1/1 calls.  --weighted N: the weighted DP (nc_snp_phase_set_weights: ONT-like qualities drawn per
+entry, capped at --w-max, every read allowed) against the plain one on the same entries, interleaved; then whether the contig still solves inside
+the DP's 16-bit relative range when EVERY entry weighs --w-max, and if not the largest uniform weight that does.  Prints one JSON line.
+Usage: python tools/bench_phase.py [--length L] [--reps N] [--realign | --compare N | --distrust N | --weighted N] [--w-max W] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -30,7 +32,10 @@ def main():
     ap.add_argument("--distrust", type=int, default=0, help="N interleaved runs of the plain solve, the genotype-aware solve on the same het-only sites, "
                     "and the genotype-aware solve with the homozygous sites added: medians, and the DP's ratio to the plain form")
     ap.add_argument("--distrust-cost", type=int, default=1)
-    ap.add_argument("--out", default=None, help="with --distrust: also write the JSON to this file")
+    ap.add_argument("--weighted", type=int, default=0, help="N interleaved runs of the plain solve and of the weighted solve on the same entries: medians, "
+                    "the DP's ratio to the plain form, and the capacity check at --w-max")
+    ap.add_argument("--w-max", type=int, default=93)
+    ap.add_argument("--out", default=None, help="with --distrust / --weighted: also write the JSON to this file")
     a = ap.parse_args()
     eng = get_engine(0)
     eng.use_torch_stream()
@@ -88,6 +93,53 @@ def main():
                           stage_ms={s_: round(med([m[s_] for m in stages[k]]), 3) for s_ in stages[k][0]})
             if "site_gt" in res:
                 out[k]["outcomes_left_call"] = int((res["site_gt"] != forms[k][2]["site_gt"]).sum())
+        print(json.dumps(out))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
+    if a.weighted:
+        from nanocaller_amd import _lib
+        first = eng.snp_phase(het, alleles, group, R, reads=reads)       # (warm; and the number of entries the weights are drawn for)
+        ne = int(first["entry_site"].size)
+        rng = np.random.default_rng(a.seed)
+        # ONT-like base qualities: a gamma body around Q20 with a tail, a seventh of the bases low (Q1-7)
+        q = np.clip(rng.gamma(5.0, 4.0, ne), 1, 93)
+        low = rng.random(ne) < 1 / 7
+        q[low] = rng.integers(1, 8, int(low.sum()))
+        q = np.minimum(q.astype(np.uint8), a.w_max).astype(np.uint8)
+        forms = dict(plain={}, weighted=dict(weights=(q, None)))
+        walls, stages, last = {k: [] for k in forms}, {k: [] for k in forms}, {}
+        for _ in range(a.weighted):
+            for k, kw_ in forms.items():
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                last[k] = eng.snp_phase(het, alleles, group, R, reads=reads, **kw_)
+                walls[k].append(time.perf_counter() - t)
+                stages[k].append(last[k]["ms"])
+        med = lambda v: float(np.median(v))                              # noqa: E731
+        dp = {k: [m["dp"] for m in stages[k]] for k in forms}
+        out = dict(metric="phase_chr20_sized_weighted_dp_over_plain", value=round(med(dp["weighted"]) / med(dp["plain"]), 4), length=L, depth=a.depth, reads=R,
+                   het_sites=int(het.size), entries=ne, w_max=a.w_max, runs=a.weighted, mean_weight=round(float(q.mean()), 2),
+                   plain_dp_ms=[round(x, 2) for x in dp["plain"]], weighted_dp_ms=[round(x, 2) for x in dp["weighted"]])
+        for k in forms:
+            res = last[k]
+            out[k] = dict(wall_s=round(med(walls[k]), 4), walls_s=[round(x, 4) for x in walls[k]], phased_sites=int(res["site_phased"].sum()),
+                          blocks=int(res["block_first"].size), mec_cost=int(res["block_cost"].sum()), tagged_reads=int((res["group_hp"] > 0).sum()),
+                          stage_ms={s_: round(med([m[s_] for m in stages[k]]), 3) for s_ in stages[k][0]})
+        out["sites_whose_h_differs"] = int((last["plain"]["site_h"] != last["weighted"]["site_h"]).sum())
+        # capacity: the worst case of a cap is every entry AT the cap (the relative costs scale with it)
+        solved = {}
+        for v in [a.w_max] + [x for x in (80, 64, 48, 40, 32, 24, 16, 8) if x < a.w_max]:
+            try:
+                eng.snp_phase(het, alleles, group, R, reads=reads, weights=(np.full(ne, v, np.uint8), None))
+                solved[v] = True
+                break
+            except _lib.NanoCallerHipError as e:
+                if "(%d)" % _lib.NC_ERR_CAPACITY not in str(e):
+                    raise
+                solved[v] = False
+        out["uniform_weight_solves"] = {str(k): v for k, v in solved.items()}
         print(json.dumps(out))
         if a.out:
             with open(a.out, "w") as f:
