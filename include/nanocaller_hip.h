@@ -941,6 +941,46 @@ int nc_fasta_decode(nc_ctx *ctx, const uint8_t *d_raw, int64_t raw_len, int64_t 
                     uint8_t *d_letters, uint8_t *d_scan, int64_t scan_pos0, int64_t scan_len, int64_t ga, int64_t gb, uint8_t *d_blind,
                     int32_t *d_status);
 
+/* Indexing a BAM on the device (csrc/nc_bamindex.hip; device_bam.build_index): record boundaries of a piece of the inflated record stream
+ * WITHOUT chain starts, and the per-record fields a .bai / .csi is assembled from.  d_raw[0, len) = the piece (dev, 16-byte aligned, readable up
+ * to `readable` >= len + 16), `first` = offset of a record start in it.  A record is "whole" when its 4 + block_size bytes lie inside the piece;
+ * the chain leaves the piece at the first record start that is not whole (the carry into the next piece, which begins with those bytes).
+ * nc_bamidx_candidates: one bit per byte position that holds a plausible whole record (block_size >= 32; refID, next_refID in [-1, n_ref); pos in
+ *   [-1, d_ref_len[refID]); l_read_name >= 1 with its NUL; l_seq >= 0; the fixed fields, name, CIGAR, bases and qualities inside block_size):
+ *   d_words [ceil(len / 4096) * 64] (bit b of word w = position 64 w + b), d_cnt [the same] = the words' population counts.
+ * nc_bamidx_chain: d_rank = exclusive prefix sums of d_cnt, n_cand = their total.  d_pos [n_cand] = the candidates' positions, ascending;
+ *   d_mark [n_cand + 1] = 1 for the candidates reached from `first` over block_size links that end on candidates (pointer doubling: log2
+ *   n_cand rounds); d_jump [2 (n_cand + 1)] workspace.
+ * nc_bamidx_collect: d_mark_rank = inclusive prefix sums of d_mark: d_out [their total] = the marked positions, ascending.
+ * nc_bamidx_verify: the proof that d_out [n_rec] is the serial chain p -> p + 4 + block_size from `first` through every whole record of the
+ *   piece.  d_res (3 x int64, written here): [0] bit 0 = not proved (the caller then runs nc_bamidx_serial), else NC_BAMIDX_* bits; [1] = the
+ *   carry.  last != 0: the piece ends the file, a carry other than len is NC_BAMIDX_TRUNCATED.
+ * nc_bamidx_serial: the serial chain itself on one lane.  d_out NULL: count only.  d_res: [0] NC_BAMIDX_* bits, [1] the carry, [2] records.
+ * nc_bamidx_fields: per record r of d_rec_off [n_rec] (offsets in d_raw; d_meta = nc_bam_meta's table of them): d_voff [2][n_rec] = virtual
+ *   offsets of its first byte and of the byte behind it, from the members d_mem_ooff / d_mem_foff [n_mem + 1] (offset of each member's first
+ *   byte in the whole inflated stream and in the file; entry n_mem = the end of both) with d_raw[0] at stream offset stream_base; a position on
+ *   a member boundary belongs to the member that starts there.  d_fields [3][n_rec] = bin (hts-specs reg2bin for min_shift / depth) and the
+ *   0-based span [beg, end) it is indexed under (one base for an unmapped or span-less record).  d_status collects NC_BAMIDX_BAD_REFID,
+ *   NC_BAMIDX_UNSORTED (against the record before; has_prev: prev_refid / prev_pos = the last record of the piece before) and
+ *   NC_BAMIDX_BAD_MEMBERS (a record outside the member table).
+ * All run on the context's stream; none waits. */
+#define NC_BAMIDX_BAD_BLOCK_SIZE 2   /* a block_size below 32 on the chain */
+#define NC_BAMIDX_BAD_FIELDS 4       /* nc_bam_meta: a record whose fields overrun its block_size */
+#define NC_BAMIDX_TRUNCATED 8        /* the chain does not end where the data ends */
+#define NC_BAMIDX_BAD_REFID 16       /* a refID outside the header's reference list, or a pos below -1 */
+#define NC_BAMIDX_UNSORTED 32        /* not coordinate-sorted */
+#define NC_BAMIDX_BAD_MEMBERS 64     /* a record outside the member table */
+int nc_bamidx_candidates(nc_ctx *ctx, const uint8_t *d_raw, int64_t len, int64_t readable, int32_t n_ref, const int32_t *d_ref_len, uint64_t *d_words,
+                         int32_t *d_cnt);
+int nc_bamidx_chain(nc_ctx *ctx, const uint8_t *d_raw, int64_t len, int64_t first, const uint64_t *d_words, const int32_t *d_rank, int32_t n_cand,
+                    int64_t *d_pos, int32_t *d_jump, int32_t *d_mark);
+int nc_bamidx_collect(nc_ctx *ctx, int32_t n_cand, const int64_t *d_pos, const int32_t *d_mark, const int32_t *d_mark_rank, int64_t *d_out);
+int nc_bamidx_verify(nc_ctx *ctx, const uint8_t *d_raw, int64_t len, int64_t first, int64_t n_rec, const int64_t *d_out, int32_t last, int64_t *d_res);
+int nc_bamidx_serial(nc_ctx *ctx, const uint8_t *d_raw, int64_t len, int64_t first, int32_t last, int64_t *d_out, int64_t *d_res);
+int nc_bamidx_fields(nc_ctx *ctx, const uint8_t *d_raw, int64_t n_rec, const int64_t *d_rec_off, int64_t stream_base, const int32_t *d_meta, int32_t n_ref,
+                     int32_t n_mem, const int64_t *d_mem_ooff, const int64_t *d_mem_foff, int32_t has_prev, int32_t prev_refid, int32_t prev_pos,
+                     int32_t min_shift, int32_t depth, int64_t *d_voff, int32_t *d_fields, int32_t *d_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,7 @@ EXPORTS = [
     "nc_snp_phase_set_weights", "nc_snp_phase_weights_from_bam", "nc_snp_phase_weights",
     "nc_bam_retag_sizes", "nc_bam_retag", "nc_bgzf_deflate_device", "nc_bgzf_crc32_device", "nc_bgzf_assemble_device",
     "nc_fasta_decode",
+    "nc_bamidx_candidates", "nc_bamidx_chain", "nc_bamidx_collect", "nc_bamidx_verify", "nc_bamidx_serial", "nc_bamidx_fields",
 ]
 
 
@@ -279,6 +280,12 @@ def lib():
         L.nc_bgzf_crc32_device.argtypes = [vp, i32, vp, vp, vp, vp]
         L.nc_bgzf_assemble_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.nc_fasta_decode.argtypes = [vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, i64, vp, vp]
+        L.nc_bamidx_candidates.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp]
+        L.nc_bamidx_chain.argtypes = [vp, vp, i64, i64, vp, vp, i32, vp, vp, vp]
+        L.nc_bamidx_collect.argtypes = [vp, i32, vp, vp, vp, vp]
+        L.nc_bamidx_verify.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp]
+        L.nc_bamidx_serial.argtypes = [vp, vp, i64, i64, i32, vp, vp]
+        L.nc_bamidx_fields.argtypes = [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

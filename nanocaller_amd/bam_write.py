@@ -248,9 +248,10 @@ def write_haplotagged_bam(sam_path, chrom, haplotags, out_path, start=None, end=
     in `haplotags` (phase.save_haplotags' table: a path or a dict), HP and PS appended.  -> dict of counts and milliseconds per stage"""
     import torch
 
-    from .device_bam import M_POS, M_RLEN, DeviceIngestUnavailable, open_device_bam
+    from .device_bam import M_POS, M_RLEN, DeviceIngestUnavailable, ensure_index, open_device_bam
     t_all = time.perf_counter()
     ms = {}
+    ensure_index(sam_path, None, device)                                # (NC_BUILD_INDEX=1: an input without index gets one)
     try:
         db = open_device_bam(sam_path, device, contigs=[chrom])
     except DeviceIngestUnavailable as e:

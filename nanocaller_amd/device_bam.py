@@ -12,6 +12,7 @@ Which reads the pileup keeps (flag filter, htslib's depth cap, the unsupported-i
 from the per-record fields with the same functions the host route uses, so a `DevicePack` made here is byte for byte the one
 `wire.upload_wire(build_wire_from_world(bam.read_bam(...)))` makes (tests/test_device_bam.py); `pack(indel=True)` adds the indel path's sections.
 Needs an index beside the file: a .bai's linear index, or a .csi's bin offsets and chunk begins, cut the record chain into independent walks.
+A file without one is indexed here, on the GPU, by `build_index` (bam_index.py) -- the callers do so when asked (`ensure_index`).
 """
 from __future__ import annotations
 
@@ -226,7 +227,7 @@ class DeviceBam:
             names.append(buf()[o + 4:o + 4 + l_name - 1].decode("ascii"))
             lengths.append(struct.unpack_from("<i", buf(), o + 4 + l_name)[0])
             o += 8 + l_name
-        self.ref_names, self.ref_lengths = names, lengths
+        self.ref_names, self.ref_lengths, self.header_len = names, lengths, o   # (header_len: where the first record starts in the inflated stream)
         return True
 
     def voffset_to_stream(self, voff):
@@ -781,6 +782,42 @@ def plan_shares(path, contigs, limit_bytes=None, device=None):
     if cur:
         shares.append((cur, True))
     return shares
+
+
+def build_index(path, fmt=None, device=0, piece_bytes=None):
+    """Index the coordinate-sorted BAM `path` on the GPU and write <path>.bai (fmt='csi', or a reference longer than 2^29: <path>.csi) beside
+    it -> the index's path.  The file streams through HBM in pieces of whole BGZF members (`piece_bytes` of compressed bytes each), so its size
+    does not matter; an unsorted or corrupt file raises NanoCallerHipError (bam_index.py)."""
+    from .bam_index import build_index as _build
+    return _build(path, fmt=fmt, device=device, piece_bytes=piece_bytes)
+
+
+def build_index_selected(params=None) -> bool:
+    """params['build_index'] truthy; without that key, the environment's NC_BUILD_INDEX == '1': a BAM without index is indexed once
+    (build_index) instead of taking the host route"""
+    if params is not None and "build_index" in params:
+        return bool(params["build_index"])
+    return os.environ.get("NC_BUILD_INDEX") == "1"
+
+
+def ensure_index(path, params=None, device=0, collective=False):
+    """the opt-in of the callers: a BAM file without index gets one when build_index_selected(params).  collective: every rank of a
+    torch.distributed run calls this at the same point -- rank 0 builds, the others wait at shard.barrier().  Without the opt-in, or for
+    an input that is no file, nothing happens."""
+    if not (isinstance(path, str) and os.path.exists(path)) or not build_index_selected(params):
+        return None
+    rank0 = True
+    if collective:
+        import torch.distributed as dist
+        rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+    try:
+        if _bai_path(path) is None and rank0:
+            build_index(path, device=device)
+    finally:
+        if collective:
+            from . import shard
+            shard.barrier()
+    return _bai_path(path)
 
 
 _OPEN = {}

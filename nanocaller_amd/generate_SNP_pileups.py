@@ -215,7 +215,8 @@ def device_ingest_pack(dct, chrom, device=0, span=None):
     sam_path, fasta_path = dct["sam_path"], dct.get("fasta_path")
     if not dct.get("device_ingest") or not isinstance(sam_path, str) or sam_path in _SOURCES or not os.path.exists(sam_path) or not fasta_path:
         return None
-    from .device_bam import DeviceIngestUnavailable, open_device_bam
+    from .device_bam import DeviceIngestUnavailable, ensure_index, open_device_bam
+    ensure_index(sam_path, dct, device)                                  # (dct['build_index'] / NC_BUILD_INDEX=1: a BAM without index gets one)
     try:
         dbam = open_device_bam(sam_path, device, contigs=[chrom])
     except DeviceIngestUnavailable:

@@ -718,16 +718,17 @@ _DEV_INGEST = {}              # one contig at a time: (BAM, contig, FASTA, flag 
 def _device_ingest_contig(dct, sam_path, chrom, supp, device, by_name=False):
     """The contig's read pack WITH the indel sections, made on the device from the BAM file itself (device_bam.py: inflate, record walk, codes,
     events, inserted bases and tails in HBM) -- what decoded_contig + device_pack + device_indel_reads assemble on host threads.  None when the
-    input cannot take that route (no .bai, too large, NC_DEVICE_INGEST=0 / dct['device_ingest'] = False): the host route follows."""
+    input cannot take that route (no .bai and no dct['build_index'] / NC_BUILD_INDEX=1 to make one, too large, NC_DEVICE_INGEST=0 / dct['device_ingest'] = False): the host route follows."""
     if not dct.get("device_ingest", os.environ.get("NC_DEVICE_INGEST", "1") != "0") or not isinstance(sam_path, str) or not os.path.exists(sam_path):
         return None
     st = os.stat(sam_path)
     key = (sam_path, chrom, dct["fasta_path"], supp, device, bool(by_name), st.st_size, st.st_mtime_ns)
     if key not in _DEV_INGEST:
-        from .device_bam import DeviceIngestUnavailable, open_device_bam
+        from .device_bam import DeviceIngestUnavailable, ensure_index, open_device_bam
         from .device_fasta import reference_for
         from .wire import indel_reads_struct
         _DEV_INGEST.clear()
+        ensure_index(sam_path, dct, device)                              # (dct['build_index'] / NC_BUILD_INDEX=1: a BAM without index gets one)
         try:
             dbam = open_device_bam(sam_path, device, contigs=[chrom])
         except DeviceIngestUnavailable:

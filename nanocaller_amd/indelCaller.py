@@ -434,6 +434,8 @@ def call_manager(params, devices=None, aligner=None):
     if world > 1:
         from .numa import bind_rank
         bind_rank(device)
+    from .device_bam import ensure_index
+    ensure_index(params.get('sam_path'), params, device, collective=True)      # opt-in: rank 0 indexes a BAM that has no index, the others wait
     mode = params['mode']
     contigs_list = {}
     for x in params['regions_list']:                                           # :299-305

@@ -416,8 +416,9 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
         # (alignments that share a read name -- a split read's records under dct['supplementary'], paired mates -- are keyed by NAME on both routes:
         # pack.name_groups, fed by nc_decoded_name_groups on the host route and by nc_bam_name_groups here)
         if piped and keys and params.get('device_ingest', os.environ.get('NC_DEVICE_INGEST', '1') != '0') and params.get('fasta_path'):
-            from .device_bam import DeviceIngestUnavailable, open_device_bam, plan_shares
+            from .device_bam import DeviceIngestUnavailable, ensure_index, open_device_bam, plan_shares
             from .device_fasta import reference_for
+            ensure_index(params['sam_path'], params, device)             # (params['build_index'] / NC_BUILD_INDEX=1: a BAM without index gets one)
             try:
                 lim = os.environ.get('NC_DEVICE_INGEST_SHARE_GB')
                 order = list(dict.fromkeys(k[0] for k in keys))
@@ -549,6 +550,8 @@ def call_manager(params, devices=None):
     chunks_Q = queue.Queue()
     counter_Q = queue.Queue()
     snp_files = []
+    from .device_bam import ensure_index
+    ensure_index(params.get('sam_path'), params, local_device(devices, rank), collective=True)   # opt-in: rank 0 indexes a BAM that has no index, the others wait
     wts = shard.depth_weights(params.get('sam_path'), params['chunks_list']) if world > 1 else None      # balance by the alignments held
     for chunk in shard.shard_chunks(params['chunks_list'], rank, world, wts):
         chunks_Q.put(chunk)
