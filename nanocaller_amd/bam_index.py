@@ -4,7 +4,7 @@
   file, piece by piece of whole BGZF members --H2D--> nc_inflate_device + nc_bgzf_crc_device --> the record stream of the piece, behind the
   bytes of the record the piece before ended in --nc_bamidx_candidates / _chain / _collect / _verify--> record offsets (proved; else
   nc_bamidx_serial) --nc_bam_meta + nc_bamidx_fields--> refID, span, bin, virtual offsets, sort check --D2H (36 B per record)-->
-  [host, numpy: bins with chunks, linear index, pseudo-bins] --> .bai, or .csi compressed on the device
+  [host, numpy, hts_index.index_bytes: bins with chunks, linear index, pseudo-bins] --> .bai, or .csi compressed on the device
 
 Between pieces travel the chain's carry (the offset of the first record that is not whole yet; its bytes are copied in front of the next piece)
 and the sort state (refID and pos of the last record).  Nothing else is kept in HBM, so the size of the file does not matter.
@@ -13,12 +13,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import struct
 import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bgzf
+from .hts_index import index_bytes           # (the writer of both formats; importable from here as before)
 
 BAI_MAX_LEN = 1 << 29            # the longest reference a .bai (min_shift 14, depth 5) can address
 MIN_SHIFT = 14
@@ -88,125 +88,23 @@ def chain_piece(eng, d_buf, length, first, n_ref, d_ref_len, last=False, stats=N
     return out, n_rec, int(r[1]), int(r[0]) & ~1
 
 
-def _inflate_piece(eng, comp, coff, clen, isize, d_buf, out_off):
-    """the members of the compressed bytes `comp` (numpy) -> d_buf[out_off:], CRC-32s checked; -> number of bad members"""
+def _inflate_piece(eng, comp, coff, clen, isize, ooff, d_buf, out_off):
+    """the members of the compressed bytes `comp` (numpy; ooff: bgzf.member_table's inflated offsets) -> d_buf[out_off:], CRC-32s checked;
+    -> status per member"""
     import torch
-    from .device_bam import CHECK_CRC, _work_buffer
-    L, dev = _lib.lib(), eng.device
-    n = int(coff.size)
+    dev = eng.device
     padded = np.zeros(comp.size + 64, np.uint8)
     padded[:comp.size] = comp
     d_comp = torch.from_numpy(padded).to(dev)
-    ooff = np.zeros(n, np.int64)
-    np.cumsum(isize[:-1], out=ooff[1:])
-    ooff += out_off
-    d64 = torch.from_numpy(np.concatenate([coff.astype(np.int64), ooff])).to(dev)
-    d32 = torch.from_numpy(np.concatenate([clen.astype(np.int32), isize.astype(np.int32)])).to(dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    batch = min(INFLATE_BATCH, (n + 63) // 64 * 64)
-    d_tok = _work_buffer(dev, "idx_tok", ((batch + 63) // 64) << 22, torch.int32)
-    d_ntok = torch.zeros(batch, dtype=torch.int32, device=dev)
-    for a in range(0, n, batch):
-        k = min(batch, n - a)
-        args = (k, _vp(d_comp), _vp(d64, 8 * a), _vp(d32, 4 * a), _vp(d_buf), _vp(d64, 8 * (n + a)), _vp(d32, 4 * (n + a)), _vp(status, 4 * a))
-        eng._check(L.nc_inflate_device(eng.ctx, *args, _vp(d_tok), _vp(d_ntok)), "nc_inflate_device")
-        if CHECK_CRC:
-            eng._check(L.nc_bgzf_crc_device(eng.ctx, *args), "nc_bgzf_crc_device")
-    return status
-
-
-# ------------------------------------------------------------------------------------------------------------ host: the index from the records' arrays
-def _ref_runs(refid, n_ref):
-    """[a, b) of every reference's records in the (sorted) record list, and the number of unplaced ones"""
-    key = np.where(refid < 0, n_ref, refid).astype(np.int64)
-    edges = np.searchsorted(key, np.arange(n_ref + 1))
-    return edges, int(refid.size - edges[n_ref])
-
-
-def _ref_tables(beg, end, bins, vbeg, vend, min_shift):
-    """one reference: (bin ids ascending, first chunk of each, chunk counts, chunk begins, chunk ends, linear index with the empty windows
-    still at the uint64 maximum)"""
-    w0, w1 = beg >> min_shift, (end - 1) >> min_shift
-    n_win = int(w1.max()) + 1
-    big = np.uint64(np.iinfo(np.uint64).max)
-    lin = np.full(n_win, big, np.uint64)
-    cnt = w1 - w0 + 1
-    rows = np.repeat(np.arange(beg.size), cnt)
-    win = w0[rows] + (np.arange(rows.size) - np.repeat(np.cumsum(cnt) - cnt, cnt))
-    np.minimum.at(lin, win, vbeg[rows])
-    o = np.argsort(bins, kind="stable")                                  # the records of a bin in file order; adjacent ones form one chunk
-    sb, svb, sve = bins[o], vbeg[o], vend[o]
-    new = np.ones(sb.size, bool)
-    new[1:] = (sb[1:] != sb[:-1]) | (svb[1:] != sve[:-1])
-    starts = np.flatnonzero(new)
-    ends = np.concatenate([starts[1:], [sb.size]]) - 1
-    ub, first = np.unique(sb[starts], return_index=True)
-    n_ch = np.diff(np.concatenate([first, [starts.size]]))
-    return ub, first, n_ch, svb[starts], sve[ends], lin
-
-
-def _chunks_blob(cb, ce):
-    c = np.empty(2 * cb.size, np.uint64)
-    c[0::2], c[1::2] = cb, ce
-    return c.astype("<u8").tobytes()
-
-
-def index_bytes(fmt, n_ref, refid, beg, end, unmapped, bins, vbeg, vend, min_shift=MIN_SHIFT, depth=5) -> bytes:
-    """the .bai (SAMv1 5.2) or the uncompressed .csi (hts-specs CSIv1, no auxiliary data) of a coordinate-sorted BAM from its records' arrays
-    in file order: refID, the 0-based span [beg, end) each is indexed under, flag & 4, bin, virtual offsets of its first byte and of the byte
-    behind it.  Per reference: the bins with their chunks, the pseudo-bin (virtual offsets of the reference's first and behind its last record;
-    mapped and unmapped counts), and -- .bai -- the linear index, an empty window taking the offset of the window before it as samtools writes
-    it, or -- .csi -- every bin's loffset = the linear index at the bin's first window, an empty one taking the next one's."""
-    from .bam_write import _bin_first_window
-    refid, beg, end = np.asarray(refid, np.int64), np.asarray(beg, np.int64), np.asarray(end, np.int64)
-    vbeg, vend, bins = np.asarray(vbeg, np.uint64), np.asarray(vend, np.uint64), np.asarray(bins, np.int64)
-    unmapped = np.asarray(unmapped, bool)
-    bai = fmt == "bai"
-    out = [b"BAI\1" + struct.pack("<i", n_ref)] if bai else [b"CSI\1", struct.pack("<3i", min_shift, depth, 0), struct.pack("<i", n_ref)]
-    meta_bin = ((1 << (depth * 3 + 3)) - 1) // 7 + 1
-    big = np.uint64(np.iinfo(np.uint64).max)
-    edges, n_no_coor = _ref_runs(refid, n_ref)
-    for r in range(n_ref):
-        a, b = int(edges[r]), int(edges[r + 1])
-        if a == b:
-            out.append(struct.pack("<ii", 0, 0) if bai else struct.pack("<i", 0))
-            continue
-        ub, first, n_ch, cb, ce, lin = _ref_tables(beg[a:b], end[a:b], bins[a:b], vbeg[a:b], vend[a:b], min_shift)
-        n_win = lin.size
-        if bai:
-            idx = np.where(lin != big, np.arange(n_win), -1)
-            idx = np.maximum.accumulate(idx)
-            lin_out = np.where(idx >= 0, lin[np.maximum(idx, 0)], np.uint64(0))
-            loff = None
-        else:
-            idx = np.where(lin != big, np.arange(n_win), n_win)
-            idx = np.minimum.accumulate(idx[::-1])[::-1]
-            filled = np.concatenate([lin, [np.uint64(0)]])[idx]
-            wdx = _bin_first_window(ub, depth)
-            loff = np.where(wdx < n_win, filled[np.minimum(wdx, n_win - 1)], np.uint64(0))
-        blob = [struct.pack("<i", ub.size + 1)]
-        for k in range(ub.size):
-            s = int(first[k])
-            head = struct.pack("<Ii", int(ub[k]), int(n_ch[k])) if bai else struct.pack("<IQi", int(ub[k]), int(loff[k]), int(n_ch[k]))
-            blob.append(head + _chunks_blob(cb[s:s + n_ch[k]], ce[s:s + n_ch[k]]))
-        n_un = int(np.count_nonzero(unmapped[a:b]))
-        pseudo = struct.pack("<QQQQ", int(vbeg[a:b].min()), int(vend[a:b].max()), b - a - n_un, n_un)
-        blob.append((struct.pack("<Ii", meta_bin, 2) if bai else struct.pack("<IQi", meta_bin, 0, 2)) + pseudo)
-        if bai:
-            blob.append(struct.pack("<i", n_win) + lin_out.astype("<u8").tobytes())
-        out.append(b"".join(blob))
-    out.append(struct.pack("<Q", n_no_coor))
-    return b"".join(out)
+    d64 = torch.from_numpy(np.concatenate([coff, ooff[:-1] + out_off])).to(dev)
+    d32 = torch.from_numpy(np.concatenate([clen, isize])).to(dev)
+    return bgzf.inflate_members(eng, d_comp, d64, d32, int(coff.size), d_buf, INFLATE_BATCH, "idx_tok")
 
 
 # ------------------------------------------------------------------------------------------------------------ the file
 def read_header(path):
     """(reference names, reference lengths, offset of the first record in the inflated stream) of a BAM file; the header may span many members"""
-    from .device_bam import DeviceBam
-    probe = DeviceBam.__new__(DeviceBam)
-    probe.path, probe.file_bytes = path, os.path.getsize(path)
-    probe._read_header()
-    return list(probe.ref_names), list(probe.ref_lengths), int(probe.header_len)
+    return bgzf.bam_header(path)[1:]
 
 
 def scan_records(path, device=0, piece_bytes=None, depth=5, keep_offsets=False):
@@ -233,42 +131,27 @@ def scan_records(path, device=0, piece_bytes=None, depth=5, keep_offsets=False):
     tail = None                                                          # its bytes, when some of them are inflated already (device tensor)
     has_prev, prev_refid, prev_pos = 0, 0, 0
     file_size, base, leftover, seen_last = os.path.getsize(path), 0, b"", False
-
-    def timed(what, fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn()
-        e1.record()
-        e1.synchronize()
-        ms[what] += e0.elapsed_time(e1)
-        return r
+    timed = bgzf.event_timed(ms)
     with open(path, "rb") as f:
         while not seen_last:
             chunk = f.read(piece_bytes)
             buf = np.frombuffer(leftover + chunk, np.uint8)
             if buf.size == 0:
                 raise _lib.NanoCallerHipError("%s does not end with a whole BGZF member" % path)
-            cap = buf.size // 28 + 16
-            coff, clen, isize = np.empty(cap, np.int64), np.empty(cap, np.int32), np.empty(cap, np.int32)
-            k, nxt = C.c_int64(), C.c_int64()
-            rc = L.nc_bgzf_scan(_lib.npp(buf), buf.size, 0, cap, _lib.npp(coff), _lib.npp(clen), _lib.npp(isize), C.byref(k), C.byref(nxt))
-            if rc != _lib.NC_OK:
-                raise _lib.NanoCallerHipError("%s is not a BGZF file (nc_bgzf_scan: %d at byte %d)" % (path, rc, base))
-            k, nxt = int(k.value), int(nxt.value)
+            try:
+                coff, clen, isize, nxt = bgzf.scan_members(buf)
+            except bgzf.ScanError as e:
+                raise _lib.NanoCallerHipError("%s is not a BGZF file (nc_bgzf_scan: %d at byte %d)" % (path, e.rc, base))
+            k = int(coff.size)
             if k == 0:
                 if not chunk:
                     raise _lib.NanoCallerHipError("%s does not end with a whole BGZF member" % path)
                 leftover = buf.tobytes()
                 continue
-            coff, clen, isize = coff[:k], clen[:k], isize[:k]
             seen_last = base + nxt == file_size
-            n_inf = int(isize.sum(dtype=np.int64))
-            mstart = np.empty(k, np.int64)
-            mstart[0] = 0
-            mstart[1:] = coff[:-1] + clen[:-1] + 8
-            oo = np.zeros(k, np.int64)
-            np.cumsum(isize[:-1], out=oo[1:])
-            mem_ooff, mem_foff = np.concatenate([mem_ooff, oo + g_total]), np.concatenate([mem_foff, mstart + base])
+            mstart, oo = bgzf.member_table(coff, clen, isize)
+            n_inf = int(oo[-1])
+            mem_ooff, mem_foff = np.concatenate([mem_ooff, oo[:-1] + g_total]), np.concatenate([mem_foff, mstart + base])
             g0, g1 = g_total, g_total + n_inf
             stats["pieces"] += 1
             stats["members"] += k
@@ -280,12 +163,10 @@ def scan_records(path, device=0, piece_bytes=None, depth=5, keep_offsets=False):
                 d_buf[length:].zero_()
                 if t_len:
                     d_buf[:t_len].copy_(tail)
-                status = timed("inflate", lambda: _inflate_piece(eng, buf[:nxt], coff, clen, isize, d_buf, t_len))
-                bad = int(status.count_nonzero().item())
-                if bad:
-                    crc = int((status == 7).sum().item())
-                    raise _lib.NanoCallerHipError("%s: %d BGZF members are not valid deflate streams of their announced size%s"
-                                                  % (path, bad - crc, (", %d fail their CRC-32" % crc) if crc else ""))
+                status = timed("inflate", lambda: _inflate_piece(eng, buf[:nxt], coff, clen, isize, oo, d_buf, t_len))
+                err = bgzf.bad_members_error(path, [status])
+                if err:
+                    raise err
                 stream_base = g0 - t_len
                 first = g_carry - stream_base
                 d_out, n_rec, carry, st = timed("chain", lambda: chain_piece(eng, d_buf, length, first, n_ref, d_ref_len, seen_last, stats))

@@ -13,7 +13,6 @@ compression on this path: without the device route (no index beside the input, a
 """
 from __future__ import annotations
 
-import gzip
 import os
 import struct
 import time
@@ -21,10 +20,10 @@ import time
 import numpy as np
 
 from . import _lib
+from .bgzf import BGZF_BLOCK, BGZF_EOF, bam_header, bgzf_members, event_timed, member_spans, virtual_offsets
+from .hts_index import index_bytes
 
-BGZF_BLOCK = 0xff00             # uncompressed bytes of every member but the last (htslib's BGZF_BLOCK_SIZE)
 PAYLOAD_SLOT = 65536            # room for one member's payload on the device (a stored block is 65,285 bytes at most)
-BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 PG_NAME = "nanocaller_amd"
 CSI_MIN_SHIFT, CSI_DEPTH = 14, 5
 
@@ -42,24 +41,9 @@ def ps_tag(v) -> bytes:
 
 
 def read_bam_header(path):
-    """(header text, [(name, length), ...]) of a BAM file (its leading members, inflated on the host: a few kilobytes)"""
-    with gzip.open(path, "rb") as f:
-        def need(n):
-            b = f.read(n)
-            if len(b) != n:
-                raise _lib.NanoCallerHipError("%s: truncated BAM header" % path)
-            return b
-        if need(4) != b"BAM\1":
-            raise _lib.NanoCallerHipError("%s is not a BAM file" % path)
-        l_text, = struct.unpack("<i", need(4))
-        text = need(l_text).split(b"\0", 1)[0].decode("ascii", "replace")
-        n_ref, = struct.unpack("<i", need(4))
-        refs = []
-        for _ in range(n_ref):
-            l_name, = struct.unpack("<i", need(4))
-            name = need(l_name)[:-1].decode("ascii")
-            refs.append((name, struct.unpack("<i", need(4))[0]))
-    return text, refs
+    """(header text, [(name, length), ...]) of a BAM file"""
+    text, names, lengths, _ = bam_header(path)
+    return text, list(zip(names, lengths))
 
 
 def add_pg(text, cl=None):
@@ -91,57 +75,9 @@ def header_bytes(text, refs):
     return b"".join(out)
 
 
-def member_spans(n_bytes, base=0, block=BGZF_BLOCK):
-    """(offsets, lengths) of the members that cut n_bytes bytes from `base` on into pieces of `block` (the last may be shorter)"""
-    k = -(-int(n_bytes) // block)
-    off = base + np.arange(k, dtype=np.int64) * block
-    ln = np.full(k, block, np.int32)
-    if k:
-        ln[-1] = int(n_bytes) - (k - 1) * block
-    return off, ln
-
-
-def bgzf_members(payloads, crcs, isizes, eof=True) -> bytes:
-    """gzip members with the BC extra field (SAMv1 4.1) around raw-deflate payloads, + the EOF block"""
-    out = []
-    for p, c, n in zip(payloads, crcs, isizes):
-        out.append(struct.pack("<BBBBIBBHBBHH", 0x1f, 0x8b, 8, 4, 0, 0, 0xff, 6, 66, 67, 2, len(p) + 25) + bytes(p) +
-                   struct.pack("<II", int(c) & 0xffffffff, int(n)))
-    if eof:
-        out.append(BGZF_EOF)
-    return b"".join(out)
-
-
 def voffsets(stream_pos, first_member, member_foff, block=BGZF_BLOCK):
-    """virtual offsets (SAMv1 4.1.1) of positions in a record stream that starts at member `first_member` and is cut into members of `block`
-    bytes; member_foff = file offset of every member (and of the EOF block behind them).  A position at a member boundary is the start of the
-    next member, as htslib's bgzf_tell gives it after a full block."""
-    q = np.asarray(stream_pos, np.int64)
-    m = first_member + q // block
-    return (member_foff[m].astype(np.uint64) << np.uint64(16)) | (q % block).astype(np.uint64)
-
-
-def _reg2bin(beg, end, min_shift=CSI_MIN_SHIFT, depth=CSI_DEPTH):
-    end = end - 1
-    out = np.zeros(beg.size, np.int64)
-    done = np.zeros(beg.size, bool)
-    s, t = min_shift, ((1 << (depth * 3)) - 1) // 7
-    for lv in range(depth, 0, -1):
-        hit = ~done & ((beg >> s) == (end >> s))
-        out[hit] = t + (beg[hit] >> s)
-        done |= hit
-        s += 3
-        t -= 1 << ((lv - 1) * 3)
-    return out
-
-
-def _bin_first_window(b, depth=CSI_DEPTH):
-    out = np.zeros(b.size, np.int64)
-    for lv in range(depth + 1):
-        t = ((1 << (3 * lv)) - 1) // 7
-        m = (b >= t) & (b < t + (1 << (3 * lv)))
-        out[m] = (b[m] - t) << (3 * (depth - lv))
-    return out
+    """bgzf.virtual_offsets of positions in a record stream that starts at member `first_member`"""
+    return virtual_offsets(stream_pos, member_foff, first_member, block)
 
 
 def csi_index(n_ref, tid, beg, end, vbeg, vend, min_shift=CSI_MIN_SHIFT, depth=CSI_DEPTH) -> bytes:
@@ -149,45 +85,8 @@ def csi_index(n_ref, tid, beg, end, vbeg, vend, min_shift=CSI_MIN_SHIFT, depth=C
     [beg[k], end[k]) (0-based) and occupies virtual offsets [vbeg[k], vend[k]).  Per bin its chunks (adjacent records merged) and
     `loffset` = the smallest virtual offset of a record overlapping the bin's first window (empty windows take the next window's), as
     samtools index -c writes them; no pseudo-bin"""
-    beg, end = np.asarray(beg, np.int64), np.asarray(end, np.int64)
-    vbeg, vend = np.asarray(vbeg, np.uint64), np.asarray(vend, np.uint64)
-    out = [b"CSI\1", struct.pack("<3i", min_shift, depth, 0), struct.pack("<i", n_ref)]
-    for r in range(n_ref):
-        if r != tid or beg.size == 0:
-            out.append(struct.pack("<i", 0))
-            continue
-        w0, w1 = beg >> min_shift, (end - 1) >> min_shift
-        n_win = int(w1.max()) + 1
-        big = np.uint64(np.iinfo(np.uint64).max)
-        lin = np.full(n_win + 1, big, np.uint64)
-        cnt = (w1 - w0 + 1)
-        rows = np.repeat(np.arange(beg.size), cnt)
-        win = w0[rows] + (np.arange(rows.size) - np.repeat(np.cumsum(cnt) - cnt, cnt))
-        np.minimum.at(lin, win, vbeg[rows])
-        idx = np.where(lin[:n_win] != big, np.arange(n_win), n_win)
-        idx = np.minimum.accumulate(idx[::-1])[::-1]
-        lin = lin[idx]
-        bins = _reg2bin(beg, end, min_shift, depth)
-        o = np.argsort(bins, kind="stable")
-        sb, svb, sve = bins[o], vbeg[o], vend[o]
-        new = np.ones(sb.size, bool)
-        new[1:] = (sb[1:] != sb[:-1]) | (svb[1:] != sve[:-1])
-        starts = np.flatnonzero(new)
-        ends = np.concatenate([starts[1:], [sb.size]]) - 1
-        ch_bin, ch_beg, ch_end = sb[starts], svb[starts], sve[ends]
-        ub, first = np.unique(ch_bin, return_index=True)
-        n_ch = np.diff(np.concatenate([first, [ch_bin.size]]))
-        wdx = _bin_first_window(ub, depth)
-        loff = np.where(wdx < n_win, lin[np.minimum(wdx, n_win - 1)], np.uint64(0))
-        blob = [struct.pack("<i", ub.size)]
-        for k in range(ub.size):
-            a = int(first[k])
-            c = np.empty(2 * int(n_ch[k]), np.uint64)
-            c[0::2], c[1::2] = ch_beg[a:a + n_ch[k]], ch_end[a:a + n_ch[k]]
-            blob.append(struct.pack("<IQi", int(ub[k]), int(loff[k]), int(n_ch[k])) + c.astype("<u8").tobytes())
-        out.append(b"".join(blob))
-    out.append(struct.pack("<Q", 0))
-    return b"".join(out)
+    n = len(beg)
+    return index_bytes("csi", n_ref, np.full(n, tid), beg, end, np.zeros(n, bool), None, vbeg, vend, min_shift, depth, pseudo_bin=False)
 
 
 def load_table(haplotags):
@@ -273,14 +172,7 @@ def write_haplotagged_bam(sam_path, chrom, haplotags, out_path, start=None, end=
     hl = len(hdr)
     th, thp, tps = load_table(haplotags)
 
-    def timed(what, fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn()
-        e1.record()
-        e1.synchronize()
-        ms[what] = ms.get(what, 0.0) + e0.elapsed_time(e1)
-        return r
+    timed = event_timed(ms)
     # ---- re-tag
     d_rec = torch.from_numpy(np.ascontiguousarray(db.rec_off[a + sel], np.int64)).to(dev)
     d_hash = torch.from_numpy(np.ascontiguousarray(th).view(np.int64)).to(dev)

@@ -18,14 +18,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import struct
-import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, bgzf, hts_index
 from .engine import DevicePack, get_engine
 from .pack import mate_table, name_groups, pileup_depth_cap
 from .synth import FLAG_FILTER_DEFAULT, FLAG_FILTER_SUPPL
@@ -81,60 +79,8 @@ def bai_linear_voffsets(bai_path):
     key = (os.path.abspath(bai_path), st.st_size, st.st_mtime_ns)
     if key not in _BAI:
         _BAI.clear()
-        _BAI[key] = _csi_record_starts(bai_path) if bai_path.endswith(".csi") else _bai_linear_voffsets(bai_path)
+        _BAI[key] = (hts_index.csi_record_starts if bai_path.endswith(".csi") else hts_index.bai_linear_voffsets)(bai_path)
     return _BAI[key]
-
-
-def _csi_record_starts(csi_path):
-    """the same from a CSI index (hts-specs CSIv1; the file is BGZF-compressed), which has no linear index: every bin's `loffset` and every
-    chunk's begin are virtual offsets of record starts of that reference -- the leaf bins (16 kb with the default min_shift) make them as
-    dense as a .bai's windows"""
-    import gzip
-    with open(csi_path, "rb") as f:
-        buf = gzip.decompress(f.read())
-    if buf[:4] != b"CSI\1":
-        raise ValueError("%s is not a CSI file" % csi_path)
-    _, depth, l_aux = struct.unpack_from("<3i", buf, 4)
-    o = 16 + l_aux
-    n_ref, = struct.unpack_from("<i", buf, o)
-    o += 4
-    meta_bin = ((1 << (depth * 3 + 3)) - 1) // 7 + 1                   # the pseudo-bin with the mapped / unmapped counts
-    out = {}
-    for r in range(n_ref):
-        n_bin, = struct.unpack_from("<i", buf, o)
-        o += 4
-        starts = []
-        for _ in range(n_bin):
-            b, loff, n_chunk = struct.unpack_from("<IQi", buf, o)
-            o += 16
-            if b != meta_bin:
-                starts.append(np.array([loff], np.uint64))
-                starts.append(np.frombuffer(buf, np.uint64, 2 * n_chunk, o)[0::2])
-            o += 16 * n_chunk
-        v = np.concatenate(starts) if starts else np.zeros(0, np.uint64)
-        out[r] = np.unique(v[v != 0])
-    return out
-
-
-def _bai_linear_voffsets(bai_path):
-    with open(bai_path, "rb") as f:
-        buf = f.read()
-    if buf[:4] != b"BAI\1":
-        raise ValueError("%s is not a BAI file" % bai_path)
-    n_ref, = struct.unpack_from("<i", buf, 4)
-    o, out = 8, {}
-    for r in range(n_ref):
-        n_bin, = struct.unpack_from("<i", buf, o)
-        o += 4
-        for _ in range(n_bin):
-            _, n_chunk = struct.unpack_from("<Ii", buf, o)
-            o += 8 + 16 * n_chunk
-        n_intv, = struct.unpack_from("<i", buf, o)
-        o += 4
-        iv = np.frombuffer(buf, np.uint64, n_intv, o)
-        o += 8 * n_intv
-        out[r] = np.unique(iv[iv != 0])
-    return out
 
 
 class DeviceBam:
@@ -152,7 +98,7 @@ class DeviceBam:
         from .bam import rank_threads
         self.threads = threads or rank_threads()
         self.file_bytes = os.path.getsize(path)
-        self._read_header()
+        _, self.ref_names, self.ref_lengths, self.header_len = bgzf.bam_header(path)
         self.B0, self.B1, self.tids = 0, self.file_bytes, None
         if contigs is not None:
             unknown = [c for c in contigs if c not in self.ref_names]
@@ -171,64 +117,6 @@ class DeviceBam:
         if self.n_bytes * 8 > resident_limit(device):                    # (the loader reserves eight times the compressed size for the inflated stream)
             raise DeviceIngestUnavailable("%s (%.1f GB to load): more than is kept in HBM at once" % (path, self.n_bytes / 1e9))
         self.loaded = False
-
-    def _read_header(self):
-        """reference names / lengths: the head of the file, inflated with zlib"""
-        L, want = _lib.lib(), 1 << 20
-        while True:
-            with open(self.path, "rb") as f:
-                head = np.frombuffer(f.read(min(want, self.file_bytes)), np.uint8)
-            cap = head.size // 28 + 16
-            coff, clen, isize = np.empty(cap, np.int64), np.empty(cap, np.int32), np.empty(cap, np.int32)
-            k, nxt = C.c_int64(), C.c_int64()
-            rc = L.nc_bgzf_scan(_lib.npp(head), head.size, 0, cap, _lib.npp(coff), _lib.npp(clen), _lib.npp(isize), C.byref(k), C.byref(nxt))
-            if rc != _lib.NC_OK:
-                raise _lib.NanoCallerHipError("%s is not a BGZF file (nc_bgzf_scan: %d)" % (self.path, rc))
-            if self._header(head, coff[:int(k.value)], clen[:int(k.value)]):
-                return
-            if head.size >= self.file_bytes:
-                raise _lib.NanoCallerHipError("%s: truncated BAM header" % self.path)
-            want *= 8
-
-    def _header(self, data, coff, clen):
-        """reference names / lengths from the leading members (inflated with zlib: a few kilobytes).  -> False when the members seen so far
-        do not hold the whole header yet"""
-        got, k = b"", 0
-
-        class Short(Exception):
-            pass
-
-        def need(n):
-            nonlocal got, k
-            while len(got) < n:
-                if k >= len(coff):
-                    raise Short()
-                c = int(coff[k])
-                got += zlib.decompress(data[c:c + int(clen[k])].tobytes(), -15)
-                k += 1
-        try:
-            return self._header_fields(need, lambda: got)
-        except Short:
-            return False
-
-    def _header_fields(self, need, buf):
-        need(12)
-        if buf()[:4] != b"BAM\1":
-            raise _lib.NanoCallerHipError("%s is not a BAM file" % self.path)
-        l_text, = struct.unpack_from("<i", buf(), 4)
-        need(12 + l_text)
-        n_ref, = struct.unpack_from("<i", buf(), 8 + l_text)
-        o = 12 + l_text
-        names, lengths = [], []
-        for _ in range(n_ref):
-            need(o + 4)
-            l_name, = struct.unpack_from("<i", buf(), o)
-            need(o + 8 + l_name)
-            names.append(buf()[o + 4:o + 4 + l_name - 1].decode("ascii"))
-            lengths.append(struct.unpack_from("<i", buf(), o + 4 + l_name)[0])
-            o += 8 + l_name
-        self.ref_names, self.ref_lengths, self.header_len = names, lengths, o   # (header_len: where the first record starts in the inflated stream)
-        return True
 
     def voffset_to_stream(self, voff):
         """virtual offsets (coffset << 16 | uoffset) -> offsets into the inflated stream"""
@@ -294,7 +182,7 @@ class DeviceBam:
         # two token workspaces: the Huffman kernel of batch i + 1 (compute stream) runs beside the match resolution of batch i (its own stream)
         # (256 KB of tokens per member: a small file gets small workspaces -- and, should its members be unusually short, more batches)
         batch = min(INFLATE_BATCH, max(64, (n // 4096 + 63) // 64 * 64))
-        toks = [(_work_buffer(dev, "tok%d" % k_, ((batch + 63) // 64) << 22, torch.int32), torch.zeros(batch, dtype=torch.int32, device=dev), [None])
+        toks = [(bgzf.token_workspace(dev, "tok%d" % k_, batch), torch.zeros(batch, dtype=torch.int32, device=dev), [None])
                 for k_ in range(2)]
         t_alloc = time.perf_counter() - t_start
         copy_stream, lz_stream = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
@@ -377,12 +265,11 @@ class DeviceBam:
                 avail = fut.result()
                 t_wait += time.perf_counter() - tw
                 while True:
-                    k, nxt = C.c_int64(), C.c_int64()
-                    rc = L.nc_bgzf_scan(_lib.npp(data), avail, scan_pos, cap - n_mem, vp(stage64, 8 * n_mem), vp(stage32, 4 * n_mem), vp(stage32, 4 * (cap + n_mem)),
-                                        C.byref(k), C.byref(nxt))
-                    if rc != _lib.NC_OK:
-                        raise _lib.NanoCallerHipError("%s is not a BGZF file (nc_bgzf_scan: %d at byte %d)" % (self.path, rc, scan_pos))
-                    k = int(k.value)
+                    try:
+                        new, _, _, nxt = bgzf.scan_members(data[:avail], scan_pos, (coff, clen, isize), n_mem)   # straight into the page-locked arrays
+                    except bgzf.ScanError as e:
+                        raise _lib.NanoCallerHipError("%s is not a BGZF file (nc_bgzf_scan: %d at byte %d)" % (self.path, e.rc, scan_pos))
+                    k = int(new.size)
                     if k:
                         ooff[n_mem] = total
                         if k > 1:
@@ -390,7 +277,7 @@ class DeviceBam:
                             ooff[n_mem + 1:n_mem + k] += total
                         total = int(ooff[n_mem + k - 1]) + int(isize[n_mem + k - 1])
                     n_mem += k
-                    scan_pos = int(nxt.value)
+                    scan_pos = nxt
                     if n_mem < cap or scan_pos >= avail:
                         break
                     raise DeviceIngestUnavailable("%s: more BGZF members than planned for" % self.path)
@@ -414,15 +301,11 @@ class DeviceBam:
         LAST_LOAD["of_which_allocations"], LAST_LOAD["of_which_waiting_for_readers"], LAST_LOAD["of_which_enqueue"] = t_alloc, t_wait, t_launch
         t0 = time.perf_counter()
         self.coff, self.clen, self.isize = coff[:n_mem].copy(), clen[:n_mem].copy(), isize[:n_mem].copy()
-        self.ooff = np.concatenate([ooff[:n_mem], [total]]).astype(np.int64)
-        self.mstart = np.zeros(n_mem, np.int64)                                               # file offset of every member
-        self.mstart[1:] = self.coff[:-1] + self.clen[:-1] + 8
+        self.mstart, self.ooff = bgzf.member_table(self.coff, self.clen, self.isize)   # file offset / inflated offset of every member (+ the total)
         lz_stream.synchronize()
-        bad = sum(int(st.count_nonzero().item()) for st in statuses)     # (also: the inflate is done)
-        if bad:
-            crc = sum(int((st == 7).sum().item()) for st in statuses)
-            raise _lib.NanoCallerHipError("%s: %d BGZF members are not valid deflate streams of their announced size%s"
-                                          % (self.path, bad - crc, (", %d fail their CRC-32" % crc) if crc else ""))
+        err = bgzf.bad_members_error(self.path, statuses)                # (also: the inflate is done)
+        if err:
+            raise err
         compute.wait_stream(lz_stream)
         if traces:
             e0 = traces[0][3][0][1]
@@ -736,18 +619,17 @@ def contig_spans(path):
     """{contig: (lo, hi)} = the bytes of the BAM file that hold its records, from the .bai alone: the member of its first record to the member of
     the next contig's first record (inclusive: a record straddles members); contigs without alignments are absent.  Raises
     DeviceIngestUnavailable when there is no .bai."""
-    probe = DeviceBam.__new__(DeviceBam)
     bai = _bai_path(path)
     if bai is None:
         raise DeviceIngestUnavailable("%s: no .bai / .csi beside it" % path)
-    probe.path, probe.lin, probe.file_bytes = path, bai_linear_voffsets(bai), os.path.getsize(path)
-    probe._read_header()
-    with_reads = [t for t in sorted(probe.lin) if probe.lin[t].size and t < len(probe.ref_names)]
+    lin, file_bytes = bai_linear_voffsets(bai), os.path.getsize(path)
+    names = bgzf.bam_header(path)[1]
+    with_reads = [t for t in sorted(lin) if lin[t].size and t < len(names)]
     out = {}
     for k, t in enumerate(with_reads):
-        hi = min(probe.file_bytes, int(probe.lin[with_reads[k + 1]][0] >> np.uint64(16)) + 65536 + 1024) if k + 1 < len(with_reads) else probe.file_bytes
-        out[probe.ref_names[t]] = (int(probe.lin[t][0] >> np.uint64(16)), hi)
-    return out, list(probe.ref_names)
+        hi = min(file_bytes, int(lin[with_reads[k + 1]][0] >> np.uint64(16)) + 65536 + 1024) if k + 1 < len(with_reads) else file_bytes
+        out[names[t]] = (int(lin[t][0] >> np.uint64(16)), hi)
+    return out, names
 
 
 def plan_shares(path, contigs, limit_bytes=None, device=None):

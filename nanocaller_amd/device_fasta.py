@@ -13,14 +13,13 @@ it reads it; a member that does not inflate to its announced size or fails its C
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, fasta
-from .device_bam import CHECK_CRC, DeviceIngestUnavailable, _work_buffer
+from . import _lib, bgzf, fasta
+from .device_bam import DeviceIngestUnavailable
 from .engine import get_engine
 
 INFLATE_BATCH = 4096          # members per nc_inflate_device call (256 KB of token workspace each)
@@ -78,31 +77,13 @@ class DeviceContig:
 
     def _inflate(self, eng, dev):
         """the covering members -> the uncompressed bytes (nc_inflate_device + nc_bgzf_crc_device on the context's stream)"""
-        L = _lib.lib()
         m = self._members
         n = int(m["n"])
-        vp = lambda t, byte_off=0: C.c_void_p(t.data_ptr() + byte_off)   # noqa: E731
         raw = torch.empty(self.image_len + 64, dtype=torch.uint8, device=dev)
-        status = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
-        d_comp, d64, d32 = self._staged["file"], self._staged["m64"], self._staged["m32"]     # [coff | ooff], [clen | isize]
-        batch = min(INFLATE_BATCH, max(64, (n + 63) // 64 * 64))
-        d_tok = _work_buffer(dev, "fa_tok", ((batch + 63) // 64) << 22, torch.int32)
-        d_ntok = torch.zeros(batch, dtype=torch.int32, device=dev)
         timed = self.owner.timed
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
-        for a in range(0, n, batch):
-            k = min(batch, n - a)
-            args = (k, vp(d_comp), vp(d64, 8 * a), vp(d32, 4 * a), vp(raw), vp(d64, 8 * (n + a)), vp(d32, 4 * (n + a)), vp(status, 4 * a))
-            if timed and a == 0:
-                ev[0].record()
-            eng._check(L.nc_inflate_device(eng.ctx, *args, vp(d_tok), vp(d_ntok)), "nc_inflate_device")
-            if timed and a + batch >= n:
-                ev[1].record()
-            if CHECK_CRC:
-                eng._check(L.nc_bgzf_crc_device(eng.ctx, *args), "nc_bgzf_crc_device")
-        if timed:
-            ev[2].record()
-        st = status[:n].cpu().numpy()
+        status = bgzf.inflate_members(eng, self._staged["file"], self._staged["m64"], self._staged["m32"], n, raw, INFLATE_BATCH, "fa_tok", ev)
+        st = status.cpu().numpy()
         if timed:
             # (with several batches the inflate figure covers the CRCs of all but the last batch as well)
             LAST_CONTIG.update(inflate=ev[0].elapsed_time(ev[1]) * 1e-3, crc=ev[1].elapsed_time(ev[2]) * 1e-3)
@@ -229,8 +210,7 @@ class DeviceFasta:
         if self.gz:
             coff, clen, isize, _ = fasta.scan_members(data[:n], lo)
             need = e.offset + e.span - ubase                             # uncompressed bytes from the first member's first to the contig's last
-            ooff = np.zeros(coff.size + 1, np.int64)
-            np.cumsum(isize, out=ooff[1:])
+            ooff = bgzf.member_table(coff, clen, isize)[1]
             k = int(np.searchsorted(ooff, need, side="left"))           # members that hold them
             if k > coff.size or ooff[min(k, coff.size)] < need:
                 raise _lib.NanoCallerHipError("%s ends %d bytes before contig %s does: the .fai does not describe this file"

@@ -12,7 +12,6 @@ kept in memory: nothing is written beside the user's file.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import struct
 import zlib
@@ -20,7 +19,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import _lib
+from . import bgzf
 from ._lib import NanoCallerHipError
 
 BGZF_MAGIC = b"\x1f\x8b\x08\x04"
@@ -160,16 +159,11 @@ def read_gzi(gzi_path, gz_path):
 
 
 def scan_members(data, base=0):
-    """the whole BGZF members of `data` (bytes-like) through nc_bgzf_scan -> (payload offset into data, payload length, inflated size, bytes scanned)"""
-    arr = np.frombuffer(data, np.uint8)
-    cap = arr.size // 26 + 4
-    coff, clen, isize = np.empty(cap, np.int64), np.empty(cap, np.int32), np.empty(cap, np.int32)
-    k, nxt = C.c_int64(), C.c_int64()
-    rc = _lib.lib().nc_bgzf_scan(_lib.npp(arr), arr.size, 0, cap, _lib.npp(coff), _lib.npp(clen), _lib.npp(isize), C.byref(k), C.byref(nxt))
-    if rc != _lib.NC_OK:
-        raise NanoCallerHipError("not a BGZF member at byte %d (nc_bgzf_scan: %d)" % (base + int(nxt.value), rc))
-    k = int(k.value)
-    return coff[:k].copy(), clen[:k].copy(), isize[:k].copy(), int(nxt.value)
+    """the whole BGZF members of `data` (bytes-like) -> (payload offset into data, payload length, inflated size, bytes scanned)"""
+    try:
+        return bgzf.scan_members(data)
+    except bgzf.ScanError as e:
+        raise NanoCallerHipError("not a BGZF member at byte %d (nc_bgzf_scan: %d)" % (base + e.pos, e.rc))
 
 
 def walk_members(gz_path, piece=64 << 20):
@@ -188,13 +182,10 @@ def walk_members(gz_path, piece=64 << 20):
             except NanoCallerHipError as e:
                 raise NanoCallerHipError("%s: %s" % (gz_path, e))
             if coff.size:
-                start = np.zeros(coff.size, np.int64)
-                start[1:] = coff[:-1] + clen[:-1] + 8
+                start, uo = bgzf.member_table(coff, clen, isize)
                 ms.append(start + pos)
-                uo = np.zeros(coff.size, np.int64)
-                np.cumsum(isize[:-1], out=uo[1:])
-                us.append(uo + u)
-                u += int(isize.sum(dtype=np.int64))
+                us.append(uo[:-1] + u)
+                u += int(uo[-1])
             if not got:
                 if nxt != len(buf):
                     raise NanoCallerHipError("%s does not end with a whole BGZF member" % gz_path)

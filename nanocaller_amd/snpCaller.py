@@ -520,9 +520,6 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
 
 
 # ------------------------------------------------------------------ BGZF (so no bgzip binary is needed)
-_BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-
-
 def bgzf_write(path, data: bytes):
     """BGZF file through the library's multi-threaded compressor (see vcfio.py)"""
     from . import vcfio

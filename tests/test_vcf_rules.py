@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from nanocaller_amd import snpCaller
+from nanocaller_amd import bgzf, snpCaller
 from tests.util import GOLD
 
 
@@ -75,7 +75,7 @@ def test_bgzf_writer_is_valid_gzip(tmp_path):
     snpCaller.bgzf_write(p, data)
     assert gzip.open(p, "rb").read() == data
     raw = open(p, "rb").read()
-    assert raw[:4] == b"\x1f\x8b\x08\x04" and raw[12:14] == b"BC" and raw.endswith(snpCaller._BGZF_EOF)
+    assert raw[:4] == b"\x1f\x8b\x08\x04" and raw[12:14] == b"BC" and raw.endswith(bgzf.BGZF_EOF)
 
 
 def test_native_formatter_matches_python_rules_and_reference():

@@ -205,3 +205,69 @@ def test_htslib_written_bgzf_files_and_their_tabix_bins(genome):
     assert rows == gsp._exclude_rows({"exclude_bed": path}, "chr1") and len(rows) >= 2
     exp = tuple((int(t[1]), int(t[2])) for t in (ln.split() for ln in text.decode().splitlines()) if t[0] == "chr1")
     assert rows == exp
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The index writer byte for byte: tests/golden/vcf_csi_bytes.bin.gz is what vcfio.csi_bytes wrote for `_csi_case()` before the three
+# binning-index writers (vcfio.csi_bytes, bam_write.csi_index, bam_index.index_bytes) were folded into hts_index.py.
+def _csi_case():
+    """three references, the middle one without records, ~2000 records in (tid, beg) order: one base long for the most part, some a few bases,
+    some over three or more 16 kb windows, some over hundreds of kilobases (higher bin levels), one that ends exactly on a window boundary,
+    runs of empty windows between them; virtual offsets of a made-up BGZF stream in which the records lie back to back except one pair.
+    (An integer generator of its own: the input must not depend on a numpy version.)"""
+    state = [20261019]
+
+    def rnd(n):
+        state[0] = (state[0] * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
+        return (state[0] >> 33) % n
+    tid, beg, end, ustart, ulen = [], [], [], [], []
+    u, on_boundary, gap_after = 777, None, None
+    for t, n_rec in ((0, 1200), (2, 800)):
+        p = 3 + 17 * t
+        for k in range(n_rec):
+            p += 1 + rnd(40)
+            if k % 97 == 96:
+                p += 16384 * (3 + rnd(60))                               # a run of empty windows
+            ln = 1
+            if k % 50 == 7:
+                ln = 2 + rnd(38)
+            elif k % 50 == 19:
+                ln = 2 * 16384 + 1 + rnd(30000)                          # three or more windows
+            elif k % 50 == 33:
+                ln = 140_000 + rnd(1 << 20)                              # the 1 Mb / 8 Mb levels
+            if (t, k) == (0, 500):
+                ln = (((p >> 14) + 1) << 14) - p                         # ends exactly where a window ends
+                on_boundary = len(tid)
+            if (t, k) == (0, 301):
+                p = beg[-1] + 1 if (beg[-1] + 1) >> 14 == beg[-1] >> 14 else beg[-1]   # in the bin of the record before it
+                u += 11                                                  # ... and not behind it in the file: two chunks in that bin
+                gap_after = len(tid) - 1
+            n_bytes = 60 + rnd(200)
+            tid.append(t), beg.append(p), end.append(p + ln), ustart.append(u), ulen.append(n_bytes)
+            u += n_bytes
+    foff = np.cumsum([0] + [20000 + rnd(10000) for _ in range(u // vcfio.BGZF_BLOCK + 2)])
+    ustart, ulen = np.array(ustart), np.array(ulen)
+    vb, ve = vcfio.virtual_offsets(foff, ustart), vcfio.virtual_offsets(foff, ustart + ulen)
+    return ["chrA", "chrNone", "chrB"], np.array(tid), np.array(beg), np.array(end), vb, ve, on_boundary, gap_after
+
+
+def test_csi_bytes_unchanged():
+    from nanocaller_amd.bam_index import index_bytes
+    names, tid, beg, end, vb, ve, on_boundary, gap_after = _csi_case()
+    # the input is what the docstring says it is
+    w0, w1 = beg >> 14, (end - 1) >> 14
+    bins = vcfio.reg2bin(beg, end)
+    levels = {sum(b >= ((1 << (3 * lv)) - 1) // 7 for lv in range(1, 6)) for b in bins.tolist()}
+    assert tid.size == 2000 and set(tid.tolist()) == {0, 2} and np.all(np.diff(beg)[np.diff(tid) == 0] >= 0)
+    assert np.count_nonzero(end - beg == 1) > 1500 and np.count_nonzero(w1 - w0 >= 2) > 40 and len(levels) >= 3
+    assert end[on_boundary] % 16384 == 0 and end[on_boundary] - beg[on_boundary] > 1
+    assert np.diff(np.unique(np.concatenate([np.arange(a, b + 1) for a, b in zip(w0[tid == 0], w1[tid == 0])]))).max() > 3
+    assert bins[gap_after] == bins[gap_after + 1] and ve[gap_after] != vb[gap_after + 1]
+    assert np.array_equal(ve[:gap_after], vb[1:gap_after + 1])
+    want = gzip.decompress(open(os.path.join(os.path.dirname(__file__), "golden", "vcf_csi_bytes.bin.gz"), "rb").read())
+    assert vcfio.csi_bytes(names, tid, beg, end, vb, ve) == want
+    # the BAM indexer's entry point on the same arrays, every record mapped: the same index without the tabix block
+    l_aux, = struct.unpack_from("<i", want, 12)
+    assert l_aux == 28 + len("chrA\0chrNone\0chrB\0")
+    bare = want[:12] + struct.pack("<i", 0) + want[16 + l_aux:]
+    assert index_bytes("csi", len(names), tid, beg, end, np.zeros(tid.size, bool), bins, vb, ve) == bare
