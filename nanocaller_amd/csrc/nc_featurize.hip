@@ -18,7 +18,7 @@
 namespace {
 
 constexpr int MAXCOV_CAP = 1024;   // LDS list of sampled reads per wave: largest supported maxcov
-constexpr int MAXCOV_SMALL = 256;  // instantiation for maxcov <= 255 (default 160): 20.5 KB of LDS per block -> 7 waves per SIMD instead of 4,
+constexpr int MAXCOV_SMALL = 256;  // instantiation for maxcov <= 255 (default 160): 21.9 KB of LDS per block -> 7 waves per SIMD instead of 4,
                                    // and 8-bit histogram fields (32-bit instead of 64-bit counter updates)
 constexpr int NBR = 20;
 
@@ -27,13 +27,24 @@ struct ModeTab { int32_t nb, W; Bucket b[7]; };
 
 // One row per list comprehension of get_cnd_pos (generate_SNP_pileups.py:6-101), expressed by distance |p-v|.
 // Left and right sides are mirror images; only the innermost bucket may pick the FARTHEST sites (quirk E5).
-__constant__ ModeTab MODES[5] = {
+constexpr ModeTab MODE_TABLES[5] = {
     {5, 50000, {{0, 2000, 2, 1}, {2000, 5000, 3, 0}, {5000, 10000, 4, 0}, {10000, 20000, 5, 0}, {20000, 1 << 30, 6, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}},
     {3, 50000, {{0, 2000, 5, 0}, {2000, 5000, 10, 0}, {5000, 1 << 30, 5, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}},
     {7, 100000, {{0, 2000, 2, 1}, {2000, 5000, 2, 0}, {5000, 10000, 3, 0}, {10000, 20000, 3, 0}, {20000, 40000, 4, 0}, {40000, 50000, 3, 0}, {50000, 1 << 30, 3, 0}}},
     {7, 300000, {{0, 10000, 2, 1}, {10000, 20000, 2, 0}, {20000, 50000, 3, 0}, {50000, 75000, 3, 0}, {75000, 100000, 4, 0}, {100000, 200000, 4, 0}, {200000, 1 << 30, 2, 0}}},
     {4, 20000, {{0, 2000, 4, 1}, {2000, 5000, 5, 0}, {5000, 10000, 5, 0}, {10000, 20000, 6, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}},
 };
+__constant__ ModeTab MODES[5] = {MODE_TABLES[0], MODE_TABLES[1], MODE_TABLES[2], MODE_TABLES[3], MODE_TABLES[4]};
+
+// k_featurize_pairs searches each bucket EDGE once: that needs every table's buckets to tile the distances from 0 on without a gap
+constexpr bool buckets_contiguous()
+{
+    for (int m = 0; m < 5; m++)
+        for (int i = 0; i < MODE_TABLES[m].nb; i++)
+            if (MODE_TABLES[m].b[i].dlo != (i ? MODE_TABLES[m].b[i - 1].dhi : 0) || MODE_TABLES[m].b[i].dhi <= MODE_TABLES[m].b[i].dlo) return false;
+    return true;
+}
+static_assert(buckets_contiguous(), "a bucket must begin where the one before it ends (the first at 0): k_featurize_pairs shares the buckets' edges");
 
 constexpr int NBR_IDX_SHIFT = 10;   // coarse index granularity: first neighbour site >= every 2^shift-th position
 
@@ -372,17 +383,28 @@ __global__ __launch_bounds__(256) void k_featurize(FeatArgs a)
 
 // ---- [r5] the same tensors with lanes as (read, column) PAIRS.  k_featurize walks the sampled reads one after the other with scalar code (the
 // entry record of a read by v_readlane, 41 of 64 lanes busy, ~45 vector + scalar instructions per read); here the covering reads' records go to an
-// LDS list and the wave sweeps the reads x columns rectangle 64 pairs a step, four steps' gathers in flight: no scalar walk, every lane busy,
-// counters by LDS atomic adds (at most the two reads that share a step meet on one counter).  int16 tensors, maxcov <= 255.
+// LDS list and the wave sweeps the (read, column) pairs 64 a step, eight steps' gathers in flight: no scalar walk, every lane busy, counters by
+// LDS atomic adds.  int16 tensors, maxcov <= 255.
+// Only the pairs a read COVERS are swept: the columns ascend and a sampled read covers the centre, so it covers one interval of them, and the
+// pairs are numbered through a prefix over the interval lengths (see the sweep; on 10 kb reads and neighbours up to 50 kb away that is about
+// one slot in four of the reads x columns rectangle).  The centre column's code is the one the pileup loop already holds.
+// What bounds the kernel is the number of cache accesses its vector memory instructions make (profiles/featurize_covered_pairs.md), so: the
+// 2 nb buckets share their 2 nb + 2 edges (one search a lane), and the tensor is put together in LDS and leaves as aligned dwords.
+// LDS: 22,432 bytes a workgroup (52 VGPRs): 7 waves per SIMD, as before.
 // MATES: the pack holds alignments that share read names (entries with bit 3 of base_flag; nc_snp_set_mates): such an entry is left out of a
 // column's pileup when a later alignment of its name covers the column, and its row reads every column through named_code.
 template <bool MATES>
 __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
 {
     __shared__ int32_t nlist[4][64];
-    __shared__ uint4 rec[4][MAXCOV_SMALL];                         // sampled reads with a base at the centre: row address, first position, span | centre base << 28
+    // per wave: the sampled reads with a base at the centre (row address, first position, span | centre base << 28); once they are spent, the site's
+    // tensor (int16 in, dwords out: the union's members, not casts of one another's pointers)
+    union alignas(16) RecBuf { uint4 r[MAXCOV_SMALL]; int16_t h[MAXCOV_SMALL * 8]; uint32_t w[MAXCOV_SMALL * 4]; };
+    static_assert((NC_SNP_TENSOR + 1) * 2 <= (int)sizeof(uint4) * MAXCOV_SMALL, "the tensor (one int16 further in for odd sites) must fit the read list");
+    __shared__ RecBuf rec[4];
     __shared__ int32_t colL[4][64];
     __shared__ uint32_t cntL[4][41 * 4 + 4];
+    __shared__ uint32_t endL[4][2 * 41];                          // one group of 64 reads: bit q = pair q is the last of its read (64 * 41 bits)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nblk = (int)gridDim.x, q8 = nblk >> 3, r8 = nblk & 7, xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
     const int blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
@@ -406,20 +428,26 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
         if (pf_ent.start <= v && v < pf_ent.end) pf_code = a.codes[(pf_ent.base_flag & ~int64_t(15)) + v];
     }
     const int rc_centre = a.ref_code[(int64_t)v - a.ref_pos0];
-    // ---- K2 (as k_featurize)
+    // ---- K2: the buckets of k_featurize, but a bucket's inner edge is the outer edge of the next nearer one (the tables are contiguous: dlo of a
+    // bucket = dhi of the one before it), so the 2 nb buckets have only 2 nb + 2 distinct edges: one search a lane instead of two in a row.
+    // Edge lanes [0, nb]: v - D, D = the outer distance of the left buckets far -> near, then 0; lanes [nb + 1, 2 nb + 1]: v + 1 + D, D = 0, then
+    // the right buckets' near -> far.  Clamping an edge into [win_lo, win_hi + 1] is the scan window's cut of both ranges it bounds.
+    int edge = 0;
+    if (lane < 2 * nb + 2) {
+        const bool left = lane <= nb;
+        const int bi = left ? nb - 1 - lane : lane - nb - 2;            // the bucket this is the outer edge of; -1: the edge at the centre
+        const int64_t D = bi < 0 ? (int64_t)0 : min((int64_t)M.b[max(bi, 0)].dhi, (int64_t)M.W - 1);
+        const int64_t key = min(max(left ? (int64_t)v - D : (int64_t)v + 1 + D, win_lo), win_hi + 1);
+        edge = lower_bound_i32(a.nbr_pos, a.n_nbr, key, a.cidx, a.cidx_pos0, a.n_cidx);
+    }
     int take = 0, idx0 = 0;
-    if (lane < 2 * nb) {
+    {
+        // bucket lanes as before: [0, nb) left far -> near, [nb, 2 nb) right near -> far
         const bool left = lane < nb;
-        const Bucket B = M.b[left ? nb - 1 - lane : lane - nb];
-        const int64_t dhi = min((int64_t)B.dhi, (int64_t)M.W - 1);
-        int64_t pmin = left ? (int64_t)v - dhi : (int64_t)v + B.dlo + 1;
-        int64_t pmax = left ? (int64_t)v - B.dlo - 1 : (int64_t)v + dhi;
-        pmin = max(pmin, win_lo);
-        pmax = min(pmax, win_hi);
-        if (pmin <= pmax) {
-            const int lo = lower_bound_i32(a.nbr_pos, a.n_nbr, pmin, a.cidx, a.cidx_pos0, a.n_cidx);
-            const int hi = lower_bound_i32(a.nbr_pos, a.n_nbr, pmax + 1, a.cidx, a.cidx_pos0, a.n_cidx);
-            take = min(hi - lo, B.k);
+        const int lo = __shfl(edge, left ? lane : lane + 1, 64), hi = __shfl(edge, left ? lane + 1 : lane + 2, 64);
+        if (lane < 2 * nb) {
+            const Bucket B = M.b[left ? nb - 1 - lane : lane - nb];
+            take = min(max(hi - lo, 0), B.k);                            // (hi < lo: a bucket beyond W, or wholly outside the window)
             const bool first = left ? (B.far != 0) : (B.far == 0);
             idx0 = first ? lo : hi - take;
         }
@@ -444,7 +472,7 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
         if (lane != nl && lane < ncols) col = a.nbr_pos[nlist[wv][jj]];
     }
     const bool active = lane < ncols;
-    colL[wv][lane] = col;
+    colL[wv][lane] = active ? col : INT32_MAX;                    // (ascending over all 64 entries: the interval searches below need no bound)
     const int rc_col = active ? a.ref_code[(int64_t)col - a.ref_pos0] : 4;
     // ---- the pileup at v: depth ballots, and the sampled reads' records into the list
     const bool ok = ncols >= a.min_nbr_sites;
@@ -488,39 +516,86 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
         const unsigned long long ms = __ballot(sel);
         if (sel) {
             rr.w |= (uint32_t)code << 28;
-            rec[wv][nsel + __popcll(ms & ((1ull << lane) - 1ull))] = rr;
+            rec[wv].r[nsel + __popcll(ms & ((1ull << lane) - 1ull))] = rr;
         }
         nsel += __popcll(ms);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // ---- reads x columns, 64 pairs a step
+    // ---- the covered (read, column) pairs, 64 a step.  The columns ascend and every sampled read covers the centre, so read r covers exactly the
+    // columns [jlo, jhi): jlo = #{columns < start}, jhi = #{columns < end} (the half-open ends of the `off < span` test below).  The sampled reads
+    // are taken 64 at a time, lanes as reads: both counts by a six-step search of colL (its unused tail holds INT32_MAX), an inclusive scan of
+    // jhi - jlo over the lanes, and the LAST pair of every read marked in a bit mask of the group's Pc <= 64 * 41 pairs (endL; lane k then keeps
+    // word k).  Pair q of step k belongs to the read r = (reads that ended before the step, a scalar running sum) + (end marks below the lane in
+    // word k: v_mbcnt), its column is q + (jlo - pre)[r]: no division, no search per pair.
     {
         typedef const uint8_t __attribute__((address_space(1))) *gbyte_ptr;
-        const int P = nsel * ncols;
-        const float inv = 1.0f / (float)ncols;
         constexpr int U = 8;                                           // steps whose gathers are in flight together
-        for (int p0 = 0; p0 < P; p0 += 64 * U) {
-            int jk[U];
-            uint32_t bc[U];
+        for (int g0 = 0; g0 < nsel; g0 += 64) {
+            const int ng = min(64, nsel - g0);
+            int len = 0, jlo = 0;
+            if (lane < ng) {
+                const uint4 rr = rec[wv].r[g0 + lane];
+                int jhi = 0;
+                const int32_t st = (int32_t)rr.z;
+                const int64_t en = (int64_t)st + (int64_t)(rr.w & 0x0fffffffu);
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int p = p0 + u * 64 + lane;
-                const bool valid = p < P;
-                const int r = (int)(((float)p + 0.5f) * inv), j = p - r * ncols;           // exact: p < 2^14, the product's error is far below 0.5 / 41
-                const uint4 rr = rec[wv][valid ? r : 0];
-                const uint32_t off = (uint32_t)(colL[wv][valid ? j : 0] - (int32_t)rr.z);
-                bc[u] = 4;
-                jk[u] = j * 4 + (int)((rr.w >> 28) & 7u);
-                if (MATES && valid && (rr.w >> 31)) {
-                    // (row address = codes + base + start; the slot starts at base + floor16(start))
-                    const int64_t key = (int64_t)((((uint64_t)rr.y << 32) | rr.x) - (uint64_t)(uintptr_t)a.codes) - (int64_t)(int32_t)rr.z + ((int32_t)rr.z & ~15);
-                    bc[u] = (uint32_t)named_code(a, key, colL[wv][j]);
-                } else if (valid && off < (rr.w & 0x0fffffffu)) bc[u] = ((gbyte_ptr)(uintptr_t)(((uint64_t)rr.y << 32) | rr.x))[off];
+                for (int w = 32; w > 0; w >>= 1) {
+                    const int32_t cl = colL[wv][jlo + w - 1], ch2 = colL[wv][jhi + w - 1];
+                    if (cl < st) jlo += w;
+                    if ((int64_t)ch2 < en) jhi += w;
+                }
+                if (MATES && (rr.w >> 31)) { jlo = 0; jhi = ncols; }       // a name-keyed row reads every column through named_code
+                len = jhi - jlo;                                           // >= 1: start <= v < end and v is column nl
             }
+            int pin = len;
 #pragma unroll
-            for (int u = 0; u < U; u++)
-                if (bc[u] < 4) atomicAdd(&cntL[wv][jk[u]], 1u << (8 * bc[u]));
+            for (int o = 1; o < 64; o <<= 1) {
+                const int y = __shfl_up(pin, o, 64);
+                if (lane >= o) pin += y;
+            }
+            const int Pc = __builtin_amdgcn_readlane(pin, 63);
+            const int dj = jlo - (pin - len);                              // column of pair q of this lane's read = q + dj
+            if (lane < 41) endL[wv][2 * lane] = endL[wv][2 * lane + 1] = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (len > 0) atomicOr(&endL[wv][(pin - 1) >> 5], 1u << ((pin - 1) & 31));
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const int ew_lo = lane < 41 ? (int)endL[wv][2 * lane] : 0, ew_hi = lane < 41 ? (int)endL[wv][2 * lane + 1] : 0;   // step k's 64 marks: lane k's
+            int base = 0;                                                  // reads of the group that ended before the step (wave-uniform)
+            for (int q0 = 0; q0 < Pc; q0 += 64 * U) {
+                int jk[U];
+                uint32_t bc[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    bc[u] = 4;
+                    jk[u] = 0;
+                    const int qs = q0 + u * 64;
+                    if (qs < Pc) {                                         // (wave-uniform: the steps past the last pair are skipped, not masked)
+                        const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane(ew_lo, qs >> 6), whi = (uint32_t)__builtin_amdgcn_readlane(ew_hi, qs >> 6);
+                        const int q = qs + lane;
+                        const bool valid = q < Pc;
+                        const int r = valid ? base + (int)__builtin_amdgcn_mbcnt_hi(whi, __builtin_amdgcn_mbcnt_lo(wlo, 0u)) : 0;
+                        base += __builtin_popcount(wlo) + __builtin_popcount(whi);
+                        const uint4 rr = rec[wv].r[g0 + r];
+                        const int djr = __shfl(dj, r, 64);                 // (every lane takes part: a lane that sat out would hand its reader 0)
+                        const int j = valid ? q + djr : 0;
+                        const int32_t cj = colL[wv][j];
+                        const uint32_t off = (uint32_t)(cj - (int32_t)rr.z);
+                        jk[u] = j * 4 + (int)((rr.w >> 28) & 7u);
+                        if (MATES && valid && (rr.w >> 31)) {
+                            // (row address = codes + base + start; the slot starts at base + floor16(start))
+                            const int64_t key = (int64_t)((((uint64_t)rr.y << 32) | rr.x) - (uint64_t)(uintptr_t)a.codes) - (int64_t)(int32_t)rr.z + ((int32_t)rr.z & ~15);
+                            bc[u] = (uint32_t)named_code(a, key, cj);
+                        } else if (valid && j == nl) bc[u] = (rr.w >> 28) & 7u;    // (the centre column: the base the pileup loop loaded)
+                        else if (valid && off < (rr.w & 0x0fffffffu)) bc[u] = ((gbyte_ptr)(uintptr_t)(((uint64_t)rr.y << 32) | rr.x))[off];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    if (bc[u] < 4) atomicAdd(&cntL[wv][jk[u]], 1u << (8 * bc[u]));
+            }
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -533,14 +608,16 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
         const bool have = ok && lane < 41 && src >= 0 && src < ncols;
         const int sl = have ? src : 0;
         const int rc_s = __shfl(rc_col, have ? src : lane, 64);
+        // The site's 1025 int16 are put together in LDS, over the read list (its records are spent), and leave as 512 aligned dwords plus one
+        // int16: 8 store instructions of 4 cache lines each instead of 15 of 41 lanes strided by 10 bytes over 410.  A site starts on a 4-byte
+        // boundary only when s is even (2050 bytes a site), so for odd s the tensor sits one int16 further into the LDS buffer and the single
+        // int16 is element 0, not element 1024.
+        const int odd = s & 1;
+        int16_t *T = rec[wv].h + odd;
         if (lane < 41) {
-            int16_t *dst = reinterpret_cast<int16_t *>(a.x) + (int64_t)s * NC_SNP_TENSOR + lane * 5;
-            typedef uint32_t __attribute__((aligned(2))) u32_a2;
             auto put_row = [&](int row, int v0, int v1, int v2, int v3, int v4) {
-                int16_t *d = dst + row * (41 * 5);
-                *reinterpret_cast<u32_a2 *>(d) = (uint32_t)(v0 & 0xffff) | ((uint32_t)v1 << 16);
-                *reinterpret_cast<u32_a2 *>(d + 2) = (uint32_t)(v2 & 0xffff) | ((uint32_t)v3 << 16);
-                d[4] = (int16_t)v4;
+                int16_t *d = T + row * (41 * 5) + lane * 5;
+                d[0] = (int16_t)v0; d[1] = (int16_t)v1; d[2] = (int16_t)v2; d[3] = (int16_t)v3; d[4] = (int16_t)v4;
             };
             const int rcs = have ? rc_s : 4;
             put_row(0, rcs == 0, rcs == 1, rcs == 2, rcs == 3, 0);
@@ -556,6 +633,14 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
                 put_row(1 + i, vv[0], vv[1], vv[2], vv[3], (have && i == rc_centre) ? 1 : 0);
             }
         }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        int16_t *dst = reinterpret_cast<int16_t *>(a.x) + (int64_t)s * NC_SNP_TENSOR;
+        uint32_t *d32 = reinterpret_cast<uint32_t *>(dst + odd);
+        const uint32_t *t32 = rec[wv].w + odd;     // dword i = elements 2i + odd, 2i + 1 + odd
+#pragma unroll
+        for (int i = 0; i < (NC_SNP_TENSOR - 1) / 2; i += 64) d32[i + lane] = t32[i + lane];
+        if (lane == 0) dst[odd ? 0 : NC_SNP_TENSOR - 1] = T[odd ? 0 : NC_SNP_TENSOR - 1];
     }
     if (lane == 0) {
         a.ref_out[s] = rc_centre;
