@@ -34,7 +34,8 @@ extern "C" {
                               11: nc_snp_trunk_info (which SNP trunk kernel the next nc_snp_forward runs, its MFMA count per site), nc_wire_build_del +
                                   nc_wire_apply_deletions (deleted columns implied by the indel events), nc_wire_ref_unpack (reference bytes two per byte), two-byte
                                   indel events (nc_indel_events_pack / _expand with l8 = NULL), nc_snp_scan_begin / _end, nc_wire_expand_del + nc_wire_arrays.blk_ev,
-                                  nc_decoded_name_groups + nc_snp_set_mates (alignments that share a read name, keyed by name in the SNP featuriser) */
+                                  nc_decoded_name_groups + nc_snp_set_mates (alignments that share a read name, keyed by name in the SNP featuriser),
+                                  nc_snp_scan_set_sites (positions to genotype whatever their allele frequency) */
 
 typedef struct nc_ctx nc_ctx;
 
@@ -415,6 +416,15 @@ int nc_snp_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d_mate_key, co
  * set and impute_indel_phase, or with chunks that leave the pack's tile grid, returns NC_ERR_UNSUPPORTED.  The kernels follow a name's ring for at most
  * 64 alignments: the caller hands over no table with a longer ring (generate_indel_pileups.indel_mate_table refuses it).  (ABI 11: an added export.) */
 int nc_indel_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d_mate_key, const int32_t *d_mate_rec);
+
+/* Positions to genotype whatever their allele frequency (known-sites calling; ABI 11: an added export).  d_pos [n_sites]: 1-based positions of the
+ * scanned contig on the device, in any order, duplicates allowed; the pointer is borrowed and read by the following nc_snp_scan / nc_snp_scan_begin
+ * calls of the context (n_sites = 0 clears the list).  The candidate test of generate_SNP_pileups.py:183 becomes
+ * `min_allele_freq <= alt_freq or v_pos in list` (only = 0) or `v_pos in list` (only != 0); every other condition stays: depth >= mincov, an
+ * unmasked AGTC reference base outside the excluded intervals (:161,170), the chunk's [start, end].  A listed position does not become a neighbour
+ * site unless it passes that test on its own.  Positions outside the pack's tile grid are ignored.  Each scan builds a bitmap on the pack's tile
+ * grid from the list on the context's stream (one bit per column); the list itself must stay valid until the scan's kernels have run. */
+int nc_snp_scan_set_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, int32_t only);
 
 /* Per-site coverage scale (snpCaller.py:93-96, 170-173) for the sites of the last scan:
  * mode 0: scale[s] = train_coverage / mean(site_depth over the site's chunk) (chunk constant, quirk E2)

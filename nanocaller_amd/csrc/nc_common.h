@@ -69,6 +69,11 @@ struct nc_ctx {
     int32_t n_imates = 0;
     const int64_t *imate_key = nullptr;
     const int32_t *imate_rec = nullptr;
+    // positions to genotype (nc_snp_scan_set_sites): a borrowed device pointer, read by the next nc_snp_scan_begin calls, which build site_bits from it
+    int32_t n_gsites = 0;
+    const int32_t *gsite_pos = nullptr;
+    bool gsites_only = false;
+    DevBuf site_bits;                       // one bit per column of the scanned pack's tile grid (k_site_bits)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms[6] = {0, 0, 0, 0, 0, 0};   // 0 scan, 1 featurize, 2 cnn stage, 3 indel, 4 trunk kernel total, 5 trunk launches
     hipEvent_t kev[128] = {nullptr};          // per-launch event pairs of the trunk kernel (timing mode)

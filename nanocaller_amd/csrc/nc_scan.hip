@@ -25,13 +25,16 @@ struct ScanP {
     int32_t scan_lo, scan_hi;
 };
 
-template <int BLOCK>
+// SITES: a list of positions to genotype is set (nc_snp_scan_set_sites): site_bits holds one bit per column of the pack's tile grid (bit g = column
+// tile_pos0 + g, k_site_bits), a lane reads the 16 bits of its 16 positions as one aligned 16-bit load, and a listed column that passes every other
+// test of :161-170 is a candidate whatever its allele frequency.  The <.., false> form never reads site_bits and is the kernel of the plain scan.
+template <int BLOCK, bool SITES>
 __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ codes, const int32_t *__restrict__ tile_off,
                                                 const nc_tile_entry *__restrict__ tile_ent, int32_t tile_pos0,
                                                 const uint8_t *__restrict__ ref_code, ScanP sp,
                                                 int32_t *__restrict__ stage_nbr, int32_t *__restrict__ stage_cpos,
                                                 int32_t *__restrict__ stage_cn, int32_t *__restrict__ stage_calt,
-                                                int2 *__restrict__ tile_cnt)
+                                                int2 *__restrict__ tile_cnt, const uint16_t *__restrict__ site_bits)
 {
     constexpr int TILE = BLOCK * 16;
     const int t = blockIdx.x;
@@ -79,6 +82,8 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ code
     const uint4 rv = *reinterpret_cast<const uint4 *>(ref_code + (int64_t)t * TILE + threadIdx.x * 16);
     const uint32_t rw[4] = {rv.x, rv.y, rv.z, rv.w};
     uint32_t nbr_mask = 0, cand_mask = 0;
+    uint32_t listed = 0;
+    if constexpr (SITES) listed = site_bits[(int64_t)t * BLOCK + threadIdx.x];
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const int d = i >> 2, k = i & 3;
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ code
             const double f = (double)alt / (double)n;                 // alt_freq, float64 (:166)
             const bool nb = sp.haploid ? (sp.t0 <= f) : (sp.t0 <= f && f < sp.t1);   // :173 / :177
             if (nb) nbr_mask |= 1u << i;
-            if (sp.min_af <= f) cand_mask |= 1u << i;                 // :183 (chunk membership applied later)
+            if (sp.min_af <= f || (SITES && ((listed >> i) & 1))) cand_mask |= 1u << i;   // :183 (chunk membership applied later)
         }
     }
 
@@ -138,6 +143,19 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ code
         }
     }
     if (threadIdx.x == 0) tile_cnt[t] = make_int2((int)(total & 0xFFFF), (int)(total >> 16));
+}
+
+// The bitmap of the listed positions (nc_snp_scan_set_sites) on the pack's tile grid, from the position list in HBM: one thread per position, bit
+// g = pos - tile_pos0 of the zeroed bitmap set with an atomic OR (duplicates and order do not matter).  A position outside the grid's npos columns
+// (position 0, a negative one, one past the contig, one outside the span a rank's pack holds) is dropped, never written.
+__global__ __launch_bounds__(256) void k_site_bits(int32_t n, const int32_t *__restrict__ pos, int32_t tile_pos0, int64_t npos,
+                                                   uint32_t *__restrict__ bits)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = (int64_t)pos[i] - tile_pos0;
+    if (g < 0 || g >= npos) return;
+    atomicOr(&bits[g >> 5], 1u << (g & 31));
 }
 
 // single-workgroup exclusive scan of int2 counts (n_tiles is at most a few million).  A WAVE owns a contiguous sixteenth of the counts and walks it 64
@@ -315,6 +333,26 @@ int nc_selftest_device(nc_ctx *ctx)
     return NC_OK;
 }
 
+template <bool SITES>
+static void launch_scan(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_code_dev, const ScanP &sp)
+{
+    auto *sn = (int32_t *)ctx->stage_nbr.p;
+    auto *sc = (int32_t *)ctx->stage_cpos.p;
+    auto *scn = (int32_t *)ctx->stage_cn.p;
+    auto *sca = (int32_t *)ctx->stage_calt.p;
+    auto *tc = (int2 *)ctx->tile_cnt.p;
+    const auto *sb = SITES ? (const uint16_t *)ctx->site_bits.p : nullptr;
+    if (pack->tile_size == 1024)
+        hipLaunchKernelGGL((k_scan<64, SITES>), dim3(pack->n_tiles), dim3(64), 0, ctx->stream, pack->codes, pack->tile_off,
+                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb);
+    else if (pack->tile_size == 2048)
+        hipLaunchKernelGGL((k_scan<128, SITES>), dim3(pack->n_tiles), dim3(128), 0, ctx->stream, pack->codes, pack->tile_off,
+                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb);
+    else
+        hipLaunchKernelGGL((k_scan<256, SITES>), dim3(pack->n_tiles), dim3(256), 0, ctx->stream, pack->codes, pack->tile_off,
+                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb);
+}
+
 extern "C" {
 
 // The scan in two halves (round 6): nc_snp_scan_begin enqueues every kernel up to the candidate compaction and the copy of the totals into the pinned
@@ -383,21 +421,22 @@ int nc_snp_scan_begin(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_c
     sp.scan_lo = scan_lo;
     sp.scan_hi = scan_hi;
 
+    const bool listed = ctx->n_gsites > 0;
+    if (listed) {
+        NC_TRY(nc_ensure(ctx, ctx->site_bits, (size_t)(npos / 8)));  // (npos is a multiple of 1024: whole 32-bit words)
+        if (ctx->gsites_only) sp.min_af = 2.0;                       // alt <= n: the frequency test of :183 never fires, the list alone decides
+    }
     NcTimer tm(ctx, 0);
-    auto *sn = (int32_t *)ctx->stage_nbr.p;
-    auto *sc = (int32_t *)ctx->stage_cpos.p;
-    auto *scn = (int32_t *)ctx->stage_cn.p;
-    auto *sca = (int32_t *)ctx->stage_calt.p;
     auto *tc = (int2 *)ctx->tile_cnt.p;
-    if (tile == 1024)
-        hipLaunchKernelGGL(k_scan<64>, dim3(pack->n_tiles), dim3(64), 0, ctx->stream, pack->codes, pack->tile_off,
-                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc);
-    else if (tile == 2048)
-        hipLaunchKernelGGL(k_scan<128>, dim3(pack->n_tiles), dim3(128), 0, ctx->stream, pack->codes, pack->tile_off,
-                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc);
-    else
-        hipLaunchKernelGGL(k_scan<256>, dim3(pack->n_tiles), dim3(256), 0, ctx->stream, pack->codes, pack->tile_off,
-                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc);
+    if (listed) {
+        NC_HIP(ctx, hipMemsetAsync(ctx->site_bits.p, 0, (size_t)(npos / 8), ctx->stream));
+        hipLaunchKernelGGL(k_site_bits, dim3((ctx->n_gsites + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_gsites, ctx->gsite_pos,
+                           pack->tile_pos0, npos, (uint32_t *)ctx->site_bits.p);
+        NC_HIP(ctx, hipGetLastError());
+        launch_scan<true>(ctx, pack, ref_code_dev, sp);
+    } else {
+        launch_scan<false>(ctx, pack, ref_code_dev, sp);
+    }
     NC_HIP(ctx, hipGetLastError());
     tm.stop();
     hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, ctx->stream, tc, (int2 *)ctx->tile_pre.p, pack->n_tiles,
@@ -482,6 +521,16 @@ int nc_snp_scan(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_code_de
 {
     const int rc = nc_snp_scan_begin(ctx, pack, ref_code_dev, ref_pos0, ref_len, scan_lo, scan_hi, params, n_chunks, chunk_start_host, chunk_end_host);
     return rc != NC_OK ? rc : nc_snp_scan_end(ctx, n_nbr, n_cand, n_sites);
+}
+
+int nc_snp_scan_set_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, int32_t only)
+{
+    if (!ctx) return NC_ERR_ARG;
+    if (n_sites < 0 || (n_sites > 0 && !d_pos)) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_scan_set_sites: bad argument");
+    ctx->n_gsites = n_sites;
+    ctx->gsite_pos = n_sites ? d_pos : nullptr;
+    ctx->gsites_only = n_sites > 0 && only != 0;
+    return NC_OK;
 }
 
 static int scan_fetch(nc_ctx *ctx, hipStream_t st, bool wait, int32_t *nbr_pos, int32_t *site_pos, int32_t *site_chunk, int32_t *site_n,

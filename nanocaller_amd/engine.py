@@ -221,9 +221,24 @@ class Engine:
         self._loaded[kind] = w.path
 
     # ------------------------------------------------------------------ K1
-    def snp_scan(self, dp: DevicePack, chunks, *, mincov, min_allele_freq, threshold, haploid=False, async_fetch=False, between=None) -> SnpSites:
+    def snp_scan(self, dp: DevicePack, chunks, *, mincov, min_allele_freq, threshold, haploid=False, async_fetch=False, between=None,
+                 sites=None, sites_only=False) -> SnpSites:
         """chunks: list of (start, end) inclusive, same contig, ascending.  `between` (callable): run after the scan's kernels are enqueued and before
-        the host waits for the scan's totals (nc_snp_scan_begin / _end): what it enqueues keeps the GPU busy during that round trip."""
+        the host waits for the scan's totals (nc_snp_scan_begin / _end): what it enqueues keeps the GPU busy during that round trip.
+        sites (known-sites calling, nc_snp_scan_set_sites): 1-based positions of the contig (int array, or an int32 device tensor), any order,
+        duplicates allowed -- a listed column that passes every other test is a candidate whatever its allele frequency; sites_only: the list
+        alone decides (with no position in it, nothing is a candidate).  The list is cleared when the scan's kernels are enqueued."""
+        d_sites = None
+        if sites is not None:
+            if isinstance(sites, torch.Tensor):
+                d_sites = sites.to(device=self.device, dtype=torch.int32).contiguous()
+            else:
+                a = np.asarray(sites).astype(np.int64, copy=False).ravel()
+                a = a[(a >= 1) & (a <= np.iinfo(np.int32).max)]          # (no contig has other positions)
+                d_sites = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.device)
+            d_sites.record_stream(torch.cuda.current_stream(self.device))
+        if sites_only and (d_sites is None or d_sites.numel() == 0):
+            min_allele_freq = 2.0                                    # alt <= n: no column passes the frequency test, none is listed
         cs = np.ascontiguousarray([c[0] for c in chunks], np.int32)
         ce = np.ascontiguousarray([c[1] for c in chunks], np.int32)
         scan_lo = max(1, int(cs.min()) - _lib.FLANK)
@@ -233,8 +248,15 @@ class Engine:
         params = _lib.ScanParamsC(mincov=int(mincov), min_allele_freq=float(min_allele_freq), nbr_t0=float(threshold[0]),
                                   nbr_t1=float(threshold[1]), haploid=1 if haploid else 0)
         pc = dp.c_struct()
-        self._check(self.L.nc_snp_scan_begin(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, dp.ref_code.numel(), scan_lo,
-                                             scan_hi, C.byref(params), len(chunks), _lib.npp(cs), _lib.npp(ce)), "nc_snp_scan_begin")
+        listed = d_sites is not None and d_sites.numel() > 0
+        if listed:
+            self._check(self.L.nc_snp_scan_set_sites(self.ctx, int(d_sites.numel()), _ptr(d_sites), 1 if sites_only else 0), "nc_snp_scan_set_sites")
+        try:
+            self._check(self.L.nc_snp_scan_begin(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, dp.ref_code.numel(), scan_lo,
+                                                 scan_hi, C.byref(params), len(chunks), _lib.npp(cs), _lib.npp(ce)), "nc_snp_scan_begin")
+        finally:
+            if listed:                                               # the context never carries a list into a later call
+                self.L.nc_snp_scan_set_sites(self.ctx, 0, None, 0)
         if between is not None:
             between()                                                # enqueued behind the scan's kernels, ahead of the host's wait for its totals
         n_nbr, n_cand, n_sites = C.c_int32(), C.c_int32(), C.c_int32()

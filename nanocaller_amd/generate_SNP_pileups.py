@@ -249,8 +249,11 @@ def get_snp_testing_candidates(dct, region, device=0):
     eng = get_engine(device)
     eng.use_torch_stream()
     dp_ = device_pack_for(dct, chrom, device)
+    # known-sites calling (genotype_sites.py): dct['genotype_sites'] / dct['genotype_only'], read with .get -- the reference's dct has neither
+    from .genotype_sites import sites_for
+    listed, only = sites_for(dct, chrom)
     sites = eng.snp_scan(dp_, [(start, end)], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"],
-                         threshold=dct["threshold"], haploid=(ploidy == "haploid"))
+                         threshold=dct["threshold"], haploid=(ploidy == "haploid"), sites=listed, sites_only=only)
     empty = ([], [], [], [], [], 0, [], [])
     if sites.n_sites == 0:
         return empty

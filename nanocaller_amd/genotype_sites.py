@@ -1,0 +1,85 @@
+"""Known-sites calling: the list of SNP positions a run is asked to genotype ("Genotyping a given list of sites").
+
+`dct['genotype_sites']` / `params['genotype_sites']` is a VCF path (plain, gzipped or bgzipped) or a `{contig: positions}` dict;
+`genotype_only` truthy makes the list the only source of candidates.  Without the keys the environment's NC_GENOTYPE_SITES /
+NC_GENOTYPE_ONLY=1 are read, so the reference's `run(args)`, which builds the dicts itself, can drive the mode.  The candidate test
+of generate_SNP_pileups.py:183 then reads `min_allele_freq <= alt_freq or v_pos in S` (or `v_pos in S` alone); the scan kernel
+applies it (nc_snp_scan_set_sites), nothing downstream changes.
+"""
+from __future__ import annotations
+
+import os
+import threading
+
+import numpy as np
+
+_EMPTY = np.zeros(0, np.int32)
+_VCFS = {}                    # (path, size, mtime) -> ({contig: sorted unique int32 positions}, data lines skipped)
+_LOCK = threading.Lock()
+
+
+def parse_sites_vcf(path):
+    """-> ({contig: sorted unique int32 POS}, n_skipped): every data line with a one-base REF contributes its POS, whatever its ALT;
+    the others (indels, MNPs, malformed lines) are skipped and counted"""
+    from .vcfio import read_vcf_gz
+    _, recs = read_vcf_gz(path)
+    by_contig, skipped = {}, 0
+    for ln in recs:
+        f = ln.split("\t", 5)
+        if len(f) < 5 or len(f[3]) != 1 or not f[1].isdigit():
+            skipped += bool(ln.strip())
+            continue
+        by_contig.setdefault(f[0], []).append(int(f[1]))
+    lim = np.iinfo(np.int32).max
+    out = {}
+    for c, p in by_contig.items():
+        a = np.unique(np.asarray(p, np.int64))
+        out[c] = a[(a >= 1) & (a <= lim)].astype(np.int32)
+    return out, skipped
+
+
+def load_sites_vcf(path):
+    """parse_sites_vcf, once per file (keyed by path, size and modification time)"""
+    path = str(path)
+    st = os.stat(path)
+    key = (path, st.st_size, st.st_mtime_ns)
+    with _LOCK:
+        hit = _VCFS.get(key)
+    if hit is None:
+        hit = parse_sites_vcf(path)
+        with _LOCK:
+            for k in [k for k in _VCFS if k[0] == path]:
+                del _VCFS[k]
+            _VCFS[key] = hit
+    return hit
+
+
+def sites_for(dct, chrom):
+    """-> (positions, only): the sorted unique int32 positions listed for `chrom` (None when no list is given at all) and whether
+    the list alone decides.  A list that names no position of `chrom` is an empty array: in only mode that contig yields nothing."""
+    src = dct.get("genotype_sites") if "genotype_sites" in dct else (os.environ.get("NC_GENOTYPE_SITES") or None)
+    if src is None or (isinstance(src, str) and not src):
+        return None, False
+    only = bool(dct["genotype_only"]) if "genotype_only" in dct else os.environ.get("NC_GENOTYPE_ONLY") == "1"
+    if isinstance(src, dict):
+        p = src.get(chrom)
+        if p is None:
+            return _EMPTY, only
+        a = np.unique(np.asarray(p).astype(np.int64, copy=False).ravel())
+        return a[(a >= 1) & (a <= np.iinfo(np.int32).max)].astype(np.int32), only
+    return load_sites_vcf(src)[0].get(chrom, _EMPTY), only
+
+
+def count_listed(sites, chunks, emitted_pos):
+    """-> (listed, emitted): how many listed positions lie inside one of `chunks` ((start, end) inclusive), and how many of those are
+    among `emitted_pos` (the positions that got a record).  listed - emitted positions failed a test of :161-170 or had no tensor."""
+    if sites is None or sites.size == 0:
+        return 0, 0
+    inside = np.zeros(sites.size, bool)
+    for a, b in chunks:
+        inside[np.searchsorted(sites, a, "left"):np.searchsorted(sites, b, "right")] = True
+    s = sites[inside]
+    return int(s.size), int(np.isin(s, np.asarray(emitted_pos)).sum()) if s.size else 0
+
+
+__all__ = ["parse_sites_vcf", "load_sites_vcf", "sites_for", "count_listed"]

@@ -205,6 +205,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     """Run pileup featurisation + CNN for a list of chunks of ONE contig and ploidy on the GPU.
     `dpk`: alignments already resident in HBM (engine.DevicePack); default: packed from params['sam_path'].
     -> dict of host arrays (pos, chunk, ref, probs, gt, dp, freq, fwd_dp, rev_dp, chunk_depth).
+    params['genotype_sites'] / params['genotype_only'] (genotype_sites.py; both optional): positions to genotype whatever their allele
+    frequency; the result then counts them: genotype_listed = listed positions inside these chunks, genotype_emitted = those with a record.
     defer=True -> PendingCall: returns once the group's work is handed over; the caller starts the next group and collects result() afterwards.
     pipeline (NC_PIPE_CNN=1; OFF by default): this group's CNN is not enqueued by this call but INSIDE the next call's scan (nc_snp_scan_begin ->
     the pending CNN -> nc_snp_scan_end), or by result() / flush_pending_cnn() if no call follows: the host's round trip for the next scan's totals
@@ -237,10 +239,14 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
         dpk = device_pack_for(params, chrom, device, span=contig_span(params['sam_path'], chrom, chunks))
     # Results drain on a second stream while the GPU keeps computing: the candidate arrays right after the scan, the
     # featuriser's per-site arrays during the CNN, and every CNN batch's probabilities while the next batch runs.
-    sites = eng.snp_scan(dpk, [(c['start'], c['end']) for c in chunks], mincov=params['mincov'],
+    from .genotype_sites import count_listed, sites_for
+    listed, only = sites_for(params, chrom)
+    spans = [(c['start'], c['end']) for c in chunks]
+    sites = eng.snp_scan(dpk, spans, mincov=params['mincov'],
                          min_allele_freq=params['min_allele_freq'], threshold=params['threshold'],
-                         haploid=(ploidy == 'haploid'), async_fetch=True, between=(lambda: flush_pending_cnn(device)) if pipeline else None)
-    res = dict(chrom=chrom, ploidy=ploidy, n=0)
+                         haploid=(ploidy == 'haploid'), async_fetch=True, between=(lambda: flush_pending_cnn(device)) if pipeline else None,
+                         sites=listed, sites_only=only)
+    res = dict(chrom=chrom, ploidy=ploidy, n=0, genotype_listed=count_listed(listed, spans, ())[0], genotype_emitted=0)
     if sites.n_sites == 0:
         eng.wait_copies()
         return PendingCall(lambda: res) if defer else res
@@ -309,6 +315,7 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
             out = {k: (v[m] if v is not None else None) for k, v in out.items()}
         # host arrays keep the device dtypes (int32 / float32)
         res.update(out, n=int(out['pos'].shape[0]), chunk_depth=chunk_depth)
+        res['genotype_listed'], res['genotype_emitted'] = count_listed(listed, spans, out['pos'])
         return res
     return PendingCall(finish) if defer else finish()
 
@@ -380,11 +387,14 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
 
     with open(curr_vcf_path, 'wb') as f, ThreadPoolExecutor(max_workers=1) as pool:
         pending, in_flight = None, []                                # groups whose kernels are queued and whose results have not been collected
+        unrecorded = {}                                              # contig -> listed positions (params['genotype_sites']) inside its chunks that got no record
 
         def collect():
             nonlocal pending
             chrom, ploidy, call, grp, gi = in_flight.pop(0)
             r = call.result()
+            if r.get('genotype_listed'):
+                unrecorded[chrom] = unrecorded.get(chrom, 0) + r['genotype_listed'] - r['genotype_emitted']
             if pending is not None:
                 pending.result()                                    # keeps the records in group order; re-raises errors
             pending = pool.submit(emit, f, chrom, ploidy, r, grp)
@@ -507,6 +517,9 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
             collect()
         if pending is not None:
             pending.result()
+        if not params.get('suppress_progress'):
+            for chrom_, n_ in unrecorded.items():                    # (below mincov, a masked / non-AGTC / excluded reference base, no tensor)
+                print('%s: %s: %d listed sites got no record (not eligible for a pileup).' % (str(datetime.datetime.now()), chrom_, n_), flush=True)
         if piped and keys:
             prep_pool.shutdown(wait=True)
         if dbam is not None:
