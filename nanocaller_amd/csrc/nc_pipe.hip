@@ -271,8 +271,15 @@ extern "C" int nc_indel_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d
 extern "C" int nc_indel_sites_scoring(nc_ctx *ctx, int32_t open, int32_t extend, int32_t match, int32_t mismatch)
 {
     if (!ctx) return NC_ERR_ARG;
-    // the packed 16-bit fill keeps |scores| below 2^15: 272 matches and 1,300 gap extensions must fit
-    if (open < 0 || extend < 0 || open > 100 || extend > 10 || match < 0 || match > 100 || mismatch > 0 || mismatch < -100)
+    // The packed 16-bit fills keep every value, and every difference whose sign bit becomes a traceback bit, inside int16.  The binding one is
+    // k_fill_band: its registers carry the bias 20,000 (minus infinity = 0), and the largest value it forms is the diagonal candidate
+    // H[i-1][j-1] + match + 20,000 <= match * min(n1, n2) + 20,000 with min(n1, n2) <= 272 (the longest window the plan takes; cells outside the
+    // rectangle never match).  It must stay <= 32,767 - extend, so that the difference against a fresh minus infinity on the band's border,
+    // (0 - extend) - H', is above -2^15: match * 273 <= 12,767, match <= 46.  (match = 100, accepted until now, wraps on the band after 128
+    // matching bases.)  The lower side has room: inside a band a path reaches any cell by gaps of at most 15, so H >= -(272 / 15) * 2 *
+    // (open + 14 extend) - open > -9,000 at the limits below, and the chains of -extend outside the rectangle stay above -20,000 - 600 extend.
+    // k_fill16q has no bias: |H - open| <= 46 * 272, and its minus infinity (-20,000 - extend) only meets column 0 and row 0, which are <= 0.
+    if (open < 0 || extend < 0 || open > 100 || extend > 10 || match < 0 || match > 46 || mismatch > 0 || mismatch < -100)
         return nc_fail(ctx, NC_ERR_ARG, "nc_indel_sites_scoring: scores out of the range the 16-bit aligner covers");
     if (!ctx->pipe) ctx->pipe = new (std::nothrow) nc_pipe_state();
     if (!ctx->pipe) return NC_ERR_NOMEM;

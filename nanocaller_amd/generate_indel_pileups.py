@@ -605,11 +605,12 @@ def device_indel_reads(ctg, flag, dp, device):
 
 
 def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, win_size, small_win_size, ins_t, del_t, window_after,
-                       haploid=False, excl=None, fetch=True, impute=False, mates=None):
+                       haploid=False, excl=None, fetch=True, impute=False, mates=None, scoring=None):
     """nc_indel_sites_plan + _run (+ _fetch) for a list of (start, end) chunks of one contig -> dict: n, x (device float32
     [n, sets * 5, 128, 2]: the CNN input), and with fetch: pos / chunk / type / phase int32 [n], ref_len / alt_len int32 [n, sets],
     alt (uint8 codes, the ALT prefixes back to back in (site, set) order).  mates: indel_mate_table's (key, rec) when kept alignments share read
-    names.  Raises NanoCallerHipError with .status."""
+    names.  scoring: the star alignment's (gap open, gap extend, match, mismatch), default _lib.STAR_SCORING; nc_indel_sites_scoring refuses values
+    the 16-bit aligners do not cover.  Raises NanoCallerHipError with .status."""
     L = eng.L
     prm = _lib.IndelScanParamsC(mincov=int(mincov), win_size=int(win_size), small_win_size=int(small_win_size), ins_t=float(ins_t),
                                 del_t=float(del_t), haploid=1 if haploid else 0, impute=1 if (impute and not haploid) else 0)
@@ -624,7 +625,7 @@ def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, w
             err = _lib.NanoCallerHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
             err.status = rc
             raise err
-    check(L.nc_indel_sites_scoring(eng.ctx, *[int(v) for v in _lib.STAR_SCORING]), "nc_indel_sites_scoring")
+    check(L.nc_indel_sites_scoring(eng.ctx, *[int(v) for v in (_lib.STAR_SCORING if scoring is None else scoring)]), "nc_indel_sites_scoring")
     # alignments that share read names: the plan keys them by name from this table (none: no table, the plain kernels run).  The context borrows
     # the pointers, so the table is cleared again once the plan's and the run's launches are enqueued, whatever their outcome
     check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,

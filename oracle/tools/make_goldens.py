@@ -13,6 +13,7 @@ synthetic worlds; what is committed is DATA: the world arrays (inputs) and the r
   indel_msa.npz            msa() tensors (generate_indel_pileups.py:12-73) on canned MUSCLE output
   indel_scan*.npz          `variants` of pass 1 (:197-276, haploid :185-241) captured from the reference's frame
   indel_impute.npz         `variants` + `extra_variants` of pass 1 with impute_indel_phase (:278-304)
+  allele_prediction_ties.json   allele_prediction (:77-127) on the tie-heavy pairs of tests/align_cases.py (`allele_ties` writes it alone)
 """
 import io
 import os
@@ -699,6 +700,41 @@ def make_pass2_goldens():
         json.dump(dict(n_pipeline=n_pipeline, calls=calls), f)
     print("allele_prediction cases: %d from the pipeline + %d seeded (%d (None, None), %d raised)" % (
         n_pipeline, len(calls) - n_pipeline, sum(1 for c in calls if c[3] is None), sum(1 for c in calls if isinstance(c[3], str) and c[3].startswith("!"))))
+    _allele_ties_block(ref_ap)
+
+
+def _allele_ties_block(ref_ap):
+    """The reference's allele_prediction on the tie-heavy (consensus, window, max_range) pairs of tests/align_cases.py (homopolymers, tandem
+    repeats, runs in a flank, two-letter and disjoint sequences, the shape edges, per lane layout of the device aligner) -> its own file,
+    tests/golden/allele_prediction_ties.json: {call name: [[alt, ref_seq, max_range, REF, ALT]]}, an exception as "!" + its type name."""
+    import json
+
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import align_cases
+    out, n, n_none, n_raised = {}, 0, 0, 0
+    for name, (alts, refs, mrs) in align_cases.allele_calls().items():
+        rows = []
+        for alt, ref, mr in zip(alts, refs, mrs):
+            try:
+                r = ref_ap(alt, ref, mr)
+                rows.append([alt, ref, int(mr), r[0], r[1]])
+                n_none += r[0] is None
+            except Exception as e:
+                rows.append([alt, ref, int(mr), "!" + type(e).__name__, None])
+                n_raised += 1
+        out[name] = rows
+        n += len(rows)
+    with open(os.path.join(OUT, "allele_prediction_ties.json"), "w") as f:
+        json.dump(dict(calls=out), f)
+    print("allele_prediction tie cases: %d in %d calls (%d (None, None), %d raised)" % (n, len(out), n_none, n_raised))
+
+
+def make_allele_ties_golden():
+    """_allele_ties_block alone (make_pass2_goldens runs it too): the reference's unchanged allele_prediction over the oracle aligner,
+    without rewriting indel_pass2.npz / allele_prediction.json"""
+    from nanocaller_src import generate_indel_pileups as ref_indel
+    _install_aligner_stubs(ref_indel)
+    _allele_ties_block(ref_indel.allele_prediction)
 
 
 # ----------------------------------------------------------------------------- CNNs through the reference's own call()
@@ -909,6 +945,8 @@ if __name__ == "__main__":
         make_indel_impute_goldens()
     if "pass2" in what:
         make_pass2_goldens()
+    elif "allele_ties" in what:
+        make_allele_ties_golden()
     if "cnn" in what:
         make_cnn_goldens()
     if "e2e" in what:

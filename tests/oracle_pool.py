@@ -10,21 +10,23 @@ from oracle import oracle
 MAX_WORKERS = 8
 
 
-def site_task(p, recs, hap, ps, ref, window_after, mincov, maxcov, haploid=False, band=True):
+def site_task(p, recs, hap, ps, ref, window_after, mincov, maxcov, haploid=False, band=True, scoring=None):
     """the arguments of one site_ref call: `ref` is the contig's reference (1-based positions as a string's offsets + 1); only the window
     of the site travels"""
     end = min(len(ref), p + window_after + 1)
-    return (p, recs, [int(v) for v in hap], [int(v) for v in ps], p - 1, ref[p - 1:end], window_after, mincov, maxcov, haploid, band)
+    return (p, recs, [int(v) for v in hap], [int(v) for v in ps], p - 1, ref[p - 1:end], window_after, mincov, maxcov, haploid, band) + (
+        (tuple(scoring),) if scoring is not None else ())
 
 
 def site_ref(task):
     """-> None when the site fails the oracle's set-size tests, else dict: x, cns, win, phase, and per alignment of the star alignment
     (set by set, as indel_site_ref aligns them): record index, window length, how it was aligned (32 / 64 / 'width' / 'edge') and the band
     (lo, B) or None its CIGAR gives"""
-    p, recs, hap, ps, off, piece, window_after, mincov, maxcov, haploid, band = task
+    p, recs, hap, ps, off, piece, window_after, mincov, maxcov, haploid, band = task[:11]
+    kw = dict(scoring=task[11]) if len(task) > 11 else {}                 # (the star alignment's scoring; default: oracle.indel_site_ref's own)
     ref = "N" * off + piece
     how, reads = [], []
-    got = oracle.indel_site_ref(recs, hap, ps, ref, p, window_after, mincov, maxcov, haploid=haploid, band=band, how_out=how, reads_out=reads)
+    got = oracle.indel_site_ref(recs, hap, ps, ref, p, window_after, mincov, maxcov, haploid=haploid, band=band, how_out=how, reads_out=reads, **kw)
     if got is None:
         return None
     x, cns, win, phase = got
