@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
+from contextlib import contextmanager
 from dataclasses import dataclass
 
 import numpy as np
@@ -110,6 +111,7 @@ class Engine:
         self.ctx = ctx
         self._loaded = {}
         self._pinned = _PinnedPool()
+        self.x_int16 = self.exact_fp32 = False              # the library's defaults (set_tensor_format / set_cnn_precision)
         self.use_torch_stream()
 
     def close(self):
@@ -134,7 +136,6 @@ class Engine:
         stream the library used a stream of its own beside it, and every torch kernel in a pass cost two cross-queue hand-overs (~0.4 ms of idle GPU
         per 11 ms contig pass: bench.py 56.0 -> 58.2 M sites/s; `rocprofv3 --kernel-trace` timelines by tools/one_pass.py).  Work the caller has
         already enqueued on the default stream is waited for.  NC_ONE_QUEUE=0: the old arrangement."""
-        import os
         s = torch.cuda.current_stream(self.device)
         if s.cuda_stream == 0 and os.environ.get("NC_ONE_QUEUE", "1") != "0":
             if getattr(self, "_tstream", None) is None:
@@ -149,7 +150,6 @@ class Engine:
         stream (one hardware queue); the CONTEXT's launch stream is left alone (get_engine used to call use_torch_stream(), which rewrites
         the shared ctx->stream -- a worker thread could retarget another thread's launches between its `with torch.cuda.stream(...)` and its kernel).
         Only an explicit use_torch_stream() retargets the context."""
-        import os
         s = torch.cuda.current_stream(self.device)
         if s.cuda_stream == 0 and os.environ.get("NC_ONE_QUEUE", "1") != "0" and getattr(self, "_tstream", None) is not None:
             self._tstream.wait_stream(s)
@@ -161,18 +161,42 @@ class Engine:
         self.exact_fp32 = bool(exact_fp32)
 
     def set_tensor_format(self, int16: bool):
-        """SNP tensors between snp_featurize and snp_forward as int16 (exact: every entry is a small integer; half the
-        bytes) instead of the reference's float32.  Read by the split-precision trunk only."""
+        """The engine's default tensor format: what snp_featurize(int16=None) writes and what trunk_info() reports for -- int16 (exact: every
+        entry is a small integer; half the bytes) instead of the reference's float32.  snp_forward does not read it: a tensor's dtype says
+        which it is."""
         self._check(self.L.nc_set_tensor_format(self.ctx, 1 if int16 else 0), "nc_set_tensor_format")
         self.x_int16 = bool(int16)
 
+    @contextmanager
+    def _snp_state(self, int16=None, exact_fp32=None, range_flags=None):
+        """The context's tensor format, CNN precision (None: as they stand) and range watch (nc_cnn_range_watch; None: none) for ONE library
+        call; what was there before is put back, also when the call raises.  The only place that saves and restores this state."""
+        was_i16, was_exact = self.x_int16, self.exact_fp32
+        try:
+            if int16 is not None and bool(int16) != was_i16:
+                self.set_tensor_format(int16)
+            if exact_fp32 is not None and bool(exact_fp32) != was_exact:
+                self.set_cnn_precision(exact_fp32)
+            if range_flags is not None:
+                self._check(self.L.nc_cnn_range_watch(self.ctx, C.c_void_p(range_flags.data_ptr())), "nc_cnn_range_watch")
+            yield
+        finally:
+            if range_flags is not None:                              # (no watch outlives a call: there was none before)
+                self.L.nc_cnn_range_watch(self.ctx, None)
+            if self.exact_fp32 != was_exact:
+                self.set_cnn_precision(was_exact)
+            if self.x_int16 != was_i16:
+                self.set_tensor_format(was_i16)
+
     TRUNK_KERNELS = {0: "k4_conv12", 2: "k5_trunk_p3", 3: "k5_trunk_lin"}
 
-    def trunk_info(self):
-        """-> (v_mfma_f32_16x16x32_f16 instructions per site, kernel name) of the SNP trunk the next snp_forward of this context launches (it depends
-        on the tensor format and the precision mode): k5_trunk_p3 13 x 24 + 10 x 27 + 8 x 18 = 726, k5_trunk_lin (int16 tensors) 613"""
+    def trunk_info(self, int16=None):
+        """-> (v_mfma_f32_16x16x32_f16 instructions per site, kernel name) of the SNP trunk a snp_forward launches in the current precision mode for
+        int16 (True) or float32 (False) tensors; None: for the engine's default format.  k5_trunk_p3 13 x 24 + 10 x 27 + 8 x 18 = 726, k5_trunk_lin
+        (int16 tensors) 613"""
         n, k = C.c_int32(), C.c_int32()
-        self._check(self.L.nc_snp_trunk_info(self.ctx, C.byref(n), C.byref(k)), "nc_snp_trunk_info")
+        with self._snp_state(int16=int16):
+            self._check(self.L.nc_snp_trunk_info(self.ctx, C.byref(n), C.byref(k)), "nc_snp_trunk_info")
         return int(n.value), self.TRUNK_KERNELS[int(k.value)]
 
     def trunk_mfma_per_site(self) -> int:
@@ -221,10 +245,9 @@ class Engine:
         self._loaded[kind] = w.path
 
     # ------------------------------------------------------------------ K1
-    def snp_scan(self, dp: DevicePack, chunks, *, mincov, min_allele_freq, threshold, haploid=False, async_fetch=False, between=None,
-                 sites=None, sites_only=False) -> SnpSites:
-        """chunks: list of (start, end) inclusive, same contig, ascending.  `between` (callable): run after the scan's kernels are enqueued and before
-        the host waits for the scan's totals (nc_snp_scan_begin / _end): what it enqueues keeps the GPU busy during that round trip.
+    def snp_scan(self, dp: DevicePack, chunks, *, mincov, min_allele_freq, threshold, haploid=False, async_fetch=False, sites=None,
+                 sites_only=False) -> SnpSites:
+        """chunks: list of (start, end) inclusive, same contig, ascending.
         sites (known-sites calling, nc_snp_scan_set_sites): 1-based positions of the contig (int array, or an int32 device tensor), any order,
         duplicates allowed -- a listed column that passes every other test is a candidate whatever its allele frequency; sites_only: the list
         alone decides (with no position in it, nothing is a candidate).  The list is cleared when the scan's kernels are enqueued."""
@@ -257,8 +280,6 @@ class Engine:
         finally:
             if listed:                                               # the context never carries a list into a later call
                 self.L.nc_snp_scan_set_sites(self.ctx, 0, None, 0)
-        if between is not None:
-            between()                                                # enqueued behind the scan's kernels, ahead of the host's wait for its totals
         n_nbr, n_cand, n_sites = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self.L.nc_snp_scan_end(self.ctx, C.byref(n_nbr), C.byref(n_cand), C.byref(n_sites)), "nc_snp_scan_end")
         N = n_sites.value
@@ -280,20 +301,14 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ K2-K4
-    def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1) -> SnpSites:
+    def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1, int16=None) -> SnpSites:
+        """int16: sites.x as int16 (True) or as the reference's float32 (False); None: the engine's default (set_tensor_format)"""
         N = sites.n_sites
         dev = self.device
-        if dp.mates is not None and not getattr(self, "x_int16", False):
-            # alignments that share read names are keyed by name in the int16-tensor kernel only: run it, hand the tensors on as float32 (exact)
-            self.set_tensor_format(int16=True)
-            try:
-                self.snp_featurize(dp, sites, seq=seq, maxcov=maxcov, min_nbr_sites=min_nbr_sites)
-            finally:
-                self.set_tensor_format(int16=False)
-            sites.x = sites.x.to(torch.float32)
-            return sites
+        want16 = self.x_int16 if int16 is None else bool(int16)
+        # alignments that share read names are keyed by name in the int16-tensor kernel only: it runs, float32 tensors are its cast (exact)
+        i16 = want16 or dp.mates is not None
         # one allocation carved into the six outputs (this sits between the scan's totals and the featuriser's launch: the GPU idles)
-        i16 = getattr(self, "x_int16", False)
         xb = N * 1025 * (2 if i16 else 4)
         a16 = lambda v: (v + 15) & ~15     # noqa: E731
         o_ref = a16(xb); o_fwd = a16(o_ref + 4 * N); o_rev = a16(o_fwd + 16 * N); o_dep = a16(o_rev + 16 * N); o_val = a16(o_dep + 4 * N)
@@ -308,13 +323,16 @@ class Engine:
         if dp.mates is not None:                                     # alignments that share read names: the featuriser keys them by name
             self._check(self.L.nc_snp_set_mates(self.ctx, int(dp.mates[0].numel()), _ptr(dp.mates[0]), _ptr(dp.mates[1])), "nc_snp_set_mates")
         try:
-            self._check(self.L.nc_snp_featurize(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, dp.ref_code.numel(),
-                                                _lib.SEQ_MODES[seq], int(maxcov), int(min_nbr_sites), _ptr(sites.x),
-                                                _ptr(sites.ref_code), _ptr(sites.fwd_dp), _ptr(sites.rev_dp), _ptr(sites.depth),
-                                                _ptr(sites.valid)), "nc_snp_featurize")
+            with self._snp_state(int16=i16):
+                self._check(self.L.nc_snp_featurize(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, dp.ref_code.numel(),
+                                                    _lib.SEQ_MODES[seq], int(maxcov), int(min_nbr_sites), _ptr(sites.x),
+                                                    _ptr(sites.ref_code), _ptr(sites.fwd_dp), _ptr(sites.rev_dp), _ptr(sites.depth),
+                                                    _ptr(sites.valid)), "nc_snp_featurize")
         finally:
             if dp.mates is not None:
                 self.L.nc_snp_set_mates(self.ctx, 0, None, None)
+        if not want16 and i16:
+            sites.x = sites.x.to(torch.float32)
         return sites
 
     def snp_scale(self, sites: SnpSites, n_chunks, train_coverage, per_site=False, async_fetch=False):
@@ -355,16 +373,10 @@ class Engine:
 
     def range_rerun(self, kind, x, ref_code, scale, scale_mode, idx, probs, gt):
         """the sites `idx` (device int64) once more on the exact fp32 MFMA trunk; their rows of probs / gt (device tensors) are replaced"""
-        was_exact, was_i16 = getattr(self, "exact_fp32", False), getattr(self, "x_int16", False)
         xs = x[idx].to(torch.float32).contiguous()                   # the exact trunk reads the reference's float32 layout
-        self.set_tensor_format(int16=False)
-        self.set_cnn_precision(exact_fp32=True)
-        try:
+        with self._snp_state(exact_fp32=True):
             p2, g2 = self.snp_forward(kind, xs, ref_code[idx].contiguous(), scale[idx].contiguous() if scale is not None else None, scale_mode,
                                       want_gt=gt is not None)
-        finally:
-            self.set_cnn_precision(exact_fp32=was_exact)
-            self.set_tensor_format(int16=was_i16)
         probs[idx] = p2
         if gt is not None and g2 is not None:
             gt[idx] = g2
@@ -372,30 +384,26 @@ class Engine:
     def snp_forward(self, kind, x, ref_code, scale, scale_mode=0, want_gt=True, drain=False, range_flags=None):
         """-> (probs, gt) device tensors; with drain=True also (probs_host, gt_host) numpy arrays in pinned memory that
         the copy stream fills batch by batch while the next batch computes (wait_copies() before reading them).
+        x: int16 tensors (the featuriser's exact short form) or the reference's float32 layout -- its dtype says which, the engine's default
+        format plays no part.
         range_flags (uint8 device tensor [n], zeroed): the split-precision trunk marks the sites whose scaled tensor exceeds the
         model's x_limit (nc_cnn_range_watch)."""
+        if x.dtype not in (torch.int16, torch.float32):
+            raise ValueError("snp_forward: tensors of dtype %s (int16 or float32 expected)" % x.dtype)
         n = int(x.shape[0])
-        if range_flags is not None:
-            self._check(self.L.nc_cnn_range_watch(self.ctx, C.c_void_p(range_flags.data_ptr())), "nc_cnn_range_watch")
-        try:
-            return self._snp_forward(kind, x, ref_code, scale, scale_mode, want_gt, drain, n)
-        finally:
-            if range_flags is not None:
-                self.L.nc_cnn_range_watch(self.ctx, None)
-
-    def _snp_forward(self, kind, x, ref_code, scale, scale_mode, want_gt, drain, n):
         probs = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         gt = torch.empty((n, 2), dtype=torch.float32, device=self.device) if (want_gt and kind == _lib.MODEL_SNP) else None
-        if not drain:
-            self._check(self.L.nc_snp_forward(self.ctx, kind, n, _ptr(x), _ptr(ref_code), _ptr(scale), int(scale_mode),
-                                              _ptr(probs), _ptr(gt)), "nc_snp_forward")
-            return probs, gt
-        hp, hp_np = self._pinned.get((n, 4), torch.float32)
-        hg, hg_np = self._pinned.get((n, 2), torch.float32) if gt is not None else (None, None)
-        self._check(self.L.nc_snp_forward_drain(self.ctx, kind, n, _ptr(x), _ptr(ref_code), _ptr(scale), int(scale_mode),
-                                                _ptr(probs), _ptr(gt), self._copy_stream_ptr(), C.c_void_p(hp.data_ptr()),
-                                                C.c_void_p(hg.data_ptr()) if hg is not None else None), "nc_snp_forward_drain")
-        return probs, gt, hp_np, hg_np
+        with self._snp_state(int16=x.dtype == torch.int16, range_flags=range_flags):
+            if not drain:
+                self._check(self.L.nc_snp_forward(self.ctx, kind, n, _ptr(x), _ptr(ref_code), _ptr(scale), int(scale_mode),
+                                                  _ptr(probs), _ptr(gt)), "nc_snp_forward")
+                return probs, gt
+            hp, hp_np = self._pinned.get((n, 4), torch.float32)
+            hg, hg_np = self._pinned.get((n, 2), torch.float32) if gt is not None else (None, None)
+            self._check(self.L.nc_snp_forward_drain(self.ctx, kind, n, _ptr(x), _ptr(ref_code), _ptr(scale), int(scale_mode),
+                                                    _ptr(probs), _ptr(gt), self._copy_stream_ptr(), C.c_void_p(hp.data_ptr()),
+                                                    C.c_void_p(hg.data_ptr()) if hg is not None else None), "nc_snp_forward_drain")
+            return probs, gt, hp_np, hg_np
 
     def indel_forward(self, kind, x):
         n = int(x.shape[0])
@@ -749,7 +757,6 @@ def get_engine(device: int = 0) -> Engine:
 def local_device(devices=None, rank=0) -> int:
     """GPU of this process: one process per GPU.  `devices` (a sequence) is indexed by the local rank; by default the local
     rank itself (LOCAL_RANK from torchrun, else the global rank) modulo the number of visible devices."""
-    import os
     local = int(os.environ.get("LOCAL_RANK", rank))
     if devices:
         return int(devices[local % len(devices)])

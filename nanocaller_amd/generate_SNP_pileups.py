@@ -181,6 +181,12 @@ def contig_span(sam_path, chrom, chunks):
         length = bf.get_reference_length(chrom)
     finally:
         bf.close()
+    return span_of(chunks, length)
+
+
+def span_of(chunks, length):
+    """contig_span's rule on a contig of `length` bases: (lo, hi) = the chunks' extent +- _lib.FLANK inside [1, length], None where that
+    covers at least 90 % of the contig"""
     lo = max(1, min(c['start'] for c in chunks) - _lib.FLANK)
     hi = min(length, max(c['end'] for c in chunks) + _lib.FLANK)
     return None if (hi - lo + 1) >= 0.9 * length else (lo, hi)

@@ -191,16 +191,6 @@ class PendingCall:
         return self._res
 
 
-_PENDING_CNN = {}                  # device -> the CNN launch of the previous deferred call_chunks (enqueued inside the next call's scan, or on demand)
-
-
-def flush_pending_cnn(device=0):
-    """enqueue the CNN a pipelined call_chunks left pending on `device` (no-op when there is none)"""
-    f = _PENDING_CNN.pop(device, None)
-    if f is not None:
-        f()
-
-
 def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     """Run pileup featurisation + CNN for a list of chunks of ONE contig and ploidy on the GPU.
     `dpk`: alignments already resident in HBM (engine.DevicePack); default: packed from params['sam_path'].
@@ -208,15 +198,10 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     params['genotype_sites'] / params['genotype_only'] (genotype_sites.py; both optional): positions to genotype whatever their allele
     frequency; the result then counts them: genotype_listed = listed positions inside these chunks, genotype_emitted = those with a record.
     defer=True -> PendingCall: returns once the group's work is handed over; the caller starts the next group and collects result() afterwards.
-    pipeline (NC_PIPE_CNN=1; OFF by default): this group's CNN is not enqueued by this call but INSIDE the next call's scan (nc_snp_scan_begin ->
-    the pending CNN -> nc_snp_scan_end), or by result() / flush_pending_cnn() if no call follows: the host's round trip for the next scan's totals
-    (~0.2 ms) then runs under 8 ms of CNN instead of beside an idle GPU.  Device order scan(k+1), CNN(k), tensors(k+1),
-    scan(k+2), CNN(k+1) ...; same results.  Measured: 10.55 -> 11.2 ms per contig (the scan's and the featuriser's result copies -- blit kernels on this
-    platform -- then collide with the trunk instead of running in the gap they filled): not the default (profiles/README.md, round 6)."""
-    if pipeline is None:
-        pipeline = bool(defer) and os.environ.get('NC_PIPE_CNN', '0') == '1'
-    if not pipeline:
-        flush_pending_cnn(device)                                    # keep the device order of calls that do not take part
+    pipeline: None or False.  True asked for a removed path (a group's CNN enqueued inside the next call's scan; measured slower, 10.55 ->
+    11.2 ms per contig: profiles/README.md, round 6) and raises."""
+    if pipeline:
+        raise ValueError("call_chunks(pipeline=True): the pipelined-CNN path (NC_PIPE_CNN=1) was removed")
     chrom = chunks[0]['chrom']
     ploidy = chunks[0]['ploidy']
     assert all(c['chrom'] == chrom and c['ploidy'] == ploidy for c in chunks)
@@ -244,16 +229,15 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     spans = [(c['start'], c['end']) for c in chunks]
     sites = eng.snp_scan(dpk, spans, mincov=params['mincov'],
                          min_allele_freq=params['min_allele_freq'], threshold=params['threshold'],
-                         haploid=(ploidy == 'haploid'), async_fetch=True, between=(lambda: flush_pending_cnn(device)) if pipeline else None,
-                         sites=listed, sites_only=only)
+                         haploid=(ploidy == 'haploid'), async_fetch=True, sites=listed, sites_only=only)
     res = dict(chrom=chrom, ploidy=ploidy, n=0, genotype_listed=count_listed(listed, spans, ())[0], genotype_emitted=0)
     if sites.n_sites == 0:
         eng.wait_copies()
         return PendingCall(lambda: res) if defer else res
     # the tensors stay on the device: int16 between featuriser and CNN (exact, half the HBM traffic) unless the exact-fp32
     # trunk, which reads the reference's float32 layout, has been selected
-    eng.set_tensor_format(int16=not getattr(eng, "exact_fp32", False))
-    eng.snp_featurize(dpk, sites, seq=params['seq'], maxcov=params['maxcov'], min_nbr_sites=params['min_nbr_sites'])
+    exact = eng.exact_fp32
+    eng.snp_featurize(dpk, sites, seq=params['seq'], maxcov=params['maxcov'], min_nbr_sites=params['min_nbr_sites'], int16=not exact)
     all_valid = bool(sites.valid.all().item()) if params['min_nbr_sites'] > 1 else True   # default 1 never filters (:244)
     per_site = bool(params.get('disable_coverage_normalization'))
     scale, chunk_depth = eng.snp_scale(sites, len(chunks), train_cov, per_site=per_site, async_fetch=True)
@@ -262,40 +246,15 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     h_ref, h_fwd, h_rev, h_valid = eng.to_host_async([sites.ref_code, sites.fwd_dp, sites.rev_dp, None if all_valid else sites.valid])
     # range guard of the split-precision trunk (nc_cnn_range_watch): sites whose scaled tensor exceeds what the model's weights prove
     # safe for the fp16 range are marked and, in finish(), computed once more by the exact fp32 trunk
-    guard = not getattr(eng, "exact_fp32", False)
-    i16 = not getattr(eng, "exact_fp32", False)
-    eng.set_tensor_format(int16=False)                             # the direct API keeps the reference's float32 default
-    cnn = {}                                                       # filled when the CNN is enqueued: now, or inside the next call's scan
-
-    def enqueue_cnn():
-        eng.use_torch_stream()
-        eng.set_tensor_format(int16=i16)
-        try:
-            flags_ = torch.zeros(sites.n_sites, dtype=torch.uint8, device=eng.device) if guard else None
-            cnn['d_probs'], cnn['d_gt'], cnn['h_probs'], cnn['h_gt'] = eng.snp_forward(kind, sites.x, sites.ref_code, scale, scale_mode=1 if per_site else 0,
-                                                                                   drain=True, range_flags=flags_)
-            cnn['flags'] = flags_
-            cnn['h_nflag'] = eng.to_host_async([flags_.sum(dtype=torch.int32).reshape(1)])[0] if guard else None
-        finally:
-            eng.set_tensor_format(int16=False)
-        cnn['drained'] = eng.copy_event()                          # completes with this call's last result copy
-    if pipeline:
-        _PENDING_CNN[device] = enqueue_cnn
-    else:
-        enqueue_cnn()
+    flags = None if exact else torch.zeros(sites.n_sites, dtype=torch.uint8, device=eng.device)
+    d_probs, d_gt, h_probs, h_gt = eng.snp_forward(kind, sites.x, sites.ref_code, scale, scale_mode=1 if per_site else 0, drain=True, range_flags=flags)
+    h_nflag = None if exact else eng.to_host_async([flags.sum(dtype=torch.int32).reshape(1)])[0]
+    drained = eng.copy_event()                                     # completes with this call's last result copy
     # host work that only needs the scan results runs under the CNN: freq = alt / n in float64 (:166)
     scan_copied.synchronize()
     freq = sites.alt.astype(np.float64) / sites.dp.astype(np.float64)
-    keep_alive = (sites, scale, cnn)                               # device buffers the pending copies read from
 
     def finish():
-        nonlocal keep_alive
-        if 'drained' not in cnn:                                   # nobody enqueued this group's CNN yet (no call followed): now
-            if _PENDING_CNN.get(device) is enqueue_cnn:
-                flush_pending_cnn(device)
-            else:
-                enqueue_cnn()
-        drained, h_nflag, flags, d_probs, d_gt, h_probs, h_gt = (cnn[k] for k in ('drained', 'h_nflag', 'flags', 'd_probs', 'd_gt', 'h_probs', 'h_gt'))
         drained.synchronize()
         n_rerun = int(h_nflag[0]) if h_nflag is not None else 0
         if n_rerun:
@@ -307,7 +266,6 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
             if h_gt is not None and d_gt is not None:
                 h_gt[ih] = d_gt[idx].cpu().numpy()
         res['range_reruns'] = n_rerun
-        keep_alive = None
         out = dict(pos=sites.pos, chunk=sites.chunk, ref=h_ref, probs=h_probs, gt=h_gt, dp=sites.dp, alt=sites.alt,
                    fwd_dp=h_fwd, rev_dp=h_rev, freq=freq)
         if not all_valid:
@@ -337,21 +295,166 @@ def _prepare_device(dbam, params, chrom, grp, ref=None):
     alignments the pileup keeps, the tile index -- from the per-record fields the device extracted when the file was loaded.  Alignments that
     share a read name are keyed by name (by_name=True: when name hashes repeat, one small launch on the context's own stream confirms the names)"""
     from .device_fasta import reference_for
-    from .generate_SNP_pileups import _exclude_rows
+    from .generate_SNP_pileups import _exclude_rows, span_of
     # (contig_span's rule, on the lengths the loader already holds: no second open of the BAM)
-    length = dbam.ref_lengths[dbam.ref_names.index(chrom)] if chrom in dbam.ref_names else 0
-    lo = max(1, min(c['start'] for c in grp) - _lib.FLANK)
-    hi = min(length, max(c['end'] for c in grp) + _lib.FLANK)
-    span = None if (hi - lo + 1) >= 0.9 * length else (lo, hi)
+    span = span_of(grp, dbam.ref_lengths[dbam.ref_names.index(chrom)] if chrom in dbam.ref_names else 0)
     # (the letters as bytes, or -- a bgzipped FASTA, or a plain one with params['device_fasta'] / NC_DEVICE_FASTA=1 -- the contig on its way to HBM)
     ref = ref.result() if ref is not None else reference_for(params['fasta_path'], chrom, dbam.device, params)
     return dbam.prepare(chrom, ref, supplementary=bool(params.get('supplementary')), exclude=_exclude_rows(params, chrom), span=span, by_name=True)
+
+
+def _plan_runs(params, keys, device):
+    """-> (run_end, run_dev), per group of `keys` [(contig, ploidy)]: where its run of groups ends, and the run's contigs (None: host route).
+    A file larger than HBM takes passes share by share: runs of contigs whose part of the file fits (device_bam.plan_shares;
+    NC_DEVICE_INGEST_SHARE_GB of compressed BAM, default 12); a contig that alone does not fit is decoded by the host threads.  Where the
+    device route cannot be taken at all, one run on the host route."""
+    from .device_bam import DeviceIngestUnavailable, plan_shares
+    run_end, run_dev = [len(keys)] * len(keys), [None] * len(keys)
+    try:
+        lim = os.environ.get('NC_DEVICE_INGEST_SHARE_GB')
+        order = list(dict.fromkeys(k[0] for k in keys))
+        share_of = {}
+        for n_sh, (cs, fits) in enumerate(plan_shares(params['sam_path'], order, None if lim is None else int(float(lim) * (1 << 30)), device=device)):
+            for c in cs:
+                share_of[c] = (n_sh, tuple(cs) if fits else None)
+        a0 = 0
+        for j in range(1, len(keys) + 1):
+            if j == len(keys) or share_of[keys[j][0]][0] != share_of[keys[a0][0]][0]:
+                for q in range(a0, j):
+                    run_end[q], run_dev[q] = j, share_of[keys[a0][0]][1]
+                a0 = j
+    except DeviceIngestUnavailable:
+        pass
+    return run_end, run_dev
+
+
+class _Ingest:
+    """Ingest pipeline of caller() (what bench.py's timed region does with its uploads): while the GPU runs group i, a host thread decodes the
+    BAM records of group i + 1's contig and puts them into the reference-difference wire form (native code, the GIL is released); that pack
+    then crosses PCIe on the upload stream through a ring of three device slots, under group i's kernels.
+    Device route (device_bam.py; NC_DEVICE_INGEST=0 or params['device_ingest'] = False keeps the host threads' decode): the FILE crosses
+    PCIe, is inflated and cut into records in HBM, and every group's pack is decoded there from the record stream; the worker threads only
+    decide which alignments are kept and build the tile index.  Needs the .bai (_plan_runs: which groups take it).
+    (alignments that share a read name -- a split read's records under dct['supplementary'], paired mates -- are keyed by NAME on both routes:
+    pack.name_groups, fed by nc_decoded_name_groups on the host route and by nc_bam_name_groups on the device route)"""
+
+    def __init__(self, params, keys, groups, device):
+        from concurrent.futures import ThreadPoolExecutor
+        self.params, self.keys, self.groups, self.device = params, keys, groups, device
+        self.run_end, self.run_dev = [len(keys)] * len(keys), [None] * len(keys)
+        if params.get('device_ingest', os.environ.get('NC_DEVICE_INGEST', '1') != '0') and params.get('fasta_path'):
+            from .device_bam import ensure_index
+            ensure_index(params['sam_path'], params, device)             # (params['build_index'] / NC_BUILD_INDEX=1: a BAM without index gets one)
+            self.run_end, self.run_dev = _plan_runs(params, keys, device)
+        # two groups ahead: the Python half of one pack's preparation (header parsing, the wire's index arrays, freeing the decoded
+        # arrays: ~35 of ~58 ms per 3 Mb contig) runs beside the native decode of the next one, which releases the GIL
+        self.ahead = max(1, int(os.environ.get('NC_INGEST_AHEAD', 2)))
+        self.pool = ThreadPoolExecutor(max_workers=self.ahead)
+        self.dbam = self.prepare = self.uploader = self.codes = None
+        self.preps, self.refs, self.nxt = [], {}, 0                  # the next groups' packs, being prepared; reference letters on their way
+
+    def _prepare_next(self, run_end):
+        if self.nxt < run_end:
+            k = self.keys[self.nxt]
+            self.preps.append(self.pool.submit(self.prepare, k[0], self.groups[k]))
+            self.nxt += 1
+
+    def enter_run(self, i):
+        """group i opens a run: the device route loads the run's share of the file (the previous share is dropped), the host route needs
+        nothing; then the first preparations of the run are started"""
+        from concurrent.futures import ThreadPoolExecutor
+        from .device_bam import DeviceIngestUnavailable, open_device_bam, release as release_device_bam
+        from .device_fasta import reference_for
+        params, device, refs = self.params, self.device, self.refs
+        # the previous share goes first: its DeviceBam is still referenced by the old `prepare` closure, and while it lives its stream buffer
+        # cannot be re-used -- a second one next to it is ~2 x 108 GB for a genome-sized file (more than the card holds)
+        self.dbam = self.prepare = None
+        if i > 0 and self.run_dev[i - 1] is not None:
+            get_engine(device).sync()
+            release_device_bam(params['sam_path'])
+        if self.run_dev[i] is not None:
+            # the first contigs' reference letters are read while the file is loaded (the loader mostly waits: for its reader threads, for the GPU);
+            # on the device route of the FASTA (device_fasta.py) that is the read of their byte ranges and their upload, on the upload stream
+            ref_pool = ThreadPoolExecutor(max_workers=2)
+            for k in self.keys[i:min(self.run_end[i], i + 3)]:
+                refs.setdefault(k[0], ref_pool.submit(reference_for, params['fasta_path'], k[0], device, params))
+            try:
+                self.dbam = open_device_bam(params['sam_path'], device, contigs=list(self.run_dev[i]))
+            except DeviceIngestUnavailable:
+                pass                                                  # (includes: not enough free device / page-locked memory -- the host route needs neither)
+            ref_pool.shutdown(wait=False)
+        if self.dbam is not None:
+            db = self.dbam
+            self.prepare = lambda chrom, grp: _prepare_device(db, params, chrom, grp, refs.pop(chrom, None))   # noqa: E731
+        else:
+            self.prepare = lambda chrom, grp: _prepare_wire(params, chrom, grp)   # noqa: E731
+            if self.uploader is None:
+                from .wire import WireUploader
+                self.uploader = WireUploader(get_engine(device))
+        self.nxt = i
+        while self.nxt < self.run_end[i] and len(self.preps) < self.ahead:
+            self._prepare_next(self.run_end[i])
+
+    def pack_for(self, i):
+        """-> (group i's DevicePack, callable that releases its upload slot once the group's kernels are enqueued)"""
+        if i == 0 or self.run_end[i - 1] == i:
+            self.enter_run(i)
+        wp = self.preps.pop(0).result()
+        self._prepare_next(self.run_end[i])
+        if self.dbam is not None:
+            # one codes buffer for every group: all steps run on one stream, so group i + 1's decode is ordered behind group i's last reader
+            if self.codes is None or self.codes.numel() < wp['codes_len']:
+                self.codes = torch.empty(wp['codes_len'] + wp['codes_len'] // 8, dtype=torch.uint8, device=get_engine(self.device).device)
+            return self.dbam.pack(wp, codes=self.codes), lambda: None
+        tk = self.uploader.submit(wp)
+        return self.uploader.expand(tk), lambda: self.uploader.release(tk)
+
+    def close(self):
+        self.pool.shutdown(wait=True)
+        if self.dbam is not None:
+            # the share of the file this worker had in HBM goes when the worker is done (the stages that follow -- phasing, the indel
+            # callers -- need the memory; the loader's work buffers up to 16 GB stay for the next load)
+            from .device_bam import release as release_device_bam
+            from .device_fasta import release as release_device_fasta
+            self.dbam = self.prepare = None
+            release_device_bam(self.params['sam_path'])
+            release_device_fasta(self.params['fasta_path'])              # (the last contig's FASTA image, where the reference took the device route)
+
+
+class _Records:
+    """Host pipeline of caller(): the genotype rules + record text of one (contig, ploidy) group are produced and written by a worker
+    thread (the formatter is native code: the GIL is released) while the GPU already works on the next group."""
+
+    def __init__(self, f, pool, counter_Q):
+        self.f, self.pool, self.counter_Q, self.scratch, self.pending = f, pool, counter_Q, None, None
+
+    def emit(self, chrom, ploidy, r, grp):
+        f = self.f
+        if r['n']:
+            need = (400 + len(chrom)) * r['n'] + 1024
+            if self.scratch is None or self.scratch.size < need:
+                self.scratch = np.empty(need + need // 4, np.uint8)
+            f.write(snp_vcf_text(chrom, r['pos'], r['ref'], r['probs'], r['dp'], r['freq'], r['fwd_dp'], r['rev_dp'],
+                                 haploid=(ploidy != 'diploid'), as_array=True, out=self.scratch))
+        f.flush()
+        os.fsync(f.fileno())
+        for _ in grp:
+            self.counter_Q.put(1)
+
+    def wait(self):
+        if self.pending is not None:
+            self.pending.result()                                    # keeps the records in group order; re-raises errors
+
+    def submit(self, chrom, ploidy, r, grp):
+        self.wait()
+        self.pending = self.pool.submit(self.emit, chrom, ploidy, r, grp)
 
 
 def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
     """Worker with the reference's signature (snpCaller.py:57): drains `chunks_Q`, writes
     <intermediate_snp_files_dir>/<prefix>.<worker>.snps.vcf.  Chunks are grouped per (contig, ploidy)
     and each group is one device batch."""
+    from concurrent.futures import ThreadPoolExecutor
     curr_vcf_path = os.path.join(params['intermediate_snp_files_dir'], '%s.%d.snps.vcf' % (params['prefix'], worker_id))
     snp_files.append(curr_vcf_path)
     chunks = []
@@ -367,144 +470,39 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
     groups = {}
     for c in chunks:
         groups.setdefault((c['chrom'], c['ploidy']), []).append(c)
-    # Host pipeline: the genotype rules + record text of one (contig, ploidy) group are produced and written by a worker
-    # thread (the formatter is native code: the GIL is released) while the GPU already works on the next group.
-    from concurrent.futures import ThreadPoolExecutor
-
-    scratch = [None]
-
-    def emit(f, chrom, ploidy, r, grp):
-        if r['n']:
-            need = (400 + len(chrom)) * r['n'] + 1024
-            if scratch[0] is None or scratch[0].size < need:
-                scratch[0] = np.empty(need + need // 4, np.uint8)
-            f.write(snp_vcf_text(chrom, r['pos'], r['ref'], r['probs'], r['dp'], r['freq'], r['fwd_dp'], r['rev_dp'],
-                                 haploid=(ploidy != 'diploid'), as_array=True, out=scratch[0]))
-        f.flush()
-        os.fsync(f.fileno())
-        for _ in grp:
-            counter_Q.put(1)
-
+    keys = list(groups)
+    last_use = {chrom: i for i, (chrom, _) in enumerate(keys)}         # last group of every contig
+    for k in keys:
+        groups[k].sort(key=lambda c: c['start'])
+    # BAM inputs take the ingest pipeline (_Ingest); NC_SERIAL_INGEST=1 keeps the round-2 behaviour (decode + upload inside call_chunks, the
+    # GPU idle meanwhile)
+    piped = isinstance(params['sam_path'], str) and os.path.exists(params['sam_path']) and not os.environ.get('NC_SERIAL_INGEST')
+    depth = max(1, int(os.environ.get('NC_CALLER_DEPTH', 2 if piped else 1)))
     with open(curr_vcf_path, 'wb') as f, ThreadPoolExecutor(max_workers=1) as pool:
-        pending, in_flight = None, []                                # groups whose kernels are queued and whose results have not been collected
+        records = _Records(f, pool, counter_Q)
+        ingest = _Ingest(params, keys, groups, device) if piped and keys else None
+        in_flight = []                                               # groups whose kernels are queued and whose results have not been collected
         unrecorded = {}                                              # contig -> listed positions (params['genotype_sites']) inside its chunks that got no record
 
         def collect():
-            nonlocal pending
             chrom, ploidy, call, grp, gi = in_flight.pop(0)
             r = call.result()
             if r.get('genotype_listed'):
                 unrecorded[chrom] = unrecorded.get(chrom, 0) + r['genotype_listed'] - r['genotype_emitted']
-            if pending is not None:
-                pending.result()                                    # keeps the records in group order; re-raises errors
-            pending = pool.submit(emit, f, chrom, ploidy, r, grp)
+            records.submit(chrom, ploidy, r, grp)
             if last_use[chrom] == gi:
                 # a genome is walked contig by contig: drop the decoded alignments and the HBM pack of the one just finished (on an
                 # ingest thread when there is one: unmapping ~100 MB takes 8 ms this thread would not be launching kernels)
-                if piped:
-                    prep_pool.submit(release_contig, chrom)
+                if ingest is not None:
+                    ingest.pool.submit(release_contig, chrom)
                 else:
                     release_contig(chrom)
-        keys = list(groups)
-        last_use = {chrom: i for i, (chrom, _) in enumerate(keys)}         # last group of every contig
-        for k in keys:
-            groups[k].sort(key=lambda c: c['start'])
-        # Ingest pipeline (what bench.py's timed region does with its uploads): while the GPU runs group i, a host thread decodes the
-        # BAM records of group i + 1's contig and puts them into the reference-difference wire form (native code, the GIL is released);
-        # that pack then crosses PCIe on the upload stream through a ring of three device slots, under group i's kernels.  BAM inputs
-        # only; NC_SERIAL_INGEST=1 keeps the round-2 behaviour (decode + upload inside call_chunks, the GPU idle meanwhile).
-        piped = isinstance(params['sam_path'], str) and os.path.exists(params['sam_path']) and not os.environ.get('NC_SERIAL_INGEST')
-        uploader = None
-        preps = []                                                   # the next groups' packs, being prepared
-        # Device route (device_bam.py; NC_DEVICE_INGEST=0 or params['device_ingest'] = False keeps the host threads' decode): the FILE crosses
-        # PCIe, is inflated and cut into records in HBM, and every group's pack is decoded there from the record stream; the worker threads only
-        # decide which alignments are kept and build the tile index.  Needs the .bai.  A file larger than HBM takes passes share by share: runs of
-        # contigs whose part of the file fits (device_bam.plan_shares; NC_DEVICE_INGEST_SHARE_GB of compressed BAM, default 12); a contig
-        # that alone does not fit is decoded by the host threads.
-        dev_codes, refs = [None], {}
-        run_end, run_dev = [len(keys)] * len(keys), [None] * len(keys)       # per group: where its run of groups ends; the run's contigs (None: host route)
-        # (alignments that share a read name -- a split read's records under dct['supplementary'], paired mates -- are keyed by NAME on both routes:
-        # pack.name_groups, fed by nc_decoded_name_groups on the host route and by nc_bam_name_groups here)
-        if piped and keys and params.get('device_ingest', os.environ.get('NC_DEVICE_INGEST', '1') != '0') and params.get('fasta_path'):
-            from .device_bam import DeviceIngestUnavailable, ensure_index, open_device_bam, plan_shares
-            from .device_fasta import reference_for
-            ensure_index(params['sam_path'], params, device)             # (params['build_index'] / NC_BUILD_INDEX=1: a BAM without index gets one)
-            try:
-                lim = os.environ.get('NC_DEVICE_INGEST_SHARE_GB')
-                order = list(dict.fromkeys(k[0] for k in keys))
-                share_of = {}
-                for n_sh, (cs, fits) in enumerate(plan_shares(params['sam_path'], order, None if lim is None else int(float(lim) * (1 << 30)), device=device)):
-                    for c in cs:
-                        share_of[c] = (n_sh, tuple(cs) if fits else None)
-                a0 = 0
-                for j in range(1, len(keys) + 1):
-                    if j == len(keys) or share_of[keys[j][0]][0] != share_of[keys[a0][0]][0]:
-                        for q in range(a0, j):
-                            run_end[q], run_dev[q] = j, share_of[keys[a0][0]][1]
-                        a0 = j
-            except DeviceIngestUnavailable:
-                pass
-        dbam, prepare, nxt = None, None, 0
-        depth = max(1, int(os.environ.get('NC_CALLER_DEPTH', 2 if piped else 1)))
-        if piped and keys:
-            ahead = int(os.environ.get('NC_INGEST_AHEAD', 2))
-            # two groups ahead: the Python half of one pack's preparation (header parsing, the wire's index arrays, freeing the decoded
-            # arrays: ~35 of ~58 ms per 3 Mb contig) runs beside the native decode of the next one, which releases the GIL
-            prep_pool = ThreadPoolExecutor(max_workers=max(1, ahead))
-
-        def enter_run(i):
-            """group i opens a run: the device route loads the run's share of the file (the previous share is dropped), the host route needs
-            nothing; then the first preparations of the run are started"""
-            nonlocal dbam, prepare, uploader, nxt
-            # the previous share goes first: its DeviceBam is still referenced by the old `prepare` closure, and while it lives its stream buffer
-            # cannot be re-used -- a second one next to it is ~2 x 108 GB for a genome-sized file (more than the card holds)
-            dbam = None
-            prepare = None
-            if i > 0 and run_dev[i - 1] is not None:
-                from .device_bam import release as _release_device_bam
-                get_engine(device).sync()
-                _release_device_bam(params['sam_path'])
-            if run_dev[i] is not None:
-                # the first contigs' reference letters are read while the file is loaded (the loader mostly waits: for its reader threads, for the GPU);
-                # on the device route of the FASTA (device_fasta.py) that is the read of their byte ranges and their upload, on the upload stream
-                ref_pool = ThreadPoolExecutor(max_workers=2)
-                for k in keys[i:min(run_end[i], i + 3)]:
-                    refs.setdefault(k[0], ref_pool.submit(reference_for, params['fasta_path'], k[0], device, params))
-                try:
-                    dbam = open_device_bam(params['sam_path'], device, contigs=list(run_dev[i]))
-                except DeviceIngestUnavailable:
-                    dbam = None                                           # (includes: not enough free device / page-locked memory -- the host route needs neither)
-                ref_pool.shutdown(wait=False)
-            if dbam is not None:
-                db = dbam
-                prepare = lambda chrom, grp: _prepare_device(db, params, chrom, grp, refs.pop(chrom, None))   # noqa: E731
-            else:
-                prepare = lambda chrom, grp: _prepare_wire(params, chrom, grp)   # noqa: E731
-                if uploader is None:
-                    from .wire import WireUploader
-                    uploader = WireUploader(get_engine(device))
-            nxt = i
-            while nxt < run_end[i] and len(preps) < max(1, ahead):
-                preps.append(prep_pool.submit(prepare, keys[nxt][0], groups[keys[nxt]]))
-                nxt += 1
         for i, (chrom, ploidy) in enumerate(keys):
             grp = groups[(chrom, ploidy)]
-            if piped:
-                if i == 0 or run_end[i - 1] == i:
-                    enter_run(i)
-                wp = preps.pop(0).result()
-                if nxt < run_end[i]:
-                    preps.append(prep_pool.submit(prepare, keys[nxt][0], groups[keys[nxt]]))
-                    nxt += 1
-                if dbam is not None:
-                    # one codes buffer for every group: all steps run on one stream, so group i + 1's decode is ordered behind group i's last reader
-                    if dev_codes[0] is None or dev_codes[0].numel() < wp['codes_len']:
-                        dev_codes[0] = torch.empty(wp['codes_len'] + wp['codes_len'] // 8, dtype=torch.uint8, device=get_engine(device).device)
-                    call = call_chunks(params, grp, device, dpk=dbam.pack(wp, codes=dev_codes[0]), defer=True)
-                else:
-                    tk = uploader.submit(wp)
-                    call = call_chunks(params, grp, device, dpk=uploader.expand(tk), defer=True)
-                    uploader.release(tk)
+            if ingest is not None:
+                dpk, done = ingest.pack_for(i)
+                call = call_chunks(params, grp, device, dpk=dpk, defer=True)
+                done()
             else:
                 call = call_chunks(params, grp, device, defer=True)     # enqueued behind the previous group's CNN
             in_flight.append((chrom, ploidy, call, grp, i))
@@ -515,21 +513,12 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
                 collect()
         while in_flight:
             collect()
-        if pending is not None:
-            pending.result()
+        records.wait()
         if not params.get('suppress_progress'):
             for chrom_, n_ in unrecorded.items():                    # (below mincov, a masked / non-AGTC / excluded reference base, no tensor)
                 print('%s: %s: %d listed sites got no record (not eligible for a pileup).' % (str(datetime.datetime.now()), chrom_, n_), flush=True)
-        if piped and keys:
-            prep_pool.shutdown(wait=True)
-        if dbam is not None:
-            # the share of the file this worker had in HBM goes when the worker is done (the stages that follow -- phasing, the indel
-            # callers -- need the memory; the loader's work buffers up to 16 GB stay for the next load)
-            from .device_bam import release as release_device_bam
-            dbam = None
-            release_device_bam(params['sam_path'])
-            from .device_fasta import release as release_device_fasta
-            release_device_fasta(params['fasta_path'])                   # (the last contig's FASTA image, where the reference took the device route)
+        if ingest is not None:
+            ingest.close()
 
 
 # ------------------------------------------------------------------ BGZF (so no bgzip binary is needed)

@@ -181,9 +181,8 @@ def test_hip_snp_cnn_equals_reference_call(eng, exact, i16):
         return torch.from_numpy(x).cuda()
     try:
         eng.set_cnn_precision(exact_fp32=exact)
-        eng.set_tensor_format(int16=i16)
         if i16:
-            assert eng.trunk_info() == (613, "k5_trunk_lin")
+            assert eng.trunk_info(int16=True) == (613, "k5_trunk_lin")
         for k in range(int(ZS["n"])):
             model = str(ZS["c%d_model" % k])
             case, n, mode, x, ref_code, depth, dp, out = _snp_case("c", k)
@@ -207,7 +206,6 @@ def test_hip_snp_cnn_equals_reference_call(eng, exact, i16):
             assert err < TOL_GPU, (case, err)
     finally:
         eng.set_cnn_precision(exact_fp32=False)
-        eng.set_tensor_format(int16=False)
     assert worst < 2e-5, "measured ~3e-6: far inside the 1e-4 contract"
 
 

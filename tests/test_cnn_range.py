@@ -46,11 +46,9 @@ def test_guarded_split_precision_equals_the_oracle_on_adversarial_tensors(model)
         x, rc = _tensors(rng, 96, hi)
         for fmt16 in (False, True):
             eng.set_cnn_precision(False)
-            eng.set_tensor_format(fmt16)
             xd = torch.from_numpy(x.astype(np.int16) if fmt16 else x).to(eng.device)
             rcd, sd = torch.from_numpy(rc).to(eng.device), torch.from_numpy(scale.astype(np.float64)).to(eng.device)
             pg, gg, n_rerun = eng.snp_forward_guarded(kind, xd, rcd, sd, mode)
-            eng.set_tensor_format(False)
             eng.set_cnn_precision(True)
             pe, ge = eng.snp_forward(kind, torch.from_numpy(x).to(eng.device), rcd, sd, mode)
             eng.set_cnn_precision(False)

@@ -63,8 +63,8 @@ def eng():
 
 
 @contextlib.contextmanager
-def _route(eng, exact, i16, lin_env):
-    """the engine on one SNP route; the defaults restored afterwards"""
+def _route(eng, exact, lin_env):
+    """the engine on one SNP route (which tensors it takes is the tensors' dtype: _snp_run); the defaults restored afterwards"""
     old = os.environ.get("NC_TRUNK_LIN")
     try:
         if lin_env is None:
@@ -72,7 +72,6 @@ def _route(eng, exact, i16, lin_env):
         else:
             os.environ["NC_TRUNK_LIN"] = lin_env
         eng.set_cnn_precision(exact)
-        eng.set_tensor_format(i16)
         yield
     finally:
         _restore(eng)
@@ -84,7 +83,6 @@ def _route(eng, exact, i16, lin_env):
 
 def _restore(eng):
     eng.set_cnn_precision(False)
-    eng.set_tensor_format(False)
     eng.L.nc_cnn_range_watch(eng.ctx, None)
 
 
@@ -127,8 +125,8 @@ def test_snp_routes_equal_the_oracle_on_unsaturated_weights(eng, tmp_path, kind,
                 r64 = P.oracle_forward(kind, blob, (x, rc, scale), "f64", scale_mode=mode)
                 r32 = P.oracle_forward(kind, blob, (x, rc, scale), "f32", scale_mode=mode)
                 for name, exact, i16, lin_env, kernel in SNP_ROUTES:
-                    with _route(eng, exact, i16, lin_env):
-                        assert eng.trunk_info()[1] == kernel, (name, eng.trunk_info())
+                    with _route(eng, exact, lin_env):
+                        assert eng.trunk_info(int16=i16)[1] == kernel, (name, eng.trunk_info(int16=i16))
                         worst = (0.0, 0.0)
                         for n, s0 in COUNTS:
                             sl = slice(s0, s0 + n)
@@ -235,11 +233,11 @@ def test_guarded_snp_forward_reruns_exactly_the_sites_beyond_the_bound(eng, tmp_
         for mode in (0, 1):
             r64 = P.oracle_forward(kind, blob, (x, rc, scale), "f64", scale_mode=mode)
             tol = P.tolerance(P.oracle_forward(kind, blob, (x, rc, scale), "f32", scale_mode=mode), r64)
-            with _route(eng, True, False, None):
+            with _route(eng, True, None):
                 exact = _snp_run(eng, kind, x, rc, scale, mode, False)
             for name, _, i16, lin_env, kernel in SNP_ROUTES[1:]:
-                with _route(eng, False, i16, lin_env):
-                    assert eng.trunk_info()[1] == kernel
+                with _route(eng, False, lin_env):
+                    assert eng.trunk_info(int16=i16)[1] == kernel
                     unguarded = _snp_run(eng, kind, x, rc, scale, mode, i16)
                     xd = torch.from_numpy(np.ascontiguousarray(x.astype(np.int16) if i16 else x)).to(dev)
                     flags = torch.zeros(n, dtype=torch.uint8, device=dev)

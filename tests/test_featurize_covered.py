@@ -15,11 +15,7 @@ PC_ROUND = 512                                                           # pairs
 @pytest.fixture(scope="module")
 def eng():
     from nanocaller_amd.engine import get_engine
-    e = get_engine(0)
-    was = getattr(e, "x_int16", False)
-    e.set_tensor_format(int16=True)
-    yield e
-    e.set_tensor_format(int16=was)
+    return get_engine(0)
 
 
 def _dct(seq="ont", maxcov=160, threshold=(0.4, 0.6), supplementary=False):
@@ -61,7 +57,7 @@ def _device(eng, world, dct, region):
     dpk = upload_wire(eng, build_wire_from_world(world, supplementary=dct["supplementary"]))
     sites = eng.snp_scan(dpk, [(region["start"], region["end"])], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"],
                          threshold=dct["threshold"])
-    eng.snp_featurize(dpk, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"])
+    eng.snp_featurize(dpk, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"], int16=True)
     torch.cuda.synchronize()
     assert sites.x.dtype == torch.int16
     return dpk, sites

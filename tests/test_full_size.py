@@ -79,11 +79,7 @@ def device_tensors(eng, pack, chunks, params, haploid=False):
     eng.use_torch_stream()
     sites = eng.snp_scan(pack, [(c["start"], c["end"]) for c in chunks], mincov=params["mincov"], min_allele_freq=params["min_allele_freq"],
                          threshold=params["threshold"], haploid=haploid)
-    eng.set_tensor_format(int16=True)
-    try:
-        eng.snp_featurize(pack, sites, seq=params["seq"], maxcov=params["maxcov"], min_nbr_sites=params["min_nbr_sites"])
-    finally:
-        eng.set_tensor_format(int16=False)
+    eng.snp_featurize(pack, sites, seq=params["seq"], maxcov=params["maxcov"], min_nbr_sites=params["min_nbr_sites"], int16=True)
     return sites, sites.x
 
 
@@ -102,8 +98,7 @@ def test_tensor_invariants_at_full_size(setup):
     eng.use_torch_stream()
     sub = chunks[:40]
     sites = eng.snp_scan(pack, [(c["start"], c["end"]) for c in sub], mincov=4, min_allele_freq=0.15, threshold=[0.4, 0.6])
-    eng.set_tensor_format(int16=False)
-    eng.snp_featurize(pack, sites, seq="ont", maxcov=160, min_nbr_sites=1)
+    eng.snp_featurize(pack, sites, seq="ont", maxcov=160, min_nbr_sites=1, int16=False)
     x = sites.x.cpu().numpy().reshape(-1, 5, 41, 5)
     n = x.shape[0]
     assert n > 150_000
@@ -155,21 +150,15 @@ def test_first_chunks_equal_the_oracle(setup):
 
 
 def test_the_cnn_enqueued_inside_the_next_scan_gives_the_same_results(setup):
-    """snpCaller.call_chunks(pipeline=True) (NC_PIPE_CNN=1; off by default: measured slower): a group's CNN is enqueued between nc_snp_scan_begin and
-    nc_snp_scan_end of the NEXT group, or by result() when no call follows -- device order scan(k + 1), CNN(k), tensors(k + 1) -- and every result equals
-    the unpipelined call's bit for bit"""
+    """(the name is history: the path that enqueued a group's CNN inside the next group's scan was removed.)  Four deferred calls held at once,
+    the first collected while the later ones are still pending, then the rest: every result equals the undeferred call's bit for bit"""
     from nanocaller_amd import snpCaller
     eng, pack, info, wire, chunks, params = setup
     groups = [chunks[:12], chunks[12:30], chunks[5:9], chunks[:12]]
-    plain = [snpCaller.call_chunks(params, g, dpk=pack, defer=True, pipeline=False).result() for g in groups]
-    pend = []
-    for k, g in enumerate(groups):
-        pend.append(snpCaller.call_chunks(params, g, dpk=pack, defer=True, pipeline=True))
-        assert 0 in snpCaller._PENDING_CNN                              # this group's CNN waits for the next scan
-        if k == 1:
-            assert pend[0].result()["n"] == plain[0]["n"]              # (collected while a later group's CNN is still pending)
+    plain = [snpCaller.call_chunks(params, g, dpk=pack, defer=False) for g in groups]
+    pend = [snpCaller.call_chunks(params, g, dpk=pack, defer=True) for g in groups]
+    assert pend[0].result()["n"] == plain[0]["n"]                      # (collected while the later groups are still pending)
     piped = [p.result() for p in pend]
-    assert 0 not in snpCaller._PENDING_CNN
     for a, b in zip(plain, piped):
         assert a["n"] == b["n"] > 1000
         for key in ("pos", "chunk", "ref", "dp", "alt", "fwd_dp", "rev_dp", "probs", "gt", "freq"):

@@ -249,21 +249,17 @@ def test_three_stage_trunk_at_pipeline_edges(eng, n, monkeypatch):
     scale = np.linspace(0.5, 2.0, n)
     rd, sd = torch.from_numpy(ref_code).cuda(), torch.from_numpy(scale).cuda()
     ep, _ = oracle.snp_forward(w.flat, x, ref_code, scale, precision="f64")
-    try:
-        monkeypatch.setenv("NC_TRUNK_LIN", "0")                          # (int16 tensors would otherwise take k5_trunk_lin: its own test below)
-        got = {}
-        for i16 in (False, True):
-            xd = torch.from_numpy(x).cuda()
-            if i16:
-                assert np.array_equal(x, np.rint(x)) and np.abs(x).max() < 32768
-                xd = xd.to(torch.int16)
-            eng.set_tensor_format(int16=i16)
-            assert eng.trunk_info()[1] == "k5_trunk_p3"
-            got[i16] = eng.snp_forward(_lib.MODEL_SNP, xd, rd, sd)[0].cpu().numpy()
-            assert np.abs(got[i16] - ep).max() < 2e-5, (n, i16)
-        assert np.array_equal(got[False], got[True]), n
-    finally:
-        eng.set_tensor_format(int16=False)
+    monkeypatch.setenv("NC_TRUNK_LIN", "0")                              # (int16 tensors would otherwise take k5_trunk_lin: its own test below)
+    got = {}
+    for i16 in (False, True):
+        xd = torch.from_numpy(x).cuda()
+        if i16:
+            assert np.array_equal(x, np.rint(x)) and np.abs(x).max() < 32768
+            xd = xd.to(torch.int16)
+        assert eng.trunk_info(int16=i16)[1] == "k5_trunk_p3"
+        got[i16] = eng.snp_forward(_lib.MODEL_SNP, xd, rd, sd)[0].cpu().numpy()
+        assert np.abs(got[i16] - ep).max() < 2e-5, (n, i16)
+    assert np.array_equal(got[False], got[True]), n
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 255, 257, 513, 1300])
@@ -298,25 +294,20 @@ def test_linear_conv1_trunk_equals_the_oracle_and_the_pixel_form(eng, n, monkeyp
     rd = torch.from_numpy(ref_code).cuda()
     xd16 = torch.from_numpy(x.astype(np.int16)).cuda()
     xd32 = torch.from_numpy(x.astype(np.float32)).cuda()
-    try:
-        for mode in (0, 1):
-            for with_scale in (True, False):
-                sc = scale if with_scale else np.ones(n)
-                sd = torch.from_numpy(sc).cuda()
-                ep, eg = oracle.snp_forward(w.flat, x.astype(np.float32), ref_code, sc, scale_mode=mode, precision="f64")
-                eng.set_tensor_format(int16=True)
-                assert eng.trunk_info()[1] == "k5_trunk_lin"
-                flags = torch.zeros(n, dtype=torch.uint8, device="cuda")
-                lin_p, lin_g = eng.snp_forward(_lib.MODEL_SNP, xd16, rd, sd if with_scale else None, scale_mode=mode, range_flags=flags)[:2]
-                lin_p, lin_g = lin_p.cpu().numpy(), lin_g.cpu().numpy()
-                assert int(flags.sum().item()) == 0
-                eng.set_tensor_format(int16=False)
-                assert eng.trunk_info()[1] == "k5_trunk_p3"
-                pix_p = eng.snp_forward(_lib.MODEL_SNP, xd32, rd, sd if with_scale else None, scale_mode=mode)[0].cpu().numpy()
-                assert np.abs(lin_p - ep).max() < 2e-5 and np.abs(lin_g - eg).max() < 2e-5, (n, mode, with_scale, np.abs(lin_p - ep).max())
-                assert np.abs(lin_p - pix_p).max() < 2e-5, (n, mode, with_scale)
-    finally:
-        eng.set_tensor_format(int16=False)
+    for mode in (0, 1):
+        for with_scale in (True, False):
+            sc = scale if with_scale else np.ones(n)
+            sd = torch.from_numpy(sc).cuda()
+            ep, eg = oracle.snp_forward(w.flat, x.astype(np.float32), ref_code, sc, scale_mode=mode, precision="f64")
+            assert eng.trunk_info(int16=True)[1] == "k5_trunk_lin"
+            flags = torch.zeros(n, dtype=torch.uint8, device="cuda")
+            lin_p, lin_g = eng.snp_forward(_lib.MODEL_SNP, xd16, rd, sd if with_scale else None, scale_mode=mode, range_flags=flags)[:2]
+            lin_p, lin_g = lin_p.cpu().numpy(), lin_g.cpu().numpy()
+            assert int(flags.sum().item()) == 0
+            assert eng.trunk_info(int16=False)[1] == "k5_trunk_p3"
+            pix_p = eng.snp_forward(_lib.MODEL_SNP, xd32, rd, sd if with_scale else None, scale_mode=mode)[0].cpu().numpy()
+            assert np.abs(lin_p - ep).max() < 2e-5 and np.abs(lin_g - eg).max() < 2e-5, (n, mode, with_scale, np.abs(lin_p - ep).max())
+            assert np.abs(lin_p - pix_p).max() < 2e-5, (n, mode, with_scale)
 
 
 def test_linear_conv1_trunk_flags_what_it_cannot_take(eng):
@@ -343,13 +334,9 @@ def test_linear_conv1_trunk_flags_what_it_cannot_take(eng):
     x[100, 3, 3, 3] = int(x_lim / 1.5) - 1                 # just inside
     x[101, 4, 40, 0] = 2048
     scale[101] = 1e-3
-    try:
-        eng.set_tensor_format(int16=True)
-        flags = torch.zeros(n, dtype=torch.uint8, device="cuda")
-        eng.snp_forward(_lib.MODEL_SNP, torch.from_numpy(x).cuda(), torch.zeros(n, dtype=torch.int32, device="cuda"), torch.from_numpy(scale).cuda(), range_flags=flags)
-        assert sorted(torch.nonzero(flags).flatten().tolist()) == [7, 300, 301, 599]
-    finally:
-        eng.set_tensor_format(int16=False)
+    flags = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    eng.snp_forward(_lib.MODEL_SNP, torch.from_numpy(x).cuda(), torch.zeros(n, dtype=torch.int32, device="cuda"), torch.from_numpy(scale).cuda(), range_flags=flags)
+    assert sorted(torch.nonzero(flags).flatten().tolist()) == [7, 300, 301, 599]
 
 
 def test_snp_hap_cnn_matches_oracle(eng, precision):
@@ -466,7 +453,7 @@ def test_end_to_end_vcf_matches_oracle_pipeline(eng, tmp_path):
 
 
 def test_int16_tensors_equal_float32_tensors(eng, monkeypatch):
-    """nc_set_tensor_format(ctx, 1): the featuriser's int16 tensors are the float32 tensors value for value; the pixel-form split-precision trunk
+    """snp_featurize(int16=True) (nc_set_tensor_format(ctx, 1)): the featuriser's int16 tensors are the float32 tensors value for value; the pixel-form split-precision trunk
     (k5_trunk_p3, NC_TRUNK_LIN=0) returns bit-identical probabilities from either, k5_trunk_lin (the int16 default: conv1 by linearity, other
     roundings) the same within 2e-5; the exact-fp32 trunk refuses int16"""
     import torch
@@ -480,9 +467,8 @@ def test_int16_tensors_equal_float32_tensors(eng, monkeypatch):
     out = {}
     monkeypatch.setenv("NC_TRUNK_LIN", "0")
     for i16 in (False, True):
-        eng.set_tensor_format(int16=i16)
         sites = eng.snp_scan(dp, [(20_000, 60_000), (60_001, 100_003)], mincov=4, min_allele_freq=0.15, threshold=[0.4, 0.6])
-        eng.snp_featurize(dp, sites, seq="ont", maxcov=160)
+        eng.snp_featurize(dp, sites, seq="ont", maxcov=160, int16=i16)
         scale, _ = eng.snp_scale(sites, 2, cov)
         probs, gt = eng.snp_forward(_lib.MODEL_SNP, sites.x, sites.ref_code, scale)
         out[i16] = (sites.x.clone(), probs.clone(), gt.clone(), sites.n_sites)
@@ -490,15 +476,13 @@ def test_int16_tensors_equal_float32_tensors(eng, monkeypatch):
     assert torch.equal(out[True][0].to(torch.float32), out[False][0])
     assert torch.equal(out[True][1], out[False][1]) and torch.equal(out[True][2], out[False][2])
     monkeypatch.delenv("NC_TRUNK_LIN")
-    eng.set_tensor_format(int16=True)
-    assert eng.trunk_info()[1] == "k5_trunk_lin"
+    assert eng.trunk_info(int16=True)[1] == "k5_trunk_lin"
     lp, lg = eng.snp_forward(_lib.MODEL_SNP, out[True][0], sites.ref_code, scale)
     assert float((lp - out[False][1]).abs().max()) < 2e-5 and float((lg - out[False][2]).abs().max()) < 2e-5
     eng.set_cnn_precision(exact_fp32=True)
     with pytest.raises(Exception):
         eng.snp_forward(_lib.MODEL_SNP, out[True][0], sites.ref_code, scale)
     eng.set_cnn_precision(exact_fp32=False)
-    eng.set_tensor_format(int16=False)
 
 
 def test_deferred_calls_equal_drained_calls(eng):

@@ -113,29 +113,24 @@ def test_shared_names_through_the_wire_and_the_int16_tensors_equal_the_reference
     from nanocaller_amd.wire import WireUploader, build_wire_from_world, upload_wire
     world, dct, region, exclude, gold = load_snp_case("ont_mates")
     eng = get_engine(0)
-    was = getattr(eng, "x_int16", False)
-    eng.set_tensor_format(int16=True)
-    try:
-        wp = build_wire_from_world(world, supplementary=True)
-        up = WireUploader(eng)
-        t = up.submit(wp)
-        for dpk in (upload_wire(eng, wp), up.expand(t)):
-            assert dpk.mates is not None
-            sites = eng.snp_scan(dpk, [(region["start"], region["end"])], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"], threshold=dct["threshold"])
-            eng.snp_featurize(dpk, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"])
-            torch.cuda.synchronize()
-            assert np.array_equal(sites.pos, gold["pos"]) and np.array_equal(sites.dp, gold["dp"])
-            assert sites.x.dtype == torch.int16 and np.array_equal(sites.x.cpu().numpy(), gold["mat"].astype(np.int16))
-            assert np.array_equal(sites.fwd_dp.cpu().numpy(), gold["fwd_dp"]) and np.array_equal(sites.rev_dp.cpu().numpy(), gold["rev_dp"])
-            assert float(np.mean(sites.depth.cpu().numpy().astype(np.float64))) == gold["depth"]
-        up.release(t)
-        # without the table the same pack gives the per-alignment answer: not the reference's
-        dpk.mates = None
+    wp = build_wire_from_world(world, supplementary=True)
+    up = WireUploader(eng)
+    t = up.submit(wp)
+    for dpk in (upload_wire(eng, wp), up.expand(t)):
+        assert dpk.mates is not None
         sites = eng.snp_scan(dpk, [(region["start"], region["end"])], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"], threshold=dct["threshold"])
-        eng.snp_featurize(dpk, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"])
-        assert not np.array_equal(sites.x.cpu().numpy(), gold["mat"].astype(np.int16))
-    finally:
-        eng.set_tensor_format(int16=was)
+        eng.snp_featurize(dpk, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"], int16=True)
+        torch.cuda.synchronize()
+        assert np.array_equal(sites.pos, gold["pos"]) and np.array_equal(sites.dp, gold["dp"])
+        assert sites.x.dtype == torch.int16 and np.array_equal(sites.x.cpu().numpy(), gold["mat"].astype(np.int16))
+        assert np.array_equal(sites.fwd_dp.cpu().numpy(), gold["fwd_dp"]) and np.array_equal(sites.rev_dp.cpu().numpy(), gold["rev_dp"])
+        assert float(np.mean(sites.depth.cpu().numpy().astype(np.float64))) == gold["depth"]
+    up.release(t)
+    # without the table the same pack gives the per-alignment answer: not the reference's
+    dpk.mates = None
+    sites = eng.snp_scan(dpk, [(region["start"], region["end"])], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"], threshold=dct["threshold"])
+    eng.snp_featurize(dpk, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"], int16=True)
+    assert not np.array_equal(sites.x.cpu().numpy(), gold["mat"].astype(np.int16))
 
 
 @pytest_gpu
