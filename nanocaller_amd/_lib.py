@@ -131,7 +131,11 @@ _lib = None
 
 
 class NanoCallerHipError(RuntimeError):
-    pass
+    """status: the library's return code (NC_ERR_*) where one is behind the error, else None"""
+
+    def __init__(self, message, status=None):
+        super().__init__(message)
+        self.status = status
 
 
 def lib():

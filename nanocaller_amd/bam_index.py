@@ -34,9 +34,8 @@ _STATUS_TEXT = [(2, "a record with a block_size below 32"), (4, "a record whose 
 
 
 def status_error(path, st):
-    err = _lib.NanoCallerHipError("%s cannot be indexed: %s (status %d)" % (path, "; ".join(t for b, t in _STATUS_TEXT if st & b) or "corrupt records", st))
-    err.status = int(st)
-    return err
+    return _lib.NanoCallerHipError("%s cannot be indexed: %s (status %d)" % (path, "; ".join(t for b, t in _STATUS_TEXT if st & b) or "corrupt records", st),
+                                   status=int(st))
 
 
 def _vp(t, byte_off=0):

@@ -412,9 +412,7 @@ class DeviceBam:
             if n_dup:
                 what.append("%d pairs of kept alignments carry the same read name%s; the reference's per-column dicts hold one entry per name "
                             "(generate_SNP_pileups.py:175,185,208): the host route (NC_DEVICE_INGEST=0) keys them by name" % (n_dup, "" if supplementary else " and overlap on the reference"))
-            err = _lib.NanoCallerHipError("%s, contig %s: %s -- NC_ERR_UNSUPPORTED" % (self.path, chrom, "; ".join(what)))
-            err.status = _lib.NC_ERR_UNSUPPORTED
-            raise err
+            raise _lib.NanoCallerHipError("%s, contig %s: %s -- NC_ERR_UNSUPPORTED" % (self.path, chrom, "; ".join(what)), status=_lib.NC_ERR_UNSUPPORTED)
         filt = FLAG_FILTER_SUPPL if supplementary else FLAG_FILTER_DEFAULT
         keep = pileup_depth_cap(start, end, np.ascontiguousarray((flag & filt) == 0, np.uint8))
         if haplotags:

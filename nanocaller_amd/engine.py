@@ -128,7 +128,7 @@ class Engine:
     def _check(self, rc, what):
         if rc != _lib.NC_OK:
             msg = self.L.nc_last_error(self.ctx)
-            raise _lib.NanoCallerHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+            raise _lib.NanoCallerHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""), status=rc)
 
     def use_torch_stream(self):
         """The library's kernels go to torch's current stream of this thread.  Where that is the legacy default stream, the thread is first moved to

@@ -82,10 +82,10 @@ def release_contig(chrom=None):
     _BAM_WORLDS.drop(lambda k: chrom is None or k[2] == chrom)
     _PACKS.drop(lambda k: chrom is None or k[2] == chrom)
     import sys
-    gip = sys.modules.get(__package__ + ".generate_indel_pileups")       # (the indel route's device-ingested contig: same lifetime)
-    if gip is not None:
-        for k in [k for k in gip._DEV_INGEST if chrom is None or k[1] == chrom]:
-            del gip._DEV_INGEST[k]
+    ind = sys.modules.get(__package__ + ".indel_device")                 # (the indel route's device-ingested contig: same lifetime)
+    if ind is not None:
+        for k in [k for k in ind._DEV_INGEST if chrom is None or k[1] == chrom]:
+            del ind._DEV_INGEST[k]
 
 
 DECODES = []                  # (bam, contig, span or None) of every BAM decode of this process (tests: no contig is decoded twice)
@@ -164,9 +164,7 @@ def _check_supported(world, sam_path, chrom, supplementary=False, by_name=False)
         if n_dup:
             what.append("%d pairs of kept alignments carry the same read name and overlap on the reference; the reference's per-column "
                         "dicts hold one entry per name (generate_SNP_pileups.py:175,185,208)" % n_dup)
-        err = _lib.NanoCallerHipError("%s, contig %s: %s -- NC_ERR_UNSUPPORTED" % (sam_path, chrom, "; ".join(what)))
-        err.status = _lib.NC_ERR_UNSUPPORTED
-        raise err
+        raise _lib.NanoCallerHipError("%s, contig %s: %s -- NC_ERR_UNSUPPORTED" % (sam_path, chrom, "; ".join(what)), status=_lib.NC_ERR_UNSUPPORTED)
 
 
 def contig_span(sam_path, chrom, chunks):

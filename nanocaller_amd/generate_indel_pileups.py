@@ -12,6 +12,8 @@
 * dct['impute_indel_phase'] (:278-304): the column-level predicate (:278-284) is part of the GPU scan (col_type 2); the
   read grouping of the few flagged columns (:285-304) runs here on their pileup strings (`impute_groups`), and pass 2
   takes its two read sets from `extra_variants` (:310-312).
+* `get_indel_testing_candidates_batch`: all chunks of a contig at once, each part of the list on the route `plan_routes` gives it: the
+  device-resident pipeline (indel_device.py) or the host-assembled featuriser (`_indel_batch_host`: pass 1 batched, `_pass2_native`).
 """
 from __future__ import annotations
 
@@ -19,16 +21,17 @@ import bisect
 import contextlib
 import ctypes as C
 import gc
-import os
 import subprocess
 
 import numpy as np
-import torch
 
 from . import _lib
 
 from .engine import get_engine
-from .generate_SNP_pileups import _exclude_rows, _resolve, device_pack
+from .generate_SNP_pileups import _resolve, device_pack
+# the device half; callers outside the package use these names, and watch indel_sites_device, under this module's name
+from .indel_device import (_DEV_INGEST, MATE_RING_CAP, TAIL_CAP, device_part, exclusion_mask, imputed_chunk_mask, indel_mate_table,  # noqa: F401
+                           indel_pack_for, indel_sites_device, indel_sites_fetch, keep_flag, sites_to_tuples, sites_to_vcf_text, window_after_of)
 from .phase import retag_decoded
 
 
@@ -96,7 +99,7 @@ def column_strings(world, sam_path, chrom, cols, supplementary=False):
     out = {}
     if not cols:
         return out
-    flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if supplementary else 0x800)
+    flag = keep_flag(dict(supplementary=supplementary))
     ev_off, ev_pos, ev_len = world.meta["events"]
     if "ev_ins" in world.meta:
         ins_off, ins_bases = world.meta["ev_ins"]
@@ -155,21 +158,14 @@ def scan_indel_candidates(dct, chunk, device=0, haploid=False, extra_variants=No
             raise ValueError("scan_indel_candidates: a chunk list must be of one BAM and one contig")
     first = chunk if isinstance(chunk, dict) else chunks[0]
     world = _resolve(first["sam_path"], first["chrom"], dct.get("fasta_path"))
-    excl_rows = _exclude_rows(dct, first["chrom"])
     supp = bool(dct.get("supplementary"))
     eng = get_engine(device)
     eng.use_torch_stream()
     # the SNP path's pack of this contig (same key when no exclusion list is folded into its reference codes)
     dp = device_pack(first["sam_path"], dct.get("fasta_path"), first["chrom"], supp, None, device)[0]
-    excl = None
-    if excl_rows:
-        m = np.zeros(dp.n_tiles * dp.tile_size, np.uint8)
-        for (a, b) in excl_rows:                                    # IntervalTree.overlaps(pos): a <= pos < b
-            m[max(0, a - dp.tile_pos0):max(0, b - dp.tile_pos0)] = 1
-        excl = torch.from_numpy(m).to(eng.device)
     impute = bool(dct.get("impute_indel_phase")) and not haploid
     kw = dict(mincov=dct["mincov"], win_size=dct["win_size"], small_win_size=dct["small_win_size"], ins_t=dct["ins_t"],
-              del_t=dct["del_t"], excl=excl, haploid=haploid, impute=impute)
+              del_t=dct["del_t"], excl=exclusion_mask(dct, first["chrom"], dp), haploid=haploid, impute=impute)
     one = chunks is None
     todo = [chunk] if one else chunks
     cols = [eng.indel_scan(dp, chunk["start"], chunk["end"], **kw)] if one else eng.indel_scan_batch(dp, [(c["start"], c["end"]) for c in chunks], **kw)
@@ -206,7 +202,7 @@ def nw_cigar(s1, s2, open_=9, extend=1, match=20, mismatch=-10):
     n = C.c_int32()
     rc = L.nc_nw_cigar(a, len(a), b, len(b), open_, extend, match, mismatch, _lib.npp(ops), _lib.npp(cnt), cap, C.byref(n))
     if rc != _lib.NC_OK:
-        raise _lib.NanoCallerHipError("nc_nw_cigar failed (%d)" % rc)
+        raise _lib.NanoCallerHipError("nc_nw_cigar failed (%d)" % rc, status=rc)
     return [(int(ops[k]), int(cnt[k])) for k in range(n.value)]
 
 
@@ -217,7 +213,7 @@ def allele_prediction(alt, ref_seq, max_range):
     rl, al = C.c_int32(), C.c_int32()
     rc = L.nc_allele_prediction(a, len(a), b, len(b), int(max_range), C.byref(rl), C.byref(al))
     if rc != _lib.NC_OK:
-        raise _lib.NanoCallerHipError("nc_allele_prediction failed (%d)" % rc)
+        raise _lib.NanoCallerHipError("nc_allele_prediction failed (%d)" % rc, status=rc)
     if rl.value < 0:
         return (None, None)
     return ref_seq[:rl.value], alt[:al.value]
@@ -240,14 +236,14 @@ def allele_prediction_batch(alts, ref_seqs, max_ranges, eng=None):
     rc = _lib.NC_ERR_CAPACITY
     if eng is not None:
         rc = L.nc_allele_prediction_device(eng.ctx, n, a_b, _lib.npp(aoff), r_b, _lib.npp(roff), _lib.npp(mr), _lib.npp(rl), _lib.npp(al))
-        if rc not in (_lib.NC_OK, _lib.NC_ERR_CAPACITY, _lib.NC_ERR_NOMEM):
-            raise _lib.NanoCallerHipError("nc_allele_prediction_device failed (%d): %s" % (rc, eng.last_error() if hasattr(eng, "last_error") else ""))
+        if rc not in (_lib.NC_ERR_CAPACITY, _lib.NC_ERR_NOMEM):
+            eng._check(rc, "nc_allele_prediction_device")
     # (a batch whose traceback does not fit the device call -- one very long consensus sizes every row of it -- goes to the host aligner
     # like one beyond the kernel's shapes: same results)
     if rc in (_lib.NC_ERR_CAPACITY, _lib.NC_ERR_NOMEM):
         rc = L.nc_allele_prediction_batch(n, a_b, _lib.npp(aoff), r_b, _lib.npp(roff), _lib.npp(mr), _lib.npp(rl), _lib.npp(al))
     if rc != _lib.NC_OK:
-        raise _lib.NanoCallerHipError("nc_allele_prediction_batch failed (%d)" % rc)
+        raise _lib.NanoCallerHipError("nc_allele_prediction_batch failed (%d)" % rc, status=rc)
     # plain ints: indexing numpy scalars and slicing with them costs ~2 us per pair, a third of the whole batch at 10^4 anchors
     return [(None, None) if r < 0 else (rs[:r], a_[:a]) for rs, a_, r, a in zip(ref_seqs, alts, rl.tolist(), al.tolist())]
 
@@ -297,7 +293,7 @@ def star_aligner(names, seqs, ref, open_=None, extend=None, match=None, mismatch
             cap = ncol.value
             continue
         if rc != _lib.NC_OK:
-            raise _lib.NanoCallerHipError("nc_star_msa failed (%d)" % rc)
+            raise _lib.NanoCallerHipError("nc_star_msa failed (%d)" % rc, status=rc)
         break
     sym = np.frombuffer(b"AGTC-N", np.uint8)
     nc = ncol.value
@@ -337,16 +333,14 @@ def get_indel_testing_candidates(dct, chunk, aligner=None, device=0):
     -> (pos, x0, x1, x2, alleles, phase); pass 1 on the GPU (nc_indel_scan), pass 2 through the native reader."""
     from .bam import BamFile, read_fasta
     chrom, start, end = chunk["chrom"], chunk["start"], chunk["end"]
-    window_before, window_after = 0, 160
-    if dct["seq"] == "pacbio":
-        window_after = 260
+    window_before, window_after = 0, window_after_of(dct)
     extra_variants = {}
     variants = scan_indel_candidates(dct, chunk, device, extra_variants=extra_variants)
     empty = ([], [], [], [], [], [])
     if not variants:
         return empty
     lo, hi = max(1, start - 200), end + 400                                        # ref_dict range (:174)
-    flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if dct.get("supplementary") else 0x800)
+    flag = keep_flag(dct)
     # the pileup of pass 2 covers [start-10-win, end] (:306)
     anchors = sorted(v for v in variants if max(0, start - 10 - dct["win_size"]) < v <= end)
     max_range = {0: max(10, dct["win_size"]), 1: 10}
@@ -395,9 +389,6 @@ def get_indel_testing_candidates(dct, chunk, aligner=None, device=0):
     return (out_pos, np.array(x0), np.array(x1), np.array(x2), alleles, phase)
 
 
-_DROP_AGTC = str.maketrans("", "", "AGTC")
-
-
 def _sample_set(seq_list, mincov, maxcov):
     """the part of msa() before the aligner (:13-23): down-sample to maxcov (the first maxcov reads in pileup order: a
     deterministic stand-in for the reference's unseeded random.sample), sort the names;
@@ -437,18 +428,26 @@ def decoded_contig(sam_path, chrom, fasta_path):
     return _CONTIGS[key]
 
 
-def _pass2_native(dct, variants, extra_variants, anchors, ctg, lo, hi, window_after, max_range, device, haploid, by_index=False, device_x=False):
+def contig_keep(ctg, flag):
+    """which alignments of a decoded contig the pileups keep under the FLAG filter `flag` (uint8 per alignment, the pileup's depth cap applied);
+    computed once per filter and kept with the contig"""
+    if flag not in ctg["keep"]:
+        from .pack import pileup_depth_cap
+        dec = ctg["dec"]
+        ctg["keep"][flag] = pileup_depth_cap(dec["read_start"], dec["read_end"], np.ascontiguousarray((dec["read_flag"] & flag) == 0, np.uint8))
+    return ctg["keep"][flag]
+
+
+def _pass2_native(dct, variants, extra_variants, anchors, ctg, lo, hi, window_after, max_range, device, haploid, by_index=False, device_x=False,
+                  dedup=True):
     """Pass 2 (:306-361) for all anchors of a chunk: read sets assembled natively (nc_indel_pass2_sets) from the decoded contig,
     every set aligned in ONE device call (star alignment + rows -> tensor), allele strings by nc_allele_prediction_batch.
     -> diploid (pos, x0, x1, x2, alleles, phase) / haploid (pos, x, alleles).  by_index: `variants` / `extra_variants` are keyed
-    by the anchor's INDEX in `anchors` (merged chunks) and the kept anchor indices are appended to the result."""
+    by the anchor's INDEX in `anchors` (merged chunks) and the kept anchor indices are appended to the result.  dedup=False: a read that sits
+    in several sets of an anchor is aligned once per set, not once (nc_indel_pass2_sets' duplicate map is left unused: same results)."""
     L = _lib.lib()
     dec = ctg["dec"]
-    flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if dct.get("supplementary") else 0x800)
-    if flag not in ctg["keep"]:
-        from .pack import pileup_depth_cap
-        ctg["keep"][flag] = pileup_depth_cap(dec["read_start"], dec["read_end"], np.ascontiguousarray((dec["read_flag"] & flag) == 0, np.uint8))
-    keep = ctg["keep"][flag]
+    keep = contig_keep(ctg, keep_flag(dct))
     anc = np.ascontiguousarray(anchors, np.int32)
     imp_idx = imp_off = imp_reads = None
     if extra_variants:
@@ -474,9 +473,7 @@ def _pass2_native(dct, variants, extra_variants, anchors, ctg, lo, hi, window_af
                                int(window_after), int(dct["mincov"]), int(dct["maxcov"]), 1 if haploid else 0, _lib.npp(imp_idx),
                                _lib.npp(imp_off), _lib.npp(imp_reads), C.byref(h))
     if rc != _lib.NC_OK:
-        err = _lib.NanoCallerHipError("nc_indel_pass2_sets failed (%d)" % rc)
-        err.status = rc
-        raise err
+        raise _lib.NanoCallerHipError("nc_indel_pass2_sets failed (%d)" % rc, status=rc)
     try:
         v = _lib.Pass2ArraysC()
         L.nc_pass2_view(h, C.byref(v))
@@ -488,7 +485,7 @@ def _pass2_native(dct, variants, extra_variants, anchors, ctg, lo, hi, window_af
         eng.use_torch_stream()
         x, cns_str, _ = eng.star_msa_tensor_flat(ns, C.c_void_p(v.reads), C.c_void_p(v.read_off), C.c_void_p(v.set_read0), C.c_void_p(v.refs),
                                                  C.c_void_p(v.ref_off), min(v.max_cols, 4 * window_after + 64), cns_as_str=True,
-                                                 al_dup=None if haploid or os.environ.get("NC_MSA_NO_DEDUP") else C.c_void_p(v.al_dup))
+                                                 al_dup=C.c_void_p(v.al_dup) if dedup and not haploid else None)
         kept = np.ctypeslib.as_array(C.cast(v.anchor_idx, C.POINTER(C.c_int32)), (nk,)).copy()
         first0 = np.ctypeslib.as_array(C.cast(v.first0, C.POINTER(C.c_int32)), (nk,)).copy()
         ref_off = np.ctypeslib.as_array(C.cast(v.ref_off, C.POINTER(C.c_int32)), (ns + 1,))
@@ -511,33 +508,61 @@ def _pass2_native(dct, variants, extra_variants, anchors, ctg, lo, hi, window_af
     return (pos, xh[:, 0], xh[:, 1], xh[:, 2], alleles, phase) + tail
 
 
-def get_indel_testing_candidates_batch(dct, chunks, device=0, haploid=False, device_x=False, device_route=True):
+MAX_BATCH_CHUNKS = 64          # chunks per native pass-2 / alignment call (100 kb chunks at 30x: ~15 k anchors, ~150 MB of read windows)
+ROUTES = (None, "host", "split")
+
+
+def plan_routes(dct, chunks, haploid, route=None, mask=None, device=0):
+    """Which route the chunks (a non-empty list, one BAM and contig) take -> [(kind, chunk indices, dct of that part)], kind "device" (the
+    device-resident pipeline, indel_device.py) or "host" (the host-assembled featuriser, _indel_batch_host).  The one place that decides; reads no
+    environment.  A "device" part that ends in NC_ERR_CAPACITY is redone by its caller on the host-assembled route (device_part).
+    route=None: one device part -- unless the input is not a BAM path, or the chunks, sorted by (start, end), do not have ascending ends (nested
+    lists: nc_indel_sites_plan takes chunks whose starts AND ends ascend), which go to the host.  route="host": everything on the host.
+    route="split", for dct['impute_indel_phase'] (diploid) only: the chunks with a column that meets the rule's column predicate (`mask`, one bool per
+    chunk; default imputed_chunk_mask, a scan on `device`) go to the host, whose read grouping works on the pileup strings; the others are the
+    flag-off problem and go to the device with impute_indel_phase=False; all on the host when none is left for the device."""
+    if route not in ROUTES:
+        raise ValueError("route=%r: one of %r" % (route, ROUTES))
+    every = list(range(len(chunks)))
+    order = sorted(every, key=lambda k: (chunks[k]["start"], chunks[k]["end"]))
+    ends = [chunks[k]["end"] for k in order]
+    if route == "host" or not isinstance(chunks[0]["sam_path"], str) or any(b < a for a, b in zip(ends, ends[1:])):
+        return [("host", every, dct)]
+    if route == "split" and dct.get("impute_indel_phase") and not haploid:
+        if mask is None:
+            mask = [None] * len(chunks)
+            for k, m in zip(order, imputed_chunk_mask(dct, [chunks[k] for k in order], device)):
+                mask[k] = m
+        dev, host = [k for k in every if not mask[k]], [k for k in every if mask[k]]
+        if not dev:
+            return [("host", every, dct)]
+        return [("device", dev, dict(dct, impute_indel_phase=False))] + ([("host", host, dct)] if host else [])
+    return [("device", every, dct)]
+
+
+def get_indel_testing_candidates_batch(dct, chunks, device=0, haploid=False, device_x=False, route=None, dedup=True):
     """get_indel_testing_candidates[_haploid] for ALL chunks of one contig and BAM in one go -> list of the per-chunk tuples
-    (each exactly what the per-chunk call returns): pass 1 of every chunk in the same launches (nc_indel_scan_batch), the
-    anchors of all chunks through ONE native pass-2 call, ONE device star alignment and ONE allele batch.  What
-    indelCaller.indel_run uses; the device / native route only (no external aligner).  device_x: the tensors of the tuples are
-    torch float32 tensors on the device (no download / float64 conversion / upload round trip on the way to the CNN)."""
+    (each exactly what the per-chunk call returns), every part of the list on the route plan_routes(route=) gives it: the device pipeline, or
+    pass 1 of every chunk in the same launches (nc_indel_scan_batch), the anchors of all chunks through ONE native pass-2 call, ONE device
+    star alignment and ONE allele batch.  What indelCaller.indel_run uses; no external aligner.  device_x: the tensors of the tuples are
+    torch float32 tensors on the device (no download / float64 conversion / upload round trip on the way to the CNN).  dedup: _pass2_native's."""
     chunks = list(chunks)
     if not chunks:
         return []
+    kw = dict(device=device, haploid=haploid, device_x=device_x, route=route, dedup=dedup)
     # A whole chromosome is hundreds of chunks and ~10^5 anchors: the read windows of all of them do not fit the native
     # assembler's 1 GiB arrays.  Chunks are independent (a chunk's tuple is what the per-chunk call returns), so long lists go
     # through in groups, and a group that still overflows is halved.
     if len(chunks) > MAX_BATCH_CHUNKS:
-        out = []
-        for i in range(0, len(chunks), MAX_BATCH_CHUNKS):
-            out += get_indel_testing_candidates_batch(dct, chunks[i:i + MAX_BATCH_CHUNKS], device=device, haploid=haploid, device_x=device_x,
-                                                      device_route=device_route)
-        return out
+        return [t for i in range(0, len(chunks), MAX_BATCH_CHUNKS) for t in get_indel_testing_candidates_batch(dct, chunks[i:i + MAX_BATCH_CHUNKS], **kw)]
     try:
         with _gc_paused():
-            return _indel_batch(dct, chunks, device, haploid, device_x, device_route)
+            return _indel_batch(dct, chunks, device, haploid, device_x, route, dedup)
     except _lib.NanoCallerHipError as e:
-        if getattr(e, "status", None) != _lib.NC_ERR_CAPACITY or len(chunks) == 1:
+        if e.status != _lib.NC_ERR_CAPACITY or len(chunks) == 1:
             raise
     h = len(chunks) // 2
-    return (get_indel_testing_candidates_batch(dct, chunks[:h], device=device, haploid=haploid, device_x=device_x, device_route=device_route) +
-            get_indel_testing_candidates_batch(dct, chunks[h:], device=device, haploid=haploid, device_x=device_x, device_route=device_route))
+    return get_indel_testing_candidates_batch(dct, chunks[:h], **kw) + get_indel_testing_candidates_batch(dct, chunks[h:], **kw)
 
 
 @contextlib.contextmanager
@@ -545,450 +570,103 @@ def _gc_paused():
     """The batch builds ~10^5 result objects (tuples, strings) that all survive: every threshold they cross starts a
     collection that finds nothing, and a full one walks the whole heap (measured: 53 ms of a 125 ms batch of 40 chunks went into
     one generation-2 pass started from the allele list).  Collections are postponed to the end of the call."""
-    if os.environ.get("NC_KEEP_GC") or not gc.isenabled():
-        yield
-        return
+    was = gc.isenabled()
     gc.disable()
     try:
         yield
     finally:
-        gc.enable()
+        if was:
+            gc.enable()
 
 
-MAX_BATCH_CHUNKS = 64          # chunks per native pass-2 / alignment call (100 kb chunks at 30x: ~15 k anchors, ~150 MB of read windows)
-
-
-
-# ------------------------------------------------------------------------------------------------- device-resident pass 1 + 2
-TAIL_CAP = 272                 # query bases kept behind a read's last aligned base (>= the longest window, 260 + rounding)
-
-
-def device_indel_reads(ctg, flag, dp, device):
-    """The per-read inputs of the device pass 2 beyond the read pack: inserted bases of every insertion event, the bases that
-    follow the last aligned one, PS tags (nc_indel_pack_build), uploaded once per (contig, flag filter).  -> (IndelReadsC, tensors)"""
-    key = ("dev_reads", flag, device)
-    if key in ctg and ctg[key][2] is not dp:                         # the pack was rebuilt (LRU eviction, release_contig): these pointers belong to the old one
-        del ctg[key]
-    if key not in ctg:
-        L = _lib.lib()
-        keep = ctg["keep"][flag]
-        h = C.c_void_p()
-        rc = L.nc_indel_pack_build(ctg["handle"], _lib.npp(keep), TAIL_CAP, C.byref(h))
-        if rc != _lib.NC_OK:
-            raise _lib.NanoCallerHipError("nc_indel_pack_build failed (%d)" % rc)
-        try:
-            v = _lib.IndelPackArraysC()
-            L.nc_indel_pack_view(h, C.byref(v))
-            if dp.events is None or dp.reads is None or v.n_reads != dp.events["n_reads"] or v.n_reads != dp.reads["n_reads"]:
-                err = _lib.NanoCallerHipError("the contig's read pack carries no indel events / read table for %d kept reads" % v.n_reads)
-                err.status = _lib.NC_ERR_CAPACITY                   # the callers fall back to the host-assembled route
-                raise err
-            dev = get_engine(device).device
-
-            def up(ptr, cnt, dt):
-                a = np.frombuffer((C.c_char * (int(cnt) * np.dtype(dt).itemsize)).from_address(ptr), dt) if cnt and ptr else np.zeros(0, dt)
-                a = a if a.size else np.zeros(4, dt)
-                return torch.from_numpy(a.copy()).to(dev)
-            t = dict(ins_off=up(v.ins_off, v.n_events + 1, np.int32), ins_bases=up(v.ins_bases, v.n_ins_bases, np.uint8),
-                     tail_off=up(v.tail_off, v.n_reads + 1, np.int32), tail_bases=up(v.tail_bases, v.n_tail_bases, np.uint8),
-                     read_ps=up(v.read_ps, v.n_reads, np.int32), read_flag=up(v.read_flag, v.n_reads, np.uint8))
-        finally:
-            L.nc_indel_pack_free(h)
-        ev, rd = dp.events, dp.reads
-        st = _lib.IndelReadsC(n_reads=rd["n_reads"], slot_off=rd["slot_off"].data_ptr(), rd_start=rd["rd_start"].data_ptr(), rd_end=rd["rd_end"].data_ptr(),
-                              ev_off=ev["ev_off"].data_ptr(), ev_pos=ev["ev_pos"].data_ptr(), ev_len=ev["ev_len"].data_ptr(),
-                              ins_off=t["ins_off"].data_ptr(), ins_bases=t["ins_bases"].data_ptr(), tail_off=t["tail_off"].data_ptr(),
-                              tail_bases=t["tail_bases"].data_ptr(), read_ps=t["read_ps"].data_ptr(), read_hap=ev["read_hap"].data_ptr(),
-                              read_flag=t["read_flag"].data_ptr())
-        ctg[key] = (st, t, dp)                                       # dp: keeps the pack's tensors alive with the pointers
-    return ctg[key][0]
-
-
-def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, win_size, small_win_size, ins_t, del_t, window_after,
-                       haploid=False, excl=None, fetch=True, impute=False, mates=None, scoring=None):
-    """nc_indel_sites_plan + _run (+ _fetch) for a list of (start, end) chunks of one contig -> dict: n, x (device float32
-    [n, sets * 5, 128, 2]: the CNN input), and with fetch: pos / chunk / type / phase int32 [n], ref_len / alt_len int32 [n, sets],
-    alt (uint8 codes, the ALT prefixes back to back in (site, set) order).  mates: indel_mate_table's (key, rec) when kept alignments share read
-    names.  scoring: the star alignment's (gap open, gap extend, match, mismatch), default _lib.STAR_SCORING; nc_indel_sites_scoring refuses values
-    the 16-bit aligners do not cover.  Raises NanoCallerHipError with .status."""
-    L = eng.L
-    prm = _lib.IndelScanParamsC(mincov=int(mincov), win_size=int(win_size), small_win_size=int(small_win_size), ins_t=float(ins_t),
-                                del_t=float(del_t), haploid=1 if haploid else 0, impute=1 if (impute and not haploid) else 0)
-    starts = np.ascontiguousarray([c[0] for c in chunks], np.int32)
-    ends = np.ascontiguousarray([c[1] for c in chunks], np.int32)
-    pc = dp.c_struct()
-    n, na = C.c_int32(), C.c_int64()
-
-    def check(rc, what):
-        if rc != _lib.NC_OK:
-            msg = L.nc_last_error(eng.ctx)
-            err = _lib.NanoCallerHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
-            err.status = rc
-            raise err
-    check(L.nc_indel_sites_scoring(eng.ctx, *[int(v) for v in (_lib.STAR_SCORING if scoring is None else scoring)]), "nc_indel_sites_scoring")
-    # alignments that share read names: the plan keys them by name from this table (none: no table, the plain kernels run).  The context borrows
-    # the pointers, so the table is cleared again once the plan's and the run's launches are enqueued, whatever their outcome
-    check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,
-                               C.c_void_p(mates[1].data_ptr()) if mates else None), "nc_indel_set_mates")
-    S = 1 if haploid else 3
-    try:
-        check(L.nc_indel_sites_plan(eng.ctx, C.byref(pc), C.c_void_p(dp.ref_code.data_ptr()), dp.tile_pos0, dp.ref_code.numel(), int(chrom_len),
-                                    C.byref(reads_c), C.c_void_p(excl.data_ptr()) if excl is not None else None, len(chunks), _lib.npp(starts),
-                                    _lib.npp(ends), C.byref(prm), int(window_after), int(maxcov), C.byref(n), C.byref(na)), "nc_indel_sites_plan")
-        N = n.value
-        x = torch.empty((N, S * 5, 128, 2), dtype=torch.float32, device=eng.device)
-        check(L.nc_indel_sites_run(eng.ctx, C.c_void_p(x.data_ptr())), "nc_indel_sites_run")
-    finally:
-        if mates:
-            L.nc_indel_set_mates(eng.ctx, 0, None, None)
-    out = dict(n=N, sets=S, x=x, n_alignments=na.value)
-    if fetch:
-        out.update(indel_sites_fetch(eng, N, S))
+def _indel_batch(dct, chunks, device, haploid, device_x, route=None, dedup=True):
+    """the per-chunk tuples of `chunks`, part by part as plan_routes lays them out"""
+    out = [None] * len(chunks)
+    for kind, idx, d in plan_routes(dct, chunks, haploid, route, device=device):
+        part = [chunks[k] for k in idx]
+        tuples = device_part(_indel_batch_device, d, part, device, haploid, device_x) if kind == "device" else None
+        if tuples is None:
+            tuples = _indel_batch_host(d, part, device, haploid, device_x, dedup)
+        for k, t in zip(idx, tuples):
+            out[k] = t
     return out
 
 
-def indel_sites_fetch(eng, N, S):
-    L = eng.L
-    pos, chunk, typ, phase = (np.empty(max(N, 1), np.int32) for _ in range(4))
-    rl, al = np.empty((max(N, 1), S), np.int32), np.empty((max(N, 1), S), np.int32)
-    nb = C.c_int64()
-    rc = L.nc_indel_sites_fetch(eng.ctx, _lib.npp(pos), _lib.npp(chunk), _lib.npp(typ), _lib.npp(phase), _lib.npp(rl), _lib.npp(al), C.byref(nb))
-    if rc != _lib.NC_OK:
-        msg = L.nc_last_error(eng.ctx)
-        err = _lib.NanoCallerHipError("nc_indel_sites_fetch failed (%d): %s" % (rc, msg.decode() if msg else ""))
-        err.status = rc
-        raise err
-    alt = np.empty(max(int(nb.value), 1), np.uint8)
-    if nb.value:
-        rc = L.nc_indel_sites_fetch_alt(eng.ctx, _lib.npp(alt), int(nb.value))
-        if rc != _lib.NC_OK:
-            raise _lib.NanoCallerHipError("nc_indel_sites_fetch_alt failed (%d)" % rc)
-    return dict(pos=pos[:N], chunk=chunk[:N], type=typ[:N], phase=phase[:N], ref_len=rl[:N], alt_len=al[:N], alt=alt[:int(nb.value)])
-
-
-MATE_RING_CAP = 64           # alignments of one read name that k_hap_depth_b, k_event_tiles and k_sets<.., true> walk (their `guard` loops)
-
-
-def indel_mate_table(dp, read_ps):
-    """nc_indel_set_mates' table of a pack whose kept alignments share read names (dp.mates: pack.mate_table's key / rec on the device), or None.
-    The reference keys hap_reads_0 / hap_reads_1 and phase_dict by name (generate_indel_pileups.py:178-188): a name is in a hap set when ANY of its
-    records carries that HP (in both when they disagree), and phase_dict[name] is the PS of its LAST record in file order, None (0 here) when that
-    record has no HP.  read_ps: the pack's PS per kept read (device int32).  -> (key int64 [M], rec int32 [M, 8]) device tensors.
-    A name with more than MATE_RING_CAP kept alignments is refused (NC_ERR_UNSUPPORTED): the kernels walk a ring that far and no further."""
-    if getattr(dp, "mates", None) is None or dp.reads is None or dp.events is None:
-        return None
-    key, rec4 = dp.mates
-    M = int(key.numel())
-    if M == 0:
-        return None
-    K = int(dp.reads["n_reads"])
-    r = torch.searchsorted(dp.reads["slot_off"][:K].contiguous(), key.contiguous())       # the member's index among the kept reads (slots are unique)
-    if int((r >= K).any()) or not bool((dp.reads["slot_off"][r] == key).all()):
-        raise _lib.NanoCallerHipError("indel_mate_table: the table of shared names is not this pack's")
-    rec4 = rec4.view(-1, 4).cpu().numpy()
-    hap = dp.events["read_hap"][r].cpu().numpy().astype(np.int32)
-    ps = read_ps[r].cpu().numpy().astype(np.int32)
-    idx = np.arange(M, dtype=np.int64)
-    nxt = rec4[:, 2].astype(np.int64)
-    if M < 2 or nxt.min() < 0 or nxt.max() >= M:
-        raise _lib.NanoCallerHipError("indel_mate_table: the table of shared names is not this pack's")
-    g, cur = idx.copy(), nxt.copy()                                 # the name's first member: the smallest index on the member's ring
-    for _ in range(MATE_RING_CAP - 1):                              # (cur: one hop further per step, held once it is back at the member)
-        g = np.minimum(g, cur)
-        cur = np.where(cur != idx, nxt[cur], cur)
-    if (cur != idx).any():
-        err = _lib.NanoCallerHipError("indel_mate_table: a read name with more than %d kept alignments (the first: alignment %d of the kept ones)"
-                                      % (MATE_RING_CAP, int(r[int(np.flatnonzero(cur != idx)[0])])))
-        err.status = _lib.NC_ERR_UNSUPPORTED
-        raise err
-    bits = np.zeros(M, np.int32)
-    np.bitwise_or.at(bits, g, np.where((hap == 1) | (hap == 2), 1 << (hap - 1).clip(0, 1), 0).astype(np.int32))
-    last = np.zeros(M, np.int64)
-    np.maximum.at(last, g, idx)
-    rec = np.zeros((M, 8), np.int32)
-    rec[:, :3] = rec4[:, :3]
-    rec[:, 3] = r.cpu().numpy()
-    rec[:, 4] = bits[g]
-    rec[:, 5] = np.where(hap[last[g]] != 0, ps[last[g]], 0)
-    return key.contiguous(), torch.from_numpy(rec).to(key.device)
-
-
-_DEV_INGEST = {}              # one contig at a time: (BAM, contig, FASTA, flag filter, device, by name or not, file identity) -> (pack, nc_indel_reads, contig dict, indel_mate_table or None)
-
-
-def _device_ingest_contig(dct, sam_path, chrom, supp, device, by_name=False):
-    """The contig's read pack WITH the indel sections, made on the device from the BAM file itself (device_bam.py: inflate, record walk, codes,
-    events, inserted bases and tails in HBM) -- what decoded_contig + device_pack + device_indel_reads assemble on host threads.  None when the
-    input cannot take that route (no .bai and no dct['build_index'] / NC_BUILD_INDEX=1 to make one, too large, NC_DEVICE_INGEST=0 / dct['device_ingest'] = False): the host route follows."""
-    if not dct.get("device_ingest", os.environ.get("NC_DEVICE_INGEST", "1") != "0") or not isinstance(sam_path, str) or not os.path.exists(sam_path):
-        return None
-    st = os.stat(sam_path)
-    key = (sam_path, chrom, dct["fasta_path"], supp, device, bool(by_name), st.st_size, st.st_mtime_ns)
-    if key not in _DEV_INGEST:
-        from .device_bam import DeviceIngestUnavailable, ensure_index, open_device_bam
-        from .device_fasta import reference_for
-        from .wire import indel_reads_struct
-        _DEV_INGEST.clear()
-        ensure_index(sam_path, dct, device)                              # (dct['build_index'] / NC_BUILD_INDEX=1: a BAM without index gets one)
-        try:
-            dbam = open_device_bam(sam_path, device, contigs=[chrom])
-        except DeviceIngestUnavailable:
-            return None
-        # the letters as bytes, or (a bgzipped FASTA; a plain one with dct['device_fasta'] / NC_DEVICE_FASTA=1) the contig in HBM: the pack's
-        # reference codes come from there, and the host's copy of the letters -- the windows' reference text -- is one D2H
-        ref = reference_for(dct["fasta_path"], chrom, device, dct)
-        dp = dbam.pack(dbam.prepare(chrom, ref, supplementary=supp, haplotags=getattr(sam_path, "tags", None), by_name=bool(by_name)), indel=True,
-                       tail_cap=TAIL_CAP)
-        ref_contig = ref if hasattr(ref, "scan_codes") else None
-        if ref_contig is not None:
-            try:
-                fasta_b = ref_contig.host_letters()
-            except DeviceIngestUnavailable:
-                from .bam import read_fasta_bytes
-                fasta_b, ref_contig = read_fasta_bytes(dct["fasta_path"], chrom), None
-        else:
-            fasta_b = ref
-        _DEV_INGEST[key] = (dp, indel_reads_struct(dp), dict(fasta=fasta_b.decode("ascii"), fasta_b=fasta_b, device_ingest=True, ref_contig=ref_contig),
-                            indel_mate_table(dp, dp.indel["read_ps"]) if by_name else None)
-    return _DEV_INGEST[key]
-
-
-def _indel_pack_for(dct, chunks, device, by_name=False):
-    """(engine, read pack with the indel sections, nc_indel_reads struct, contig dict, exclusion mask or None, table of shared names or None) of the
-    chunks' BAM and contig: made on the device from the BAM file itself where that route is open (_device_ingest_contig), else from the host decode.
-    by_name (the device pipeline without impute_indel_phase): kept alignments that share a read name are not refused, and the last item is their
-    table for nc_indel_set_mates (None without by_name or when no name is shared).  The device-ingested packs of the two settings are cached apart;
-    the host decode's pack is one and the same (it always carries bit 3 and the name rings: by_name only lifts the refusal)."""
-    chrom, sam_path = chunks[0]["chrom"], chunks[0]["sam_path"]
-    supp = bool(dct.get("supplementary"))
-    eng = get_engine(device)
-    eng.use_torch_stream()
-    di = _device_ingest_contig(dct, sam_path, chrom, supp, device, by_name)
-    if di is not None:
-        dp, reads_c, ctg, mates = di
-    else:
-        ctg = decoded_contig(sam_path, chrom, dct["fasta_path"])
-        flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if supp else 0x800)
-        if flag not in ctg["keep"]:
-            from .pack import pileup_depth_cap
-            dec = ctg["dec"]
-            ctg["keep"][flag] = pileup_depth_cap(dec["read_start"], dec["read_end"], np.ascontiguousarray((dec["read_flag"] & flag) == 0, np.uint8))
-        dp = device_pack(sam_path, dct.get("fasta_path"), chrom, supp, None, device, by_name=by_name)[0]
-        reads_c = device_indel_reads(ctg, flag, dp, device)
-        mates = None
-        if by_name and getattr(dp, "mates", None) is not None:
-            mk = ("dev_mates", flag, device)
-            if mk not in ctg or ctg[mk][0] is not dp:
-                ctg[mk] = (dp, indel_mate_table(dp, ctg[("dev_reads", flag, device)][1]["read_ps"]))
-            mates = ctg[mk][1]
-    excl = None
-    excl_rows = _exclude_rows(dct, chrom)
-    if excl_rows:
-        m = np.zeros(dp.n_tiles * dp.tile_size, np.uint8)
-        for (a, b) in excl_rows:
-            m[max(0, a - dp.tile_pos0):max(0, b - dp.tile_pos0)] = 1
-        excl = torch.from_numpy(m).to(eng.device)
-    return eng, dp, reads_c, ctg, excl, mates
-
-
-def imputed_chunk_mask(dct, chunks, device):
-    """impute_indel_phase (generate_indel_pileups.py:278-304) on the device pipeline: which chunks hold a column that meets the rule's COLUMN-level
-    predicate (:278-284; K7's col_type 2 on the resident pack).  A chunk without one takes no imputed anchor, and its `variants` are those of the flag
-    off -- it runs on the device pipeline; the others (their read grouping needs the pileup strings, :285-304) take the host-assembled route."""
-    eng, dp, _, _, excl, _ = _indel_pack_for(dct, chunks, device)
-    cols = eng.indel_scan_batch(dp, [(c["start"], c["end"]) for c in chunks], mincov=dct["mincov"], win_size=dct["win_size"],
-                                small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"], excl=excl, haploid=False, impute=True)
-    return [bool((ct == 2).any()) for ct in cols]
+_indel_pack_for = indel_pack_for                                    # (its name before it moved)
 
 
 def indel_sites_for_chunks(dct, chunks, device, haploid, fetch=True):
-    """The device pipeline for chunks (ascending) of one BAM and contig -> (result dict of indel_sites_device, contig dict)"""
-    window_after = 260 if dct["seq"] == "pacbio" else 160
+    """The device pipeline for chunks of one BAM and contig, run in ascending (start, end) order -> (result dict of indel_sites_device, contig
+    dict, order: the chunk index behind each of the result's chunk numbers)"""
+    order = sorted(range(len(chunks)), key=lambda k: (chunks[k]["start"], chunks[k]["end"]))
     # shared read names are keyed by name here (nc_indel_set_mates), except with impute_indel_phase (diploid), whose read grouping is per alignment:
     # that combination keeps the refusal
     by_name = haploid or not dct.get("impute_indel_phase")
-    eng, dp, reads_c, ctg, excl, mates = _indel_pack_for(dct, chunks, device, by_name=by_name)
-    r = indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), [(c["start"], c["end"]) for c in chunks], mincov=dct["mincov"], maxcov=dct["maxcov"],
-                           win_size=dct["win_size"], small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"],
-                           window_after=window_after, haploid=haploid, excl=excl, fetch=fetch, impute=bool(dct.get("impute_indel_phase")),
+    eng, dp, reads_c, ctg, excl, mates = indel_pack_for(dct, chunks, device, by_name=by_name)
+    r = indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), [(chunks[k]["start"], chunks[k]["end"]) for k in order], mincov=dct["mincov"],
+                           maxcov=dct["maxcov"], win_size=dct["win_size"], small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"],
+                           window_after=window_after_of(dct), haploid=haploid, excl=excl, fetch=fetch, impute=bool(dct.get("impute_indel_phase")),
                            mates=mates)
-    return r, ctg
+    return r, ctg, order
 
 
-def _indel_batch_device(dct, chunks, device, haploid, device_x):
-    """_indel_batch on the device-resident pipeline (impute_indel_phase: only chunks impute_split_chunks sends here): the per-chunk tuples of the reference's calls"""
-    order = sorted(range(len(chunks)), key=lambda k: (chunks[k]["start"], chunks[k]["end"]))
-    r, ctg = indel_sites_for_chunks(dct, [chunks[k] for k in order], device, haploid)
-    tuples = sites_to_tuples(r, len(chunks), ctg["fasta"], haploid, device_x)
-    out = [None] * len(chunks)
-    for k, t in zip(order, tuples):
-        out[k] = t
+def _by_chunk(order, parts):
+    out = [None] * len(order)
+    for k, p in zip(order, parts):
+        out[k] = p
     return out
 
 
-def device_route_ok(dct, chunks, haploid, impute_split=False):
-    """the device pipeline covers BAM inputs; its plan takes chunks whose starts AND ends ascend (nc_indel_sites_plan): nested or overlapping chunk
-    lists, which sorting by (start, end) does not make monotone, go through the host-assembled route instead of failing the worker.  With
-    dct['impute_indel_phase'] (diploid) the route is open only to callers that split the chunk list first (impute_split_chunks: chunks with a
-    column that meets the rule's predicate take the host-assembled route, whose read grouping needs the pileup strings)"""
-    imputes = bool(dct.get("impute_indel_phase")) and not haploid
-    if imputes and os.environ.get("NC_IMPUTE_SPLIT") == "0":
-        return False
-    if not (isinstance(chunks[0]["sam_path"], str) and (impute_split or not imputes or impute_on_device())
-            and not os.environ.get("NC_INDEL_HOST_PASS2")):
-        return False
-    ends = [c["end"] for c in sorted(chunks, key=lambda c: (c["start"], c["end"]))]
-    return all(b >= a for a, b in zip(ends, ends[1:]))
+def _indel_batch_device(dct, chunks, device, haploid, device_x):
+    """everything between the column decisions and the CNN input on the device (nc_pipe.hip) -> the per-chunk tuples of the reference's calls"""
+    r, ctg, order = indel_sites_for_chunks(dct, chunks, device, haploid)
+    return _by_chunk(order, sites_to_tuples(r, len(chunks), ctg["fasta"], haploid, device_x))
 
 
 def indel_chunks_vcf_text(dct, chunks, device, haploid, model_kind):
     """candidates -> tensors -> Indel_model -> genotype rules -> VCF record text for chunks of one BAM and contig, without a
     Python object per site: nc_indel_sites_* (device), nc_indel_forward (K9), nc_indel_vcf_format (native host rules).
     -> list of bytes, the records of every chunk (what indelCaller.indel_run writes chunk by chunk)"""
-    order = sorted(range(len(chunks)), key=lambda k: (chunks[k]["start"], chunks[k]["end"]))
-    r, ctg = indel_sites_for_chunks(dct, [chunks[k] for k in order], device, haploid)
-    out = [b""] * len(chunks)
-    N, S = r["n"], r["sets"]
-    if N == 0:
-        return out
+    r, ctg, order = indel_sites_for_chunks(dct, chunks, device, haploid)
+    if r["n"] == 0:
+        return [b""] * len(chunks)
     eng = get_engine(device)
-    probs = eng.indel_forward(model_kind, r["x"]).cpu().numpy()
-    del r["x"]
-    L = eng.L
-    chrom = chunks[0]["chrom"].encode()
-    cap = int(N) * (96 + len(chrom)) + 2 * int(np.maximum(r["ref_len"], 0).sum() + np.maximum(r["alt_len"], 0).sum()) * 2 + 4096
-    buf = np.empty(cap, np.uint8)
-    nb = C.c_int64()
-    coff = np.empty(len(chunks) + 1, np.int64)
-    pos, chunk, phase = (np.ascontiguousarray(r[k], np.int32) for k in ("pos", "chunk", "phase"))
-    rl, al = np.ascontiguousarray(r["ref_len"], np.int32), np.ascontiguousarray(r["alt_len"], np.int32)
-    rc = L.nc_indel_vcf_format(chrom, N, _lib.npp(pos), _lib.npp(chunk), len(chunks), _lib.npp(np.ascontiguousarray(probs, np.float32)), S,
-                               _lib.npp(rl), _lib.npp(al), _lib.npp(np.ascontiguousarray(r["alt"], np.uint8)), _lib.npp(phase), ctg["fasta_b"],
-                               len(ctg["fasta"]), 1 if haploid else 0, _lib.npp(buf), cap, C.byref(nb), _lib.npp(coff))
-    if rc != _lib.NC_OK:
-        raise _lib.NanoCallerHipError("nc_indel_vcf_format failed (%d)" % rc)
-    raw = buf[:nb.value].tobytes()
-    co = coff.tolist()
-    for j, k in enumerate(order):
-        out[k] = raw[co[j]:co[j + 1]]
-    return out
+    probs = eng.indel_forward(model_kind, r.pop("x")).cpu().numpy()
+    return _by_chunk(order, sites_to_vcf_text(eng, r, probs, chunks[0]["chrom"], len(chunks), ctg, haploid))
 
 
-def sites_to_tuples(r, n_chunks, fasta, haploid, device_x):
-    """the per-chunk tuples get_indel_testing_candidates[_haploid] returns, from the arrays of the device pipeline"""
-    N, S = r["n"], r["sets"]
-    empty = ([], [], []) if haploid else ([], [], [], [], [], [])
-    if N == 0:
-        return [empty for _ in range(n_chunks)]
-    x = r["x"] if device_x else r["x"].cpu().numpy().astype(np.float64)
-    pos, chunk = r["pos"].tolist(), r["chunk"]
-    rl, al = r["ref_len"].reshape(-1).tolist(), r["alt_len"].reshape(-1).tolist()
-    alt_all = np.frombuffer(b"AGTCN", np.uint8)[r["alt"]].tobytes().decode("ascii")
-    alleles, o = [], 0
-    for k in range(N):
-        p, row = pos[k], []
-        for t in range(S):
-            a, b = rl[k * S + t], al[k * S + t]
-            if a < 0:
-                row.append((None, None))
-            else:
-                row.append((fasta[p - 1:p - 1 + a], alt_all[o:o + b]))
-            o += max(b, 0)
-        alleles.append(row)
-    phase = [v if v else None for v in r["phase"].tolist()]          # PS of set 0's first read; a read without the tag (imputed sets): None (:181-183,349)
-    bounds = np.searchsorted(chunk, np.arange(n_chunks + 1))                       # sites are chunk-major
-    out = []
-    for ci in range(n_chunks):
-        a, b = int(bounds[ci]), int(bounds[ci + 1])
-        if a == b:
-            out.append(empty)
-        elif haploid:
-            out.append((pos[a:b], x[a:b], [alleles[k][0] for k in range(a, b)]))
-        else:
-            out.append((pos[a:b], x[a:b, 0:5], x[a:b, 5:10], x[a:b, 10:15], alleles[a:b], phase[a:b]))
-    return out
-
-def impute_on_device():
-    """[r6] the device pipeline groups the reads of the imputed columns itself (k_impute_flags, k_sets<.., true>); NC_IMPUTE_DEVICE=0: round 5's
-    split (chunks with a column that meets the rule's predicate take the host-assembled route)"""
-    return os.environ.get("NC_IMPUTE_DEVICE", "1") != "0"
-
-
-def impute_split_chunks(dct, chunks, device, haploid):
-    """dct['impute_indel_phase'] on a chunk list the device pipeline could take, when the device does not group the reads itself
-    (NC_IMPUTE_DEVICE=0): -> (indices for the device pipeline, indices for the host-assembled route), or None when there is nothing to split
-    (flag off, haploid, route closed, or the device takes the rule).  NC_IMPUTE_SPLIT=0: everything on the host-assembled route"""
-    if not dct.get("impute_indel_phase") or haploid or os.environ.get("NC_IMPUTE_SPLIT") == "0" or not device_route_ok(dct, chunks, haploid, impute_split=True):
-        return None
-    if impute_on_device():
-        return None
-    order = sorted(range(len(chunks)), key=lambda k: (chunks[k]["start"], chunks[k]["end"]))
-    mask = imputed_chunk_mask(dct, [chunks[k] for k in order], device)
-    dev = sorted(k for k, m in zip(order, mask) if not m)
-    host = sorted(k for k, m in zip(order, mask) if m)
-    return dev, host
-
-
-def _indel_batch(dct, chunks, device, haploid, device_x, device_route=True):
-    """device_route=False: the caller has already met a capacity limit of the device pipeline for these chunks (indelCaller.indel_run): straight to
-    the host-assembled route instead of computing the expensive groups on the device a second time"""
+def _indel_batch_host(dct, chunks, device, haploid, device_x, dedup=True):
+    """the host-assembled route: pass 1 of every chunk in the same launches, the anchors of all chunks through one _pass2_native call"""
     chrom, sam_path = chunks[0]["chrom"], chunks[0]["sam_path"]
-    split = impute_split_chunks(dct, chunks, device, haploid) if device_route else None
-    if split is not None and split[0]:
-        # impute_indel_phase: the chunks without a column that meets the rule's predicate are the flag-off problem -> device pipeline
-        dev, host = split
-        off = dict(dct, impute_indel_phase=False)
-        out = [None] * len(chunks)
-        for k, t in zip(dev, _indel_batch(off, [chunks[k] for k in dev], device, haploid, device_x, True)):
-            out[k] = t
-        if host:
-            for k, t in zip(host, _indel_batch(dct, [chunks[k] for k in host], device, haploid, device_x, False)):
-                out[k] = t
-        return out
-    if device_route and device_route_ok(dct, chunks, haploid):
-        # everything between the column decisions and the CNN input on the device (nc_pipe.hip); a capacity limit of that route
-        # (sets of > 1024 alignment columns, chunks of > 130 kb) sends the group through the host-assembled route below
-        try:
-            return _indel_batch_device(dct, chunks, device, haploid, device_x)
-        except _lib.NanoCallerHipError as e:
-            if getattr(e, "status", None) != _lib.NC_ERR_CAPACITY:
-                raise
-    window_after = 260 if dct["seq"] == "pacbio" else 160
     extras = [dict() for _ in chunks]
     ctg = decoded_contig(sam_path, chrom, dct["fasta_path"]) if isinstance(sam_path, str) else None   # before pass 1: one decode for both
     variants = scan_indel_candidates(dct, chunks, device, haploid=haploid, extra_variants=None if haploid else extras)
     max_range = {0: max(10, dct["win_size"]), 1: 10}
-    per_chunk, flat_anchor, flat_chunk = [], [], []
-    for ci, (c, var) in enumerate(zip(chunks, variants)):
-        anc = sorted(v for v in var if max(0, c["start"] - 10 - dct["win_size"]) < v <= c["end"])
-        per_chunk.append(anc)
-        flat_anchor += anc
-        flat_chunk += [ci] * len(anc)
+    # (anchor, owner chunk) ascending over the contig: one sweep over the reads
+    flat = sorted((v, ci) for ci, (c, var) in enumerate(zip(chunks, variants)) for v in var if max(0, c["start"] - 10 - dct["win_size"]) < v <= c["end"])
     empty = ([], [], []) if haploid else ([], [], [], [], [], [])
-    if not flat_anchor:
+    if not flat:
         return [empty for _ in chunks]
     if ctg is None:
         raise ValueError("the batched indel featuriser reads a BAM file (chunk['sam_path'])")
-    order = np.argsort(np.asarray(flat_anchor), kind="stable")                      # ascending over the contig: one sweep over the reads
-    anchors = [flat_anchor[i] for i in order]
-    owner = [flat_chunk[i] for i in order]
+    anchors, owner = [v for v, _ in flat], [ci for _, ci in flat]
     # every anchor's window lies inside its own chunk's ref_dict range [start-200, end+400] (:174), so the contig-wide range is
-    # the same test; variant types / imputed sets are looked up per owner chunk
-    merged_var = _ChunkedLookup([variants[ci] for ci in owner], anchors)
+    # the same test; variant types / imputed sets are looked up per owner chunk, by ANCHOR INDEX (the same position can be an anchor of two
+    # adjacent chunks with different types)
+    merged_var = [variants[ci][v] for v, ci in zip(anchors, owner)]
     merged_extra = {}
     if not haploid:
         for k, (v, ci) in enumerate(zip(anchors, owner)):
             if v in extras[ci]:
                 merged_extra[k] = extras[ci][v]
-    res = _pass2_native(dct, merged_var, merged_extra, anchors, ctg, 1, len(ctg["fasta"]), window_after, max_range, device, haploid,
-                        by_index=True, device_x=device_x)
+    res = _pass2_native(dct, merged_var, merged_extra, anchors, ctg, 1, len(ctg["fasta"]), window_after_of(dct), max_range, device, haploid,
+                        by_index=True, device_x=device_x, dedup=dedup)
     pos, kept = res[0], res[-1]
     out = [[] for _ in chunks]
     for j, k in enumerate(kept):
         out[owner[k]].append(j)
     tuples = []
-    for ci in range(len(chunks)):
-        sel = out[ci]
+    for sel in out:
         if not sel:
             tuples.append(empty)
         elif haploid:
@@ -996,17 +674,6 @@ def _indel_batch(dct, chunks, device, haploid, device_x, device_route=True):
         else:
             tuples.append(([pos[j] for j in sel], res[1][sel], res[2][sel], res[3][sel], [res[4][j] for j in sel], [res[5][j] for j in sel]))
     return tuples
-
-
-class _ChunkedLookup:
-    """variants lookup by ANCHOR INDEX for a merged anchor list (the same position can be an anchor of two adjacent chunks
-    with different types)"""
-
-    def __init__(self, var_of_anchor, anchors):
-        self.t = [var[v] for var, v in zip(var_of_anchor, anchors)]
-
-    def __getitem__(self, k):
-        return self.t[k]
 
 
 def __getattr__(name):

@@ -9,23 +9,21 @@ from __future__ import annotations
 
 import numpy as np
 
-from .generate_indel_pileups import (_pass2_native, allele_prediction, decoded_contig, default_aligner, msa, scan_indel_candidates,
-                                     star_aligner)
+from .generate_indel_pileups import (_pass2_native, allele_prediction, decoded_contig, default_aligner, keep_flag, msa, scan_indel_candidates,
+                                     star_aligner, window_after_of)
 
 
 def get_indel_testing_candidates_haploid(dct, chunk, aligner=None, device=0):
     """generate_indel_pileups_haploid.py:128-277 -> (pos, x, alleles): one read set per anchor, no HP split."""
     from .bam import BamFile, read_fasta
     chrom, start, end = chunk["chrom"], chunk["start"], chunk["end"]
-    window_before, window_after = 0, 160
-    if dct["seq"] == "pacbio":
-        window_after = 260
+    window_before, window_after = 0, window_after_of(dct)
     variants = scan_indel_candidates(dct, chunk, device, haploid=True)
     empty = ([], [], [])
     if not variants:
         return empty
     lo, hi = max(1, start - 200), end + 400
-    flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if dct.get("supplementary") else 0x800)
+    flag = keep_flag(dct)
     anchors = sorted(v for v in variants if max(0, start - 10 - dct["win_size"]) < v <= end)
     max_range = {0: max(10, dct["win_size"]), 1: 10}
     if aligner is None and default_aligner() is star_aligner:

@@ -119,12 +119,15 @@ INDEL_VCF_HEADER = (                                                 # indelCall
     '#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{sample}\n')
 
 
-def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, worker_id=1, aligner=None):
+def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, worker_id=1, aligner=None, route=None, rules="native"):
     """Worker with the reference's signature (indelCaller.py:41-189): drains ('indel', chunk) jobs from `job_Q`, writes
     <intermediate_indel_files_dir>/<prefix>.<worker>.indel.vcf.  Per chunk: candidates + tensors + allele strings
     (generate_indel_pileups.get_indel_testing_candidates[_haploid]: window scan, star alignment / MUSCLE, K8), the indel CNN on
     the GPU for the whole chunk (the reference feeds batches of 100; the per-site probabilities do not depend on the batching),
-    then the genotype rules in batches of 100 with `prev` carried through the chunk."""
+    then the genotype rules in batches of 100 with `prev` carried through the chunk.
+    Without an external aligner, route= is generate_indel_pileups.plan_routes' (None, "host", "split") and rules= says who applies the genotype
+    rules to the device pipeline's sites: "native" (nc_indel_vcf_format, no Python object per site) or "python" (the per-chunk tuples and
+    indel_vcf_lines[_haploid], which the host-assembled route always takes): the same file every way."""
     import os
     import queue
     import sys
@@ -133,11 +136,14 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
 
     from . import _lib
     from .engine import get_engine
-    from .generate_indel_pileups import (default_aligner, device_route_ok, get_indel_testing_candidates, get_indel_testing_candidates_batch,
-                                         impute_split_chunks, indel_chunks_vcf_text, star_aligner)
+    from .generate_indel_pileups import (ROUTES, default_aligner, get_indel_testing_candidates, get_indel_testing_candidates_batch,
+                                         indel_chunks_vcf_text, plan_routes, star_aligner)
     from .generate_indel_pileups_haploid import get_indel_testing_candidates_haploid
+    from .indel_device import device_part
     from .phase import tagged_source
     from .weights import Weights
+    if route not in ROUTES or rules not in ("native", "python"):
+        raise ValueError("indel_run(route=%r, rules=%r): route is one of %r, rules 'native' or 'python'" % (route, rules, ROUTES))
     curr_vcf_path = os.path.join(params['intermediate_indel_files_dir'], '%s.%d.indel.vcf' % (params['prefix'], worker_id))
     indel_files_list.append(curr_vcf_path)
     model_path = get_indel_model(params['indel_model'])
@@ -171,28 +177,30 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
             o += len(t[0])
         return out
 
+    def write_chunk(f, text):
+        """a chunk's records go to the file, and to the disk, before the chunk is counted as done"""
+        f.write(text)
+        f.flush()
+        os.fsync(f.fileno())
+        counter_Q.put(1)
+
     def emit(f, chunk, tup, probs=None):
         chrom = chunk['chrom']
         if probs is None and len(tup[0]):
             probs = forward(chunk['ploidy'], [tup])[0]
+        out, prev = [], 0
         if chunk['ploidy'] == 'diploid':
             pos, x0, x1, x2, alleles_seq, phase = tup
-            if len(pos) != 0:
-                prev = 0
-                for b in range(0, len(pos), batch_size):
-                    lines, prev = indel_vcf_lines(chrom, pos[b:b + batch_size], probs[b:b + batch_size], alleles_seq[b:b + batch_size],
-                                                  phase[b:b + batch_size], prev)
-                    f.writelines(lines)
+            for b in range(0, len(pos), batch_size):
+                lines, prev = indel_vcf_lines(chrom, pos[b:b + batch_size], probs[b:b + batch_size], alleles_seq[b:b + batch_size],
+                                              phase[b:b + batch_size], prev)
+                out += lines
         elif chunk['ploidy'] == 'haploid':
             pos, x, alleles_seq = tup
-            if len(pos) != 0:
-                prev = 0
-                for b in range(0, len(pos), batch_size):
-                    lines, prev = indel_vcf_lines_haploid(chrom, pos[b:b + batch_size], probs[b:b + batch_size], alleles_seq[b:b + batch_size], prev)
-                    f.writelines(lines)
-        f.flush()
-        os.fsync(f.fileno())
-        counter_Q.put(1)
+            for b in range(0, len(pos), batch_size):
+                lines, prev = indel_vcf_lines_haploid(chrom, pos[b:b + batch_size], probs[b:b + batch_size], alleles_seq[b:b + batch_size], prev)
+                out += lines
+        write_chunk(f, ''.join(out))
 
     native = aligner in (None, "device") and (aligner == "device" or default_aligner() is star_aligner)
     with open(curr_vcf_path, 'w') as f:
@@ -221,64 +229,30 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
             for k, job in enumerate(jobs):
                 c = job[1]
                 groups.setdefault((c['sam_path'], c['chrom'], c['ploidy']), []).append(k)
-            # Each group is featurised, called and WRITTEN before the next one starts: nothing of a group outlives it in HBM.  The
-            # usual case runs without a Python object per site: device pipeline -> K9 -> native rules -> text (indel_chunks_vcf_text);
-            # impute_indel_phase, or a capacity limit of the device route, goes through the per-chunk tuples.
-            import os as _os
+            # Each group is featurised, called and WRITTEN before the next one starts: nothing of a group outlives it in HBM.  It goes part by
+            # part as plan_routes lays it out.  The usual part runs without a Python object per site: device pipeline -> K9 -> native rules -> text
+            # (indel_chunks_vcf_text); a host part, the Python rules, or a capacity limit of the device pipeline goes through the per-chunk tuples.
             for (sam, chrom, ploidy), ks in groups.items():
                 group = [jobs[k][1] for k in ks]
                 hap = ploidy == 'haploid'
-                texts = None
-                device_failed = False
-                split = impute_split_chunks(params, group, device, hap) if not _os.environ.get("NC_INDEL_PY_RULES") else None
-                if split is not None and split[0]:
-                    # impute_indel_phase (generate_indel_pileups.py:278-304): chunks without a column that meets the rule's predicate are the flag-off
-                    # problem and run on the device pipeline; the others need the pileup strings -> host-assembled route.  Written in job order.
-                    dev, host = split
-                    off = dict(params, impute_indel_phase=False)
-                    try:
-                        dtx = indel_chunks_vcf_text(off, [group[i] for i in dev], device, hap, _lib.MODEL_INDEL)
-                    except _lib.NanoCallerHipError as e:
-                        if getattr(e, "status", None) != _lib.NC_ERR_CAPACITY:
-                            raise
-                        dtx = None
-                    if dtx is not None:
-                        by = dict(zip(dev, dtx))
-                        htup, hpr = [], []
-                        if host:
-                            htup = get_indel_testing_candidates_batch(params, [group[i] for i in host], device=device, haploid=hap, device_x=True, device_route=False)
-                            hpr = forward(ploidy, htup)
-                            htup = [tuple(None if torch.is_tensor(v) else v for v in t) for t in htup]
-                        hby = {i: (t, pr) for i, t, pr in zip(host, htup, hpr)}
-                        for i, k in enumerate(ks):
-                            if i in by:
-                                f.write(by[i].decode("ascii"))
-                                f.flush()
-                                os.fsync(f.fileno())
-                                counter_Q.put(1)
-                            else:
-                                emit(f, jobs[k][1], hby[i][0], hby[i][1])
-                        continue
-                    device_failed = True
-                if device_route_ok(params, group, hap) and not _os.environ.get("NC_INDEL_PY_RULES"):
-                    try:
-                        texts = indel_chunks_vcf_text(params, group, device, hap, _lib.MODEL_INDEL_HAP if hap else _lib.MODEL_INDEL)
-                    except _lib.NanoCallerHipError as e:
-                        if getattr(e, "status", None) != _lib.NC_ERR_CAPACITY:
-                            raise
-                        device_failed = True                         # the tuple route below goes straight to the host-assembled featuriser
-                if texts is not None:
-                    for txt in texts:
-                        f.write(txt.decode("ascii"))
-                        f.flush()
-                        os.fsync(f.fileno())
-                        counter_Q.put(1)
-                    continue
-                tuples = get_indel_testing_candidates_batch(params, group, device=device, haploid=hap, device_x=True, device_route=not device_failed)
-                probs = forward(ploidy, tuples)
-                tuples = [tuple(None if torch.is_tensor(v) else v for v in t) for t in tuples]        # the tensors are not needed any more
-                for k, t, pr in zip(ks, tuples, probs):
-                    emit(f, jobs[k][1], t, pr)
+                done = [None] * len(group)                           # per chunk: its record text (bytes), or (tuple, probabilities)
+                for kind, idx, dct in plan_routes(params, group, hap, route, device=device):
+                    part = [group[i] for i in idx]
+                    texts, on_host = None, kind == "host"
+                    if kind == "device" and rules == "native":
+                        texts = device_part(indel_chunks_vcf_text, dct, part, device, hap, _lib.MODEL_INDEL_HAP if hap else _lib.MODEL_INDEL)
+                        on_host = texts is None                      # (not on the device a second time)
+                    if texts is None:
+                        tuples = get_indel_testing_candidates_batch(dct, part, device=device, haploid=hap, device_x=True, route="host" if on_host else None)
+                        probs = forward(ploidy, tuples)
+                        texts = [(tuple(None if torch.is_tensor(v) else v for v in t), pr) for t, pr in zip(tuples, probs)]   # the tensors are not needed any more
+                    for i, r in zip(idx, texts):
+                        done[i] = r
+                for k, r in zip(ks, done):                           # in job order
+                    if isinstance(r, bytes):
+                        write_chunk(f, r.decode("ascii"))
+                    else:
+                        emit(f, jobs[k][1], *r)
     return curr_vcf_path
 
 

@@ -196,14 +196,10 @@ def _realign_inputs(sam_path, fasta_path, chrom, supplementary, device):
     if not (isinstance(sam_path, str) and os.path.exists(sam_path)) or not fasta_path:
         raise _lib.NanoCallerHipError("phase_contig(realign=True) needs a BAM file and its FASTA: the alignments %r carry no inserted bases to rebuild "
                                       "the reads' query windows from (the column rule is not substituted)" % (sam_path,))
-    from . import generate_indel_pileups as gip
+    from .indel_device import indel_pack_for, keep_flag
     dct = dict(fasta_path=fasta_path, supplementary=bool(supplementary))
-    eng, dp, reads_c, ctg, _, _ = gip._indel_pack_for(dct, [dict(chrom=chrom, sam_path=sam_path)], device)
-    if ctg.get("device_ingest"):
-        ix = dp.indel
-    else:
-        flag = 0x4 | 0x100 | 0x200 | 0x400 | (0 if supplementary else 0x800)
-        ix = ctg[("dev_reads", flag, device)][1]
+    eng, dp, reads_c, ctg, _, _ = indel_pack_for(dct, [dict(chrom=chrom, sam_path=sam_path)], device)
+    ix = dp.indel if ctg.get("device_ingest") else ctg[("dev_reads", keep_flag(dct), device)][1]
     if dp.events is None or dp.reads is None or ix is None:
         raise _lib.NanoCallerHipError("phase_contig(realign=True): the pack of %r, contig %s, carries no indel events / inserted bases" % (sam_path, chrom))
     key = ("phase_ref_code", device)
@@ -218,12 +214,12 @@ def _ingest_records(sam_path, fasta_path, chrom, supplementary, device):
     reads' record offsets in pack order)).  The weighted model reads MAPQ and base qualities there and nowhere else: an input that does not take
     that route is refused, unit costs are not substituted."""
     from . import _lib
-    from . import generate_indel_pileups as gip
+    from .indel_device import ingest_contig
     why = None
     if not (isinstance(sam_path, str) and os.path.exists(sam_path)) or not fasta_path:
         why = "the alignments %r are not a BAM file with its FASTA (a World or a registered key carries no record bytes)" % (sam_path,)
     else:
-        di = gip._device_ingest_contig(dict(fasta_path=fasta_path, supplementary=bool(supplementary)), sam_path, chrom, bool(supplementary), device)
+        di = ingest_contig(dict(fasta_path=fasta_path, supplementary=bool(supplementary)), sam_path, chrom, bool(supplementary), device)
         if di is None:
             why = ("%s does not take the device ingest route (NC_DEVICE_INGEST=0, no .bai / .csi beside it, or too large for HBM)" % sam_path)
         elif getattr(di[0], "records", None) is None:

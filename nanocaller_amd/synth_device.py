@@ -181,7 +181,7 @@ def make_indel_device_workload(eng, L, depth=30.0, seed=812, tile_size=2048, het
     """Synthetic ONT contig with planted indels and HP / PS tags, generated in HBM (nc_synth_indel_*): the inputs of the
     device-resident indel pipeline.  -> (DevicePack with .events / .reads, IndelReadsC, info dict).  info['tensors'] keeps the
     device arrays alive; info['truth'] = (hap_indel int8 [2, L + 1] on the device)."""
-    from .generate_indel_pileups import TAIL_CAP  # noqa: F401  (documented bound of the tail section; synthetic reads have no soft clips)
+    from .indel_device import TAIL_CAP  # noqa: F401  (documented bound of the tail section; synthetic reads have no soft clips)
     dev = eng.device
     eng.use_torch_stream()
     L_ = _lib.lib()

@@ -212,7 +212,7 @@ def _device_sites(files, *, window_after=160, haploid=False, band=None, scoring=
     from nanocaller_amd import _lib
     ref, recs, bam, fa = files
     chunks = [dict(chrom=CHROM, start=1, end=len(ref), sam_path=bam)]
-    eng, dp, reads_c, ctg, excl, mates = gip._indel_pack_for(_dct(fa), chunks, 0, by_name=True)
+    eng, dp, reads_c, ctg, excl, mates = gip.indel_pack_for(_dct(fa), chunks, 0, by_name=True)
     assert eng.L.nc_indel_sites_band(eng.ctx, -1 if band is None else int(band), 0) == 0
     try:
         r = gip.indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), [(1, len(ref))], window_after=window_after, haploid=haploid, excl=excl,
@@ -265,9 +265,7 @@ def test_tie_world_band_off_returns_the_host_routes_tuples(tie_files, variant, m
     chunks = [dict(chrom=CHROM, start=s, end=min(len(ref), s + 2_999), sam_path=bam) for s in range(1, len(ref), 3_000)]
     gip._CONTIGS.clear()
     monkeypatch.setenv("NC_PIPE_BAND", "0")
-    monkeypatch.setenv("NC_INDEL_HOST_PASS2", "1")
-    exp = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=variant == "haploid")
-    monkeypatch.delenv("NC_INDEL_HOST_PASS2")
+    exp = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=variant == "haploid", route="host")
 
     def boom(*a, **k):
         raise AssertionError("the host-assembled route ran where the device pipeline was expected")

@@ -6,7 +6,6 @@ of the reference's rules (indelCaller.indel_vcf_lines[_haploid], itself pinned b
 GPU: the device pipeline returns, chunk by chunk, exactly the tuples of the host-assembled route (nc_indel_pass2_sets ->
 nc_star_msa_tensor_dup -> nc_allele_prediction_device), which tests/test_pass2_golden.py pins to the reference's own outputs."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -277,9 +276,7 @@ def test_device_pipeline_returns_the_host_routes_tuples(world_files, variant, mo
     dct = _params(fa, **kw)
     chunks = [dict(chrom=w.chrom, start=s, end=min(w.length, s + step), sam_path=bam) for s in range(1, w.length, step)]
     gip._CONTIGS.clear()
-    monkeypatch.setenv("NC_INDEL_HOST_PASS2", "1")
-    exp = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=haploid)
-    monkeypatch.delenv("NC_INDEL_HOST_PASS2")
+    exp = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=haploid, route="host")
 
     def boom(*a, **k):
         raise AssertionError("the host-assembled route ran where the device pipeline was expected")
@@ -356,17 +353,15 @@ def test_impute_indel_phase_splits_the_chunks_between_the_device_pipeline_and_th
     chunks = [dict(chrom=w.chrom, start=s, end=min(w.length, s + 10_000), sam_path=bam) for s in range(1, w.length, 10_000)]
     gip._CONTIGS.clear()
     monkeypatch.setenv("NC_PIPE_BAND", "0")                                          # the host-assembled route aligns on the full matrix
-    monkeypatch.setenv("NC_IMPUTE_SPLIT", "0")
-    exp = gip.get_indel_testing_candidates_batch(dct, chunks)
-    monkeypatch.delenv("NC_IMPUTE_SPLIT")
-    monkeypatch.setenv("NC_IMPUTE_DEVICE", "0")                                      # (round 5's route; the default groups on the device: next test)
-    dev, host = gip.impute_split_chunks(dct, chunks, 0, False)
+    exp = gip.get_indel_testing_candidates_batch(dct, chunks, route="host")
+    # (round 5's route; the default groups on the device: next test)
+    (_, dev, _), (_, host, _) = gip.plan_routes(dct, chunks, False, route="split")
     assert len(dev) >= 4 and len(host) >= 2 and sorted(dev + host) == list(range(len(chunks)))
     assert all(30_000 - 10_000 < chunks[k]["start"] < 60_000 + 200 for k in host), [chunks[k]["start"] for k in host]
     calls = []
     real = gip._indel_batch_device
     monkeypatch.setattr(gip, "_indel_batch_device", lambda d, c, *a: (calls.append(len(c)), real(d, c, *a))[1])
-    got = gip.get_indel_testing_candidates_batch(dct, chunks)
+    got = gip.get_indel_testing_candidates_batch(dct, chunks, route="split")
     assert calls == [len(dev)]
     n = _same_tuples(got, exp)
     assert n > 60
@@ -376,18 +371,14 @@ def test_impute_indel_phase_splits_the_chunks_between_the_device_pipeline_and_th
     assert len(ex) > 3 and all(any(chunks[k]["start"] - 60 <= a <= chunks[k]["end"] for k in host) for a in ex)
     # indelCaller.indel_run: the same file either way
     outs = []
-    for tag, split in (("host", "0"), ("split", None)):
-        if split:
-            monkeypatch.setenv("NC_IMPUTE_SPLIT", split)
-        else:
-            monkeypatch.delenv("NC_IMPUTE_SPLIT", raising=False)
+    for tag in ("host", "split"):
         d = tmp_path / tag
         d.mkdir()
         params = _params(fa, impute_indel_phase=True, mincov=3, ins_t=0.3, del_t=0.3, indel_model="ONT-HG002", intermediate_indel_files_dir=str(d), prefix="t")
         jobs = queue.Queue()
         for c in chunks:
             jobs.put(("indel", dict(c, ploidy="diploid")))
-        outs.append(open(indelCaller.indel_run(params, {}, jobs, queue.Queue(), [], aligner="device")).read())
+        outs.append(open(indelCaller.indel_run(params, {}, jobs, queue.Queue(), [], aligner="device", route=tag)).read())
     assert outs[0] == outs[1] and outs[0].count("\n") > 40
 
 
@@ -408,9 +399,7 @@ def test_impute_indel_phase_on_the_device_pipeline_equals_the_host_assembled_rou
         chunks = [dict(chrom=w.chrom, start=s, end=min(w.length, s + 10_000), sam_path=bam) for s in range(1, w.length, 10_000)]
         gip._CONTIGS.clear()
         monkeypatch.setenv("NC_PIPE_BAND", "0")                                      # the host-assembled route aligns on the full matrix
-        monkeypatch.setenv("NC_IMPUTE_SPLIT", "0")
-        exp = gip.get_indel_testing_candidates_batch(dct, chunks)
-        monkeypatch.delenv("NC_IMPUTE_SPLIT")
+        exp = gip.get_indel_testing_candidates_batch(dct, chunks, route="host")
         real = gip._pass2_native
 
         def boom(*a, **k):
@@ -424,24 +413,18 @@ def test_impute_indel_phase_on_the_device_pipeline_equals_the_host_assembled_rou
         ev, ex = oracle.indel_scan_impute(w, 28_000, 62_000, mincov=kw["mincov"], win_size=40, small_win_size=4, ins_t=kw["ins_t"], del_t=kw["del_t"])
         got_pos = {int(p) for t in got for p in t[0]}
         assert len(ex) > 3 and len(got_pos & set(ex)) >= 1 and any(p < 25_000 or p > 65_000 for p in got_pos), (kw, len(ex))
-    # round 5's split (NC_IMPUTE_DEVICE=0) still gives the same
-    monkeypatch.setenv("NC_IMPUTE_DEVICE", "0")
-    assert _same_tuples(gip.get_indel_testing_candidates_batch(dct, chunks), exp) == n
-    monkeypatch.delenv("NC_IMPUTE_DEVICE")
+    # round 5's split (route="split") still gives the same
+    assert _same_tuples(gip.get_indel_testing_candidates_batch(dct, chunks, route="split"), exp) == n
     # indelCaller.indel_run: the same file either way
     outs = []
-    for tag, split in (("host", "0"), ("device", None)):
-        if split:
-            monkeypatch.setenv("NC_IMPUTE_SPLIT", split)
-        else:
-            monkeypatch.delenv("NC_IMPUTE_SPLIT", raising=False)
+    for tag, route in (("host", "host"), ("device", None)):
         d = tmp_path / tag
         d.mkdir()
         params = _params(fa, impute_indel_phase=True, mincov=3, ins_t=0.3, del_t=0.3, indel_model="ONT-HG002", intermediate_indel_files_dir=str(d), prefix="t")
         jobs = queue.Queue()
         for c in chunks:
             jobs.put(("indel", dict(c, ploidy="diploid")))
-        outs.append(open(indelCaller.indel_run(params, {}, jobs, queue.Queue(), [], aligner="device")).read())
+        outs.append(open(indelCaller.indel_run(params, {}, jobs, queue.Queue(), [], aligner="device", route=route)).read())
     assert outs[0] == outs[1] and outs[0].count("\n") > 40
 
 
@@ -483,18 +466,14 @@ def test_indel_run_native_text_equals_the_python_rules(world_files, tmp_path, mo
     import queue
     w, bam, fa = world_files
     outs = []
-    for tag, env in (("py", "1"), ("native", None)):
-        if env:
-            monkeypatch.setenv("NC_INDEL_PY_RULES", env)
-        else:
-            monkeypatch.delenv("NC_INDEL_PY_RULES", raising=False)
+    for tag, rules in (("py", "python"), ("native", "native")):
         d = tmp_path / tag
         d.mkdir()
         params = _params(fa, indel_model="ONT-HG002", intermediate_indel_files_dir=str(d), prefix="t")
         jobs = queue.Queue()
         for s in range(1, w.length, 40_000):
             jobs.put(("indel", dict(chrom=w.chrom, start=s, end=min(w.length, s + 40_000), ploidy="diploid" if s < 100_000 else "haploid", sam_path=bam)))
-        outs.append(open(indelCaller.indel_run(params, {}, jobs, queue.Queue(), [], aligner="device")).read())
+        outs.append(open(indelCaller.indel_run(params, {}, jobs, queue.Queue(), [], aligner="device", rules=rules)).read())
     assert outs[0] == outs[1] and outs[0].count("\n") > 60
 
 

@@ -313,10 +313,9 @@ def test_skipping_repeated_alignments_changes_nothing(files, monkeypatch):
                    exclude_bed=None, impute_indel_phase=False, fasta_path=fa)
         dct.update(kw)
         chunks = [dict(chrom=w.chrom, start=s, end=min(w.length, s + 4_000), sam_path=bam) for s in range(1, w.length, 4_000)]
-        monkeypatch.delenv("NC_MSA_NO_DEDUP", raising=False)
-        got = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=False)
-        monkeypatch.setenv("NC_MSA_NO_DEDUP", "1")
-        exp = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=False)
+        # (route="host": the duplicate map belongs to the host-assembled route; the device pipeline has no such choice)
+        got = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=False, route="host")
+        exp = gip.get_indel_testing_candidates_batch(dct, chunks, haploid=False, route="host", dedup=False)
         assert sum(len(t[0]) for t in got) > 20
         for t, e in zip(got, exp):
             assert list(t[0]) == list(e[0])
