@@ -729,6 +729,18 @@ int nc_indel_sites_fetch(nc_ctx *ctx, int32_t *pos, int32_t *chunk, int32_t *var
                          int32_t *alt_len, int64_t *n_alt_bytes);
 /* the ALT prefixes back to back in (site, set) order, codes A0 G1 T2 C3 */
 int nc_indel_sites_fetch_alt(nc_ctx *ctx, uint8_t *alt_bases, int64_t cap);
+/* Indel columns to genotype whatever their event frequencies (known-sites calling for indels; ABI 11: an added export).  d_pos [n_sites]: 1-based
+ * columns of the contig on the device, any order, duplicates allowed; d_long [n_sites] uint8 (1 = the long-window class, 0 = the small one; a
+ * column listed with both is long) or NULL for all small.  The pointers are borrowed and read by the following nc_indel_sites_plan calls of the
+ * context; n_sites = 0 clears the list.  The candidate test of generate_indel_pileups.py:252-275 gains a third branch under the same depth test,
+ * `elif v_pos in list`, which writes the anchor of the column's class; the column predicate of impute_indel_phase (:285) reads `... or v_pos in
+ * list`; only != 0 makes the window rules and that predicate read False (the list is the only source of candidates; n_sites = 0 with only != 0 is
+ * a list that names nothing: no sites).  Everything else of pass 1 and pass 2 stays: the `prev` skip, exclusion, the depth tests, the dict
+ * overwrite of an equal anchor.  Columns outside every chunk or outside the pack's tile grid are dropped. */
+int nc_indel_set_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, const uint8_t *d_long, int32_t only);
+/* per fetched site: the listed column that wrote (or overwrote) the site's anchor, 0 for an anchor of the window rules alone; all 0 after a plan
+ * without a list.  Synchronises.  (ABI 11: an added export.) */
+int nc_indel_sites_fetch_src(nc_ctx *ctx, int32_t *src_col);
 /* per-stage HIP-event milliseconds of the last plan + run on this context (timing mode 1): [0] pass 1 + anchors + sets,
  * [1] query windows, [2] alignment fill, [3] traceback, [4] tensors + consensus, [5] allele alignment + extraction */
 int nc_indel_sites_stage_ms(nc_ctx *ctx, float *ms6, int64_t *cells2 /* [0] DP cells of the star alignments, [1] of the allele alignments */);

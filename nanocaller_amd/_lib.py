@@ -43,7 +43,7 @@ EXPORTS = [
     "nc_wire_build", "nc_wire_build_del", "nc_wire_apply_deletions", "nc_wire_ref_unpack", "nc_wire_view", "nc_wire_free", "nc_wire_expand", "nc_wire_expand_del", "nc_snp_set_mates", "nc_indel_set_mates", "nc_snp_scan_set_sites", "nc_decoded_name_groups", "nc_wire_ins_unpack", "nc_indel_events_pack8", "nc_indel_events_expand8", "nc_wire_build2", "nc_wire_expand2", "nc_d2h_async",
     "nc_indel_pass2_sets", "nc_pass2_view", "nc_pass2_free",
     "nc_decoded_check", "nc_indel_pack_build", "nc_indel_pack_view", "nc_indel_pack_free", "nc_indel_sites_plan", "nc_indel_sites_run",
-    "nc_indel_sites_fetch", "nc_indel_sites_fetch_alt", "nc_indel_sites_stage_ms", "nc_indel_sites_band_stats", "nc_indel_sites_band", "nc_indel_events_pack", "nc_indel_events_expand", "nc_inflate_device", "nc_inflate_device_phase", "nc_bgzf_crc_device", "nc_bgzf_members", "nc_bgzf_scan", "nc_bam_walk", "nc_bam_meta", "nc_bam_codes", "nc_bam_indel_reads", "nc_bam_name_groups", "nc_indel_sites_scoring", "nc_indel_vcf_format", "nc_synth_indel_truth", "nc_synth_indel_reads", "nc_cnn_x_limit", "nc_cnn_range_watch", "nc_snp_trunk_info",
+    "nc_indel_sites_fetch", "nc_indel_sites_fetch_alt", "nc_indel_set_sites", "nc_indel_sites_fetch_src", "nc_indel_sites_stage_ms", "nc_indel_sites_band_stats", "nc_indel_sites_band", "nc_indel_events_pack", "nc_indel_events_expand", "nc_inflate_device", "nc_inflate_device_phase", "nc_bgzf_crc_device", "nc_bgzf_members", "nc_bgzf_scan", "nc_bam_walk", "nc_bam_meta", "nc_bam_codes", "nc_bam_indel_reads", "nc_bam_name_groups", "nc_indel_sites_scoring", "nc_indel_vcf_format", "nc_synth_indel_truth", "nc_synth_indel_reads", "nc_cnn_x_limit", "nc_cnn_range_watch", "nc_snp_trunk_info",
     "nc_snp_phase_gather", "nc_snp_phase_load", "nc_snp_phase_solve", "nc_haplotag_run", "nc_snp_phase_view", "nc_snp_phase_free",
     "nc_snp_phase_realign", "nc_snp_phase_solve_gt", "nc_snp_phase_genotypes",
     "nc_snp_phase_set_weights", "nc_snp_phase_weights_from_bam", "nc_snp_phase_weights",
@@ -245,6 +245,8 @@ def lib():
         L.nc_indel_sites_scoring.argtypes = [vp, i32, i32, i32, i32]
         L.nc_indel_sites_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
         L.nc_indel_sites_fetch_alt.argtypes = [vp, vp, i64]
+        L.nc_indel_set_sites.argtypes = [vp, i32, vp, vp, i32]
+        L.nc_indel_sites_fetch_src.argtypes = [vp, vp]
         L.nc_indel_sites_stage_ms.argtypes = [vp, vp, vp]
         L.nc_indel_sites_band_stats.argtypes = [vp, vp]
         L.nc_indel_sites_band.argtypes = [vp, i32, i32]

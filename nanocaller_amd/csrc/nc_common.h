@@ -74,6 +74,11 @@ struct nc_ctx {
     const int32_t *gsite_pos = nullptr;
     bool gsites_only = false;
     DevBuf site_bits;                       // one bit per column of the scanned pack's tile grid (k_site_bits)
+    // indel columns to genotype (nc_indel_set_sites): borrowed device pointers, read by the next nc_indel_sites_plan calls
+    int32_t n_isites = 0;
+    const int32_t *isite_pos = nullptr;
+    const uint8_t *isite_long = nullptr;    // NULL: every listed column is of the small class
+    bool isites_only = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms[6] = {0, 0, 0, 0, 0, 0};   // 0 scan, 1 featurize, 2 cnn stage, 3 indel, 4 trunk kernel total, 5 trunk launches
     hipEvent_t kev[128] = {nullptr};          // per-launch event pairs of the trunk kernel (timing mode)

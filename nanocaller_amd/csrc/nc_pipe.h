@@ -4,6 +4,7 @@
 // structs below and reaches the kernels through the nc_pipe_launch_* / nc_pipe_scan_* functions at the end of this file.
 //
 //   nc_pipe_plan.hip     plan: k_impute_flags, k_pick, k_flatten, k_sets (anchors, read sets) and the two-launch scans
+//   nc_pipe_listed.hip   plan: k_listed, k_src_sites -- a given list of indel columns (nc_indel_set_sites) written into K7's col_type
 //   nc_pipe_windows.hip  run:  k_windows16 + k_window_lists (k_windows: the one-lane form) -- query windows and their band classes
 //   nc_pipe_align.hip          k_fill_band<1|2> (banded), k_fill16q (full matrix) -- the Gotoh DP; writes the traceback codes
 //   nc_pipe_trace.hip          k_trace_band12, k_end_cells, k_trace16p, k_allele_trace_b12, k_allele_trace16p -- reads them
@@ -77,6 +78,23 @@ struct SetArgs {
     ImpArgs imp;                       // (k_sets<.., true, ..>) the grouping of an imputed anchor's source column
     int32_t *err;
     IndelMates mt;                     // (k_sets<.., true>) alignments that share read names (nc_indel_set_mates); n = 0: none
+};
+
+// a given list of indel columns (nc_indel_set_sites) against one group of chunks and its col_type (k_listed)
+struct ListedArgs {
+    const int32_t *pos;                // [n_sites] 1-based columns, any order, duplicates allowed
+    const uint8_t *is_long;            // [n_sites] 1 = the long-window class, or NULL: all small
+    int32_t n_sites;
+    const PipeChunk *pc;               // the group's chunks (starts and ends ascend; coloff into ctype)
+    int32_t n_chunks;
+    int8_t *ctype;
+    const int32_t *tile_off;
+    const nc_tile_entry *tile_ent;
+    int32_t tile_pos0, tile_size, n_tiles;
+    const uint8_t *codes;
+    const uint8_t *excl;               // on the pack's grid, or NULL
+    int32_t mincov, haploid, impute;
+    IndelMates mt;                     // alignments that share read names; n = 0: none
 };
 
 struct WinArgs {
@@ -168,6 +186,9 @@ struct TensorArgs {
 // nc_pipe_plan.hip
 void nc_pipe_launch_impute_flags(hipStream_t st, int n_chunks, int maxcol, const PipeChunk *pc, int8_t *ctype, const ImpArgs &imp, int32_t *err);
 void nc_pipe_launch_pick(hipStream_t st, int n_chunks, const PipeChunk *pc, const int8_t *ctype, int32_t win, int32_t *seg_pos, int8_t *seg_type, int32_t *cnt, int32_t *err);
+// k_pick<true>: col_type may hold the forced codes 4 / 5 (k_listed); seg_src = the forced column behind an anchor, 0 for a natural one
+void nc_pipe_launch_pick_listed(hipStream_t st, int n_chunks, const PipeChunk *pc, const int8_t *ctype, int32_t win, int32_t *seg_pos, int8_t *seg_type,
+                                int32_t *seg_src, int32_t *cnt, int32_t *err);
 void nc_pipe_launch_flatten(hipStream_t st, int n_chunks, const PipeChunk *pc, const int32_t *seg_pos, const int8_t *seg_type, const int32_t *cnt,
                             const int32_t *off, int32_t *anc_pos, int8_t *anc_type, int32_t *anc_chunk);
 void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impute);           // k_sets<fill, impute, sa.mt.n > 0>
@@ -175,6 +196,10 @@ void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impu
 int nc_pipe_scan_i32(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int32_t *out);
 int nc_pipe_scan_twb(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int64_t *out, int32_t *total_mbox);      // of tw_blocks(in[i]); the total also as a row mailbox
 int nc_pipe_scan_pos(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int64_t *out, long long *base_io);      // of max(in[i], 0), from *base_io, which it advances
+// nc_pipe_listed.hip
+void nc_pipe_launch_listed(hipStream_t st, const ListedArgs &la);
+void nc_pipe_launch_src_sites(hipStream_t st, int n_chunks, const PipeChunk *pc, const int32_t *seg_src, const int32_t *cnt, const int32_t *off,
+                              const int32_t *kept, const int32_t *site_of, int32_t *site_src);
 // nc_pipe_windows.hip
 enum { NC_WIN_16 = 0, NC_WIN_FORCE16 = 1, NC_WIN_SERIAL = 2 };      // the 16-lane kernel; ... with every window on its serial route; one lane per window
 void nc_pipe_launch_windows(hipStream_t st, const WinArgs &wa, int mode);

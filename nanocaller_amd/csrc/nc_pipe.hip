@@ -1,5 +1,6 @@
 // Device-resident indel featuriser, the host side: nc_pipe_state and the nc_indel_sites_* entry points (the kernels and what the units share: nc_pipe.h).
-//   plan   K7 (nc_indel.hip) -> anchors (k_impute_flags, k_pick, k_flatten) -> sites, read sets and their alignments (k_sets, twice: count, fill)
+//   plan   K7 (nc_indel.hip) -> anchors (k_impute_flags, k_pick, k_flatten) -> sites, read sets and their alignments (k_sets, twice: count, fill);
+//          with a list of columns to genotype (nc_indel_set_sites): k_listed behind K7, k_pick_listed for k_pick, k_src_sites behind the fill
 //   run    per group of sites (bounded by the traceback workspace), two groups in flight (PipeRun):
 //          stage_a   stream A: k_windows16 + k_window_lists, then k_fill_band<1|2> (band off: k_fill16q)
 //          stage_b1  stream B: k_trace_band12, the redo list on the full matrix (k_fill16q, k_end_cells, k_trace16p), k_site_tensor, the scan of the
@@ -28,6 +29,8 @@ struct nc_pipe_state {
     size_t al0_cap = 0;
     DevBuf pc, seg_pos, seg_type, cnt, off, anc_pos, anc_type, anc_chunk, kept, nuniq, site_of, al_of;
     DevBuf site_pos, site_chunk, site_type, site_phase, site_al0, site_nr, site_n2, al_read, al_site, al_member, al_ev;
+    DevBuf seg_src, site_src;               // (a list of columns was set: nc_indel_set_sites) the forced column behind every anchor / site
+    bool listed = false;                    // the last plan ran with a list
     bool have_al_ev = false;
     struct GroupBufs {
         DevBuf win, n1, tw, hlast, hcol, endc, trace, cns, ncns, arow, alt_off;
@@ -94,6 +97,10 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     s->window_after = window_after; s->maxcov = maxcov; s->mincov = prm->mincov; s->win_size = prm->win_size; s->haploid = prm->haploid ? 1 : 0;
     s->S = prm->haploid ? 1 : 3;
     s->n_chunks = n_chunks; s->n_sites = 0; s->n_al = 0; s->n_anchor = 0;
+    // a list of columns to genotype (nc_indel_set_sites): k_listed between K7 and k_impute_flags, k_pick in its listed form.  Without one every
+    // launch below is the one it was
+    const bool listed = ctx->n_isites > 0 || ctx->isites_only;
+    s->listed = listed;
     *n_sites = 0;
     *n_alignments = 0;
     for (auto &m : s->stage_ms) m = 0;
@@ -127,6 +134,7 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     NC_TRY(nc_ensure(ctx, s->pc, (size_t)n_chunks * sizeof(PipeChunk)));
     NC_TRY(nc_ensure(ctx, s->seg_pos, (size_t)seg_total * 4));
     NC_TRY(nc_ensure(ctx, s->seg_type, (size_t)seg_total));
+    if (listed) NC_TRY(nc_ensure(ctx, s->seg_src, (size_t)seg_total * 4));
     NC_TRY(nc_ensure(ctx, s->cnt, ((size_t)n_chunks + 1) * 4));
     NC_TRY(nc_ensure(ctx, s->off, ((size_t)n_chunks + 2) * 4));
     NC_TRY(nc_ensure(ctx, s->misc, 256));
@@ -147,11 +155,43 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
         const int8_t *ctype = k7.ctype;
         for (int32_t k = 0; k < used; k++) pcs[(size_t)(c0 + k)].coloff = k7.ck[(size_t)k].coloff;
         NC_TRY(nc_h2d_pieces(ctx, (PipeChunk *)s->pc.p + c0, pcs.data() + c0, (size_t)used * sizeof(PipeChunk), ctx->stream));
+        if (listed) {
+            // only mode: K7 ran for its per-entry tables (k_sets reads them), its verdicts are reset: the list is the only source of candidates
+            if (ctx->isites_only && used > 0) {
+                const PipeChunk &last = pcs[(size_t)(c0 + used - 1)];
+                NC_HIP(ctx, hipMemsetAsync(const_cast<int8_t *>(ctype), 0xff, (size_t)(last.coloff + last.ncol), ctx->stream));
+            }
+            ListedArgs la;
+            memset(&la, 0, sizeof la);
+            la.pos = ctx->isite_pos; la.is_long = ctx->isite_long; la.n_sites = ctx->n_isites;
+            la.pc = (const PipeChunk *)s->pc.p + c0; la.n_chunks = used; la.ctype = const_cast<int8_t *>(ctype);
+            la.tile_off = pack->tile_off; la.tile_ent = pack->tile_ent; la.tile_pos0 = pack->tile_pos0; la.tile_size = pack->tile_size; la.n_tiles = pack->n_tiles;
+            la.codes = pack->codes; la.excl = excl_dev; la.mincov = prm->mincov; la.haploid = prm->haploid ? 1 : 0; la.impute = impute ? 1 : 0;
+            la.mt = mates;
+            nc_pipe_launch_listed(ctx->stream, la);
+            // NC_PIPE_DUMP (debugging aid): <dump>.col_type = the group's col_type behind k_listed with up to 64 bytes of K7's workspace on
+            // either side (what lies around the bytes the kernel may write), groups appended
+            if (const char *dump = getenv("NC_PIPE_DUMP")) {
+                const PipeChunk &last = pcs[(size_t)(c0 + used - 1)];
+                const char *base = (const char *)ctx->k7.ws.p, *ct = (const char *)ctype;
+                const char *a = std::max(base, ct - 64), *b = std::min(base + ctx->k7.ws.cap, ct + last.coloff + last.ncol + 64);
+                std::vector<char> h((size_t)(b - a));
+                NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                NC_HIP(ctx, hipMemcpy(h.data(), a, h.size(), hipMemcpyDeviceToHost));
+                char path[512];
+                snprintf(path, sizeof path, "%s.col_type", dump);
+                if (FILE *fp = fopen(path, c0 == 0 ? "wb" : "ab")) { fwrite(h.data(), 1, h.size(), fp); fclose(fp); }
+            }
+        }
         if (impute) {                                                 // the read grouping of every col_type-2 column: 3 (an anchor) or -1
             int32_t maxcol = 1;
             for (int32_t k = 0; k < used; k++) maxcol = std::max(maxcol, pcs[(size_t)(c0 + k)].ncol);
             nc_pipe_launch_impute_flags(ctx->stream, used, maxcol, (const PipeChunk *)s->pc.p + c0, const_cast<int8_t *>(ctype), imp, err);
         }
+        if (listed)
+            nc_pipe_launch_pick_listed(ctx->stream, used, (const PipeChunk *)s->pc.p + c0, ctype, prm->win_size, (int32_t *)s->seg_pos.p,
+                                       (int8_t *)s->seg_type.p, (int32_t *)s->seg_src.p, (int32_t *)s->cnt.p, err);
+        else
         nc_pipe_launch_pick(ctx->stream, used, (const PipeChunk *)s->pc.p + c0, ctype, prm->win_size, (int32_t *)s->seg_pos.p, (int8_t *)s->seg_type.p,
                             (int32_t *)s->cnt.p, err);
         NC_HIP(ctx, hipGetLastError());
@@ -236,6 +276,11 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
         sa.al_ev = (int2 *)s->al_ev.p;
     }
     nc_pipe_launch_sets(ctx->stream, sa, true, impute);
+    if (listed) {
+        NC_TRY(nc_ensure(ctx, s->site_src, NS * 4));
+        nc_pipe_launch_src_sites(ctx->stream, n_chunks, (const PipeChunk *)s->pc.p, (const int32_t *)s->seg_src.p, (const int32_t *)s->cnt.p,
+                                 (const int32_t *)s->off.p, (const int32_t *)s->kept.p, (const int32_t *)s->site_of.p, (int32_t *)s->site_src.p);
+    }
     NC_HIP(ctx, hipGetLastError());
     NC_TRY(nc_h2d_small(ctx, (int32_t *)s->site_al0.p + ns, &nal, 4, ctx->stream));
     if (s->al0_cap < NS + 1) {
@@ -265,6 +310,33 @@ extern "C" int nc_indel_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d
     ctx->n_imates = n_mates;
     ctx->imate_key = n_mates ? d_mate_key : nullptr;
     ctx->imate_rec = n_mates ? d_mate_rec : nullptr;
+    return NC_OK;
+}
+
+extern "C" int nc_indel_set_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, const uint8_t *d_long, int32_t only)
+{
+    if (!ctx) return NC_ERR_ARG;
+    if (n_sites < 0 || (n_sites > 0 && !d_pos)) return nc_fail(ctx, NC_ERR_ARG, "nc_indel_set_sites: bad argument");
+    ctx->n_isites = n_sites;
+    ctx->isite_pos = n_sites ? d_pos : nullptr;
+    ctx->isite_long = n_sites ? d_long : nullptr;
+    ctx->isites_only = only != 0;                                     // (n_sites = 0 with only: a list that names nothing here -- no candidates)
+    return NC_OK;
+}
+
+extern "C" int nc_indel_sites_fetch_src(nc_ctx *ctx, int32_t *src_col)
+{
+    if (!ctx) return NC_ERR_ARG;
+    nc_pipe_state *s = ctx->pipe;
+    if (!s || !s->planned) return nc_fail(ctx, NC_ERR_STATE, "nc_indel_sites_fetch_src: nc_indel_sites_plan first");
+    if (s->n_sites == 0) return NC_OK;
+    if (!src_col) return nc_fail(ctx, NC_ERR_ARG, "nc_indel_sites_fetch_src: null buffer");
+    if (!s->listed) {                                                 // a plan without a list: every anchor is a natural one
+        for (int32_t k = 0; k < s->n_sites; k++) src_col[k] = 0;
+        return NC_OK;
+    }
+    NC_HIP(ctx, hipMemcpyAsync(src_col, s->site_src.p, (size_t)s->n_sites * 4, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NC_OK;
 }
 

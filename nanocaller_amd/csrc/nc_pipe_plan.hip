@@ -150,11 +150,19 @@ __global__ __launch_bounds__(256) void k_impute_flags(const PipeChunk *__restric
     }
 }
 
-__global__ __launch_bounds__(64) void k_pick(const PipeChunk *__restrict__ pc, const int8_t *__restrict__ ctype, int32_t win,
-                                             int32_t *__restrict__ seg_pos, int8_t *__restrict__ seg_type, int32_t *__restrict__ cnt,
-                                             int32_t *__restrict__ err)
+// LISTED (a list of columns is set, nc_indel_set_sites): col_type also holds 4 / 5, a listed column forced as a long- / small-window candidate
+// (k_listed); such a column acts as a 0 / 1 and the anchor it writes or overwrites remembers it (seg_src; a later natural column that overwrites
+// the anchor's type leaves it, as extra_variants stays).  Without a list the kernel is the one it was: the plain form has no seg_src argument.
+// The source costs no LDS (a second array took k_pick from three workgroups a CU to two: two rounds for a chr20-sized contig's 645 chunks): it is
+// anchor + win or anchor + 10 by the forced column's class, so the anchor's word carries two more bits (6: a forced column wrote it, 7: of the long
+// class; stripped from seg_type) -- except where the anchor was clipped to 1, and a chunk has one such anchor: its source is a register (src1).
+template <bool LISTED>
+__device__ __forceinline__ void pick_body(const PipeChunk *__restrict__ pc, const int8_t *__restrict__ ctype, int32_t win,
+                                          int32_t *__restrict__ seg_pos, int8_t *__restrict__ seg_type, int32_t *__restrict__ seg_src,
+                                          int32_t *__restrict__ cnt, int32_t *__restrict__ err)
 {
     __shared__ uint32_t anc[PICK_CAP];                               // (anchor - aoff) << 8 | type: 4 bytes an anchor (5 in two arrays held two waves per CU)
+    int32_t src1 = 0;                                                // (LISTED) the forced column that last wrote anchor 1
     const PipeChunk c = pc[blockIdx.x];
     const int32_t aoff = c.lo - win - 16;                            // an anchor is >= max(1, column - win)
     auto apos = [&](int i) { return (int32_t)(anc[i] >> 8) + aoff; };
@@ -189,7 +197,7 @@ __global__ __launch_bounds__(64) void k_pick(const PipeChunk *__restrict__ pc, c
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const uint32_t t = (w[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-                m16 |= ((t <= 1u || t == 3u) ? 1u : 0u) << k;                 // (3: an imputed column, k_impute_flags)
+                m16 |= ((t <= 1u || t == 3u || (LISTED && (t == 4u || t == 5u))) ? 1u : 0u) << k;      // (3: an imputed column, k_impute_flags; 4, 5: k_listed)
             }
             {
                 const int64_t sh = skip_to - col0;                    // (a skip that reaches into this step)
@@ -203,8 +211,10 @@ __global__ __launch_bounds__(64) void k_pick(const PipeChunk *__restrict__ pc, c
                 const uint32_t mm = (uint32_t)__shfl((int)m16, l);
                 const int bq = __ffs((int)mm) - 1;
                 const int32_t v = c.lo + bb + 16 * l + bq;
-                const int tc = (int)((__shfl((int)w[0], l) * (bq < 4) + __shfl((int)w[1], l) * (bq >= 4 && bq < 8) + __shfl((int)w[2], l) * (bq >= 8 && bq < 12) +
-                                      __shfl((int)w[3], l) * (bq >= 12)) >> ((bq & 3) * 8)) & 0xff;
+                const int tc0 = (int)((__shfl((int)w[0], l) * (bq < 4) + __shfl((int)w[1], l) * (bq >= 4 && bq < 8) + __shfl((int)w[2], l) * (bq >= 8 && bq < 12) +
+                                       __shfl((int)w[3], l) * (bq >= 12)) >> ((bq & 3) * 8)) & 0xff;
+                const bool forced = LISTED && tc0 >= 4;
+                const int tc = forced ? tc0 - 4 : tc0;
                 const int32_t prev = tc == 0 ? v + win : v + 10;                     // :267, :273, :301
                 const int32_t an = tc == 0 ? max(1, v - win) : max(1, v - 10);       // :268, :274, :302
                 const int tb = tc == 3 ? (1 | 2 | ((v - an) << 2)) : tc;             // imputed: the small-window type + where its read sets come from
@@ -215,18 +225,20 @@ __global__ __launch_bounds__(64) void k_pick(const PipeChunk *__restrict__ pc, c
                 if (i > 0 && apos(i - 1) == an) {
                     // variants[an] is overwritten; extra_variants[an] (an imputed column's read sets) stays unless an imputed column writes it again
                     if (lane == 0) {
-                        const int old = (int)(anc[i - 1] & 0xffu);
-                        anc[i - 1] = apack(an, ((tb & 2) || !(old & 2)) ? tb : ((old & ~1) | tb));
+                        const int oldw = (int)(anc[i - 1] & 0xffu), old = LISTED ? (oldw & 0x3f) : oldw;
+                        const int nt = ((tb & 2) || !(old & 2)) ? tb : ((old & ~1) | tb);
+                        anc[i - 1] = apack(an, LISTED ? (nt | (forced ? (0x40 | (tc0 == 4 ? 0x80 : 0)) : (oldw & 0xc0))) : nt);
                     }
                 } else if (n >= PICK_CAP) {
                     over = true;
                 } else {
                     if (lane == 0) {
                         for (int k = n; k > i; k--) anc[k] = anc[k - 1];
-                        anc[i] = apack(an, tb);
+                        anc[i] = apack(an, forced ? (tb | 0x40 | (tc0 == 4 ? 0x80 : 0)) : tb);
                     }
                     n++;
                 }
+                if (forced && an == 1) src1 = v;
                 __syncthreads();
                 // every column up to `prev` is skipped by `if v_pos <= prev: continue` (:249)
                 skip_to = (int64_t)prev - c.lo + 1;
@@ -253,11 +265,26 @@ __global__ __launch_bounds__(64) void k_pick(const PipeChunk *__restrict__ pc, c
         if (ok) {
             const int w = m + __popcll(bm & ((1ull << lane) - 1));
             seg_pos[c.seg0 + w] = apos(k);
-            seg_type[c.seg0 + w] = (int8_t)(anc[k] & 0xffu);
+            const uint32_t tw = anc[k] & 0xffu;
+            seg_type[c.seg0 + w] = (int8_t)(LISTED ? (tw & 0x3fu) : tw);
+            if (LISTED) seg_src[c.seg0 + w] = !(tw & 0x40u) ? 0 : apos(k) == 1 ? src1 : apos(k) + ((tw & 0x80u) ? win : 10);
         }
         m += __popcll(bm);
     }
     if (lane == 0) cnt[c.id] = m;
+}
+
+__global__ __launch_bounds__(64) void k_pick(const PipeChunk *__restrict__ pc, const int8_t *__restrict__ ctype, int32_t win,
+                                             int32_t *__restrict__ seg_pos, int8_t *__restrict__ seg_type, int32_t *__restrict__ cnt,
+                                             int32_t *__restrict__ err)
+{
+    pick_body<false>(pc, ctype, win, seg_pos, seg_type, nullptr, cnt, err);
+}
+__global__ __launch_bounds__(64) void k_pick_listed(const PipeChunk *__restrict__ pc, const int8_t *__restrict__ ctype, int32_t win,
+                                                    int32_t *__restrict__ seg_pos, int8_t *__restrict__ seg_type, int32_t *__restrict__ seg_src,
+                                                    int32_t *__restrict__ cnt, int32_t *__restrict__ err)
+{
+    pick_body<true>(pc, ctype, win, seg_pos, seg_type, seg_src, cnt, err);
 }
 
 __device__ __forceinline__ int block_scan(int v, int *wsum, int &tot)
@@ -544,6 +571,11 @@ void nc_pipe_launch_impute_flags(hipStream_t st, int n_chunks, int maxcol, const
 void nc_pipe_launch_pick(hipStream_t st, int n_chunks, const PipeChunk *pc, const int8_t *ctype, int32_t win, int32_t *seg_pos, int8_t *seg_type, int32_t *cnt, int32_t *err)
 {
     hipLaunchKernelGGL(k_pick, dim3(n_chunks), dim3(64), 0, st, pc, ctype, win, seg_pos, seg_type, cnt, err);
+}
+void nc_pipe_launch_pick_listed(hipStream_t st, int n_chunks, const PipeChunk *pc, const int8_t *ctype, int32_t win, int32_t *seg_pos, int8_t *seg_type,
+                                int32_t *seg_src, int32_t *cnt, int32_t *err)
+{
+    hipLaunchKernelGGL(k_pick_listed, dim3(n_chunks), dim3(64), 0, st, pc, ctype, win, seg_pos, seg_type, seg_src, cnt, err);
 }
 void nc_pipe_launch_flatten(hipStream_t st, int n_chunks, const PipeChunk *pc, const int32_t *seg_pos, const int8_t *seg_type, const int32_t *cnt,
                             const int32_t *off, int32_t *anc_pos, int8_t *anc_type, int32_t *anc_chunk)

@@ -332,6 +332,7 @@ def get_indel_testing_candidates(dct, chunk, aligner=None, device=0):
     """generate_indel_pileups.py:128-371 for a BAM `chunk['sam_path']` with HP/PS tags:
     -> (pos, x0, x1, x2, alleles, phase); pass 1 on the GPU (nc_indel_scan), pass 2 through the native reader."""
     from .bam import BamFile, read_fasta
+    _no_list_on_host(dct, [chunk])                                  # (the per-chunk route does not serve dct['genotype_indel_sites'])
     chrom, start, end = chunk["chrom"], chunk["start"], chunk["end"]
     window_before, window_after = 0, window_after_of(dct)
     extra_variants = {}
@@ -527,6 +528,7 @@ def plan_routes(dct, chunks, haploid, route=None, mask=None, device=0):
     order = sorted(every, key=lambda k: (chunks[k]["start"], chunks[k]["end"]))
     ends = [chunks[k]["end"] for k in order]
     if route == "host" or not isinstance(chunks[0]["sam_path"], str) or any(b < a for a, b in zip(ends, ends[1:])):
+        _no_list_on_host(dct, chunks)
         return [("host", every, dct)]
     if route == "split" and dct.get("impute_indel_phase") and not haploid:
         if mask is None:
@@ -534,10 +536,22 @@ def plan_routes(dct, chunks, haploid, route=None, mask=None, device=0):
             for k, m in zip(order, imputed_chunk_mask(dct, [chunks[k] for k in order], device)):
                 mask[k] = m
         dev, host = [k for k in every if not mask[k]], [k for k in every if mask[k]]
+        if host:
+            _no_list_on_host(dct, chunks)
         if not dev:
             return [("host", every, dct)]
         return [("device", dev, dict(dct, impute_indel_phase=False))] + ([("host", host, dct)] if host else [])
     return [("device", every, dct)]
+
+
+def _no_list_on_host(dct, chunks):
+    """dct['genotype_indel_sites'] is served by the device pipeline only (nc_indel_set_sites): a part on the host-assembled route raises, it does
+    not ignore the list"""
+    from .genotype_sites import indel_list_given
+    if indel_list_given(dct):
+        raise ValueError("genotype_indel_sites: the list of indel sites is served by the device indel pipeline only; these chunks take the "
+                         "host-assembled or the per-chunk route (no BAM path, nested chunks, route='host', a capacity limit of the device pipeline, "
+                         "or an external aligner: MUSCLE on PATH / aligner=)")
 
 
 def get_indel_testing_candidates_batch(dct, chunks, device=0, haploid=False, device_x=False, route=None, dedup=True):
@@ -586,6 +600,7 @@ def _indel_batch(dct, chunks, device, haploid, device_x, route=None, dedup=True)
         part = [chunks[k] for k in idx]
         tuples = device_part(_indel_batch_device, d, part, device, haploid, device_x) if kind == "device" else None
         if tuples is None:
+            _no_list_on_host(d, part)
             tuples = _indel_batch_host(d, part, device, haploid, device_x, dedup)
         for k, t in zip(idx, tuples):
             out[k] = t
@@ -603,10 +618,23 @@ def indel_sites_for_chunks(dct, chunks, device, haploid, fetch=True):
     # that combination keeps the refusal
     by_name = haploid or not dct.get("impute_indel_phase")
     eng, dp, reads_c, ctg, excl, mates = indel_pack_for(dct, chunks, device, by_name=by_name)
-    r = indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), [(chunks[k]["start"], chunks[k]["end"]) for k in order], mincov=dct["mincov"],
+    # dct['genotype_indel_sites']: the columns listed for this contig become candidates under the scan's depth test (None: no list, nothing changes)
+    from .genotype_sites import indel_sites_for
+    sites, sites_long, sites_only = indel_sites_for(dct, chunks[0]["chrom"])
+    spans = [(chunks[k]["start"], chunks[k]["end"]) for k in order]
+    kw = dict(sites=sites, sites_long=sites_long, sites_only=sites_only) if sites is not None else {}
+    r = indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), spans, mincov=dct["mincov"],
                            maxcov=dct["maxcov"], win_size=dct["win_size"], small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"],
                            window_after=window_after_of(dct), haploid=haploid, excl=excl, fetch=fetch, impute=bool(dct.get("impute_indel_phase")),
-                           mates=mates)
+                           mates=mates, **kw)
+    if sites is not None:
+        inside = np.zeros(sites.size, bool)
+        for a, b in spans:
+            inside[np.searchsorted(sites, a, "left"):np.searchsorted(sites, b, "right")] = True
+        r["genotype_listed"] = int(inside.sum())
+        # listed columns that made an anchor that went through pass 2; those with a record or a reference-call line: sites_to_vcf_text
+        r["genotype_anchored"] = int(np.unique(r["src"][r["src"] > 0]).size) if "src" in r else None
+        r["genotype_recorded"] = None
     return r, ctg, order
 
 
@@ -623,16 +651,25 @@ def _indel_batch_device(dct, chunks, device, haploid, device_x):
     return _by_chunk(order, sites_to_tuples(r, len(chunks), ctg["fasta"], haploid, device_x))
 
 
-def indel_chunks_vcf_text(dct, chunks, device, haploid, model_kind):
+def indel_chunks_vcf_text(dct, chunks, device, haploid, model_kind, counts=None):
     """candidates -> tensors -> Indel_model -> genotype rules -> VCF record text for chunks of one BAM and contig, without a
     Python object per site: nc_indel_sites_* (device), nc_indel_forward (K9), nc_indel_vcf_format (native host rules).
-    -> list of bytes, the records of every chunk (what indelCaller.indel_run writes chunk by chunk)"""
+    -> list of bytes, the records of every chunk (what indelCaller.indel_run writes chunk by chunk).  counts (a dict, filled): with
+    dct['genotype_indel_sites'] the run's genotype_listed / _anchored / _recorded / _inside, its sites' pos / chunk / src and probabilities"""
     r, ctg, order = indel_sites_for_chunks(dct, chunks, device, haploid)
     if r["n"] == 0:
-        return [b""] * len(chunks)
-    eng = get_engine(device)
-    probs = eng.indel_forward(model_kind, r.pop("x")).cpu().numpy()
-    return _by_chunk(order, sites_to_vcf_text(eng, r, probs, chunks[0]["chrom"], len(chunks), ctg, haploid))
+        texts = [b""] * len(chunks)
+        if "genotype_listed" in r:
+            r["genotype_recorded"] = 0
+    else:
+        eng = get_engine(device)
+        probs = eng.indel_forward(model_kind, r.pop("x")).cpu().numpy()
+        texts = _by_chunk(order, sites_to_vcf_text(eng, r, probs, chunks[0]["chrom"], len(chunks), ctg, haploid))
+        if counts is not None:
+            counts["probs"] = probs
+    if counts is not None:
+        counts.update({k: v for k, v in r.items() if k.startswith("genotype_") or k in ("pos", "chunk", "src")}, order=order)
+    return texts
 
 
 def _indel_batch_host(dct, chunks, device, haploid, device_x, dedup=True):

@@ -16,6 +16,8 @@ from .generate_indel_pileups import (_pass2_native, allele_prediction, decoded_c
 def get_indel_testing_candidates_haploid(dct, chunk, aligner=None, device=0):
     """generate_indel_pileups_haploid.py:128-277 -> (pos, x, alleles): one read set per anchor, no HP split."""
     from .bam import BamFile, read_fasta
+    from .generate_indel_pileups import _no_list_on_host
+    _no_list_on_host(dct, [chunk])                                  # (the per-chunk route does not serve dct['genotype_indel_sites'])
     chrom, start, end = chunk["chrom"], chunk["start"], chunk["end"]
     window_before, window_after = 0, window_after_of(dct)
     variants = scan_indel_candidates(dct, chunk, device, haploid=True)

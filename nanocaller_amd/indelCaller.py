@@ -119,6 +119,24 @@ INDEL_VCF_HEADER = (                                                 # indelCall
     '#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{sample}\n')
 
 
+# with a list of indel sites to genotype (params['genotype_indel_sites']) a listed column may end as a reference call or a call without an
+# allele (indel_device.sites_to_vcf_text): the two filters of those lines, worded as the SNP header words them
+INDEL_GENOTYPE_FILTERS = (
+    '##FILTER=<ID=LOW,Description="All alleles have probability less than 50%.">\n'
+    '##FILTER=<ID=REF,Description="Homozygous Reference. Only reference allele has greater than 50% probability. '
+    'All alternative alleles having probability less than 50%.">\n')
+
+
+def indel_vcf_header(params, contigs):
+    """INDEL_VCF_HEADER for `contigs`; with a list of indel sites to genotype also the REF and LOW filters"""
+    from .genotype_sites import indel_list_given
+    h = INDEL_VCF_HEADER.format(contigs=''.join('##contig=<ID=%s>\n' % c for c in contigs), sample=params['sample'])
+    if not indel_list_given(params):
+        return h
+    mark = '##FILTER=<ID=PASS,Description="All filters passed">\n'
+    return h.replace(mark, mark + INDEL_GENOTYPE_FILTERS, 1)
+
+
 def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, worker_id=1, aligner=None, route=None, rules="native"):
     """Worker with the reference's signature (indelCaller.py:41-189): drains ('indel', chunk) jobs from `job_Q`, writes
     <intermediate_indel_files_dir>/<prefix>.<worker>.indel.vcf.  Per chunk: candidates + tensors + allele strings
@@ -127,7 +145,9 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
     then the genotype rules in batches of 100 with `prev` carried through the chunk.
     Without an external aligner, route= is generate_indel_pileups.plan_routes' (None, "host", "split") and rules= says who applies the genotype
     rules to the device pipeline's sites: "native" (nc_indel_vcf_format, no Python object per site) or "python" (the per-chunk tuples and
-    indel_vcf_lines[_haploid], which the host-assembled route always takes): the same file every way."""
+    indel_vcf_lines[_haploid], which the host-assembled route always takes): the same file every way.
+    params['genotype_indel_sites'] (a list of indel sites to genotype) is served by the device pipeline with the native rules
+    only: with an external aligner (MUSCLE on PATH, aligner=), rules="python" or a host part of the route plan the call raises ValueError."""
     import os
     import queue
     import sys
@@ -144,6 +164,14 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
     from .weights import Weights
     if route not in ROUTES or rules not in ("native", "python"):
         raise ValueError("indel_run(route=%r, rules=%r): route is one of %r, rules 'native' or 'python'" % (route, rules, ROUTES))
+    native = aligner in (None, "device") and (aligner == "device" or default_aligner() is star_aligner)
+    # params['genotype_indel_sites'] is served by the device pipeline with the native rules only: every other way through this function raises
+    # before anything is written, it does not ignore the list (an external aligner -- MUSCLE on PATH, aligner= -- takes the per-chunk functions;
+    # the Python rules write no REF / LOW line)
+    from .genotype_sites import indel_list_given
+    if indel_list_given(params) and (not native or rules != "native"):
+        raise ValueError("genotype_indel_sites: the list of indel sites is served by the device indel pipeline with the native rules only "
+                         "(this run: %s)" % ("an external aligner, the per-chunk route" if not native else "rules=%r" % rules))
     curr_vcf_path = os.path.join(params['intermediate_indel_files_dir'], '%s.%d.indel.vcf' % (params['prefix'], worker_id))
     indel_files_list.append(curr_vcf_path)
     model_path = get_indel_model(params['indel_model'])
@@ -202,7 +230,7 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
                 out += lines
         write_chunk(f, ''.join(out))
 
-    native = aligner in (None, "device") and (aligner == "device" or default_aligner() is star_aligner)
+    tally = {}                                                       # contig -> [listed, anchored, recorded, inside the previous record]
     with open(curr_vcf_path, 'w') as f:
         while len(indel_dict) > 0 or not job_Q.empty():
             jobs = []
@@ -240,8 +268,13 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
                     part = [group[i] for i in idx]
                     texts, on_host = None, kind == "host"
                     if kind == "device" and rules == "native":
-                        texts = device_part(indel_chunks_vcf_text, dct, part, device, hap, _lib.MODEL_INDEL_HAP if hap else _lib.MODEL_INDEL)
+                        counts = {}
+                        texts = device_part(indel_chunks_vcf_text, dct, part, device, hap, _lib.MODEL_INDEL_HAP if hap else _lib.MODEL_INDEL, counts)
                         on_host = texts is None                      # (not on the device a second time)
+                        if counts.get("genotype_listed") is not None:
+                            t = tally.setdefault(chrom, [0, 0, 0, 0])
+                            for i, key in enumerate(("genotype_listed", "genotype_anchored", "genotype_recorded", "genotype_inside")):
+                                t[i] += counts.get(key) or 0
                     if texts is None:
                         tuples = get_indel_testing_candidates_batch(dct, part, device=device, haploid=hap, device_x=True, route="host" if on_host else None)
                         probs = forward(ploidy, tuples)
@@ -253,6 +286,11 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
                         write_chunk(f, r.decode("ascii"))
                     else:
                         emit(f, jobs[k][1], *r)
+    if not params.get('suppress_progress'):
+        # params['genotype_indel_sites'], per contig: what was listed in this worker's chunks and got neither an anchor nor a record
+        for chrom, (n_listed, n_anchored, n_recorded, n_inside) in tally.items():
+            print('%s: %d indel sites listed, %d got neither an anchor nor a record (%d with a record or a REF / LOW line, %d inside the previous '
+                  'record)' % (chrom, n_listed, n_listed - n_anchored, n_recorded, n_inside), flush=True)
     return curr_vcf_path
 
 
@@ -383,9 +421,10 @@ def caller(params, job_Q, counter_Q, indel_dict, phased_snp_files_list, indel_fi
 
 
 def _non_snp(line):
-    """rtg vcffilter --non-snps-only (:391): keep a record unless every ALT allele has the length of REF"""
+    """rtg vcffilter --non-snps-only (:391): keep a record unless every ALT allele has the length of REF.  A line without an ALT allele ('.': the
+    reference call or the call without an allele at a listed indel site, written only with params['genotype_indel_sites']) is no SNP and stays."""
     f = line.split('\t', 5)
-    return any(len(a) != len(f[3]) for a in f[4].split(','))
+    return f[4] == '.' or any(len(a) != len(f[3]) for a in f[4].split(','))
 
 
 def call_manager(params, devices=None, aligner=None):
@@ -485,7 +524,7 @@ def call_manager(params, devices=None, aligner=None):
         vcfio.write_sorted_vcf(output_files['snps'], snp_hdr, snp_recs, contigs)
     indel_recs = []
     if output_files['indels']:
-        header = INDEL_VCF_HEADER.format(contigs=''.join('##contig=<ID=%s>\n' % c for c in contigs), sample=params['sample'])
+        header = indel_vcf_header(params, contigs)
         raw_indel_vcf = os.path.join(params['intermediate_indel_files_dir'], '%s.raw.indel.vcf' % params['prefix'])
         files = [os.path.join(params['intermediate_indel_files_dir'], '%s.%d.indel.vcf' % (params['prefix'], r + 1)) for r in range(world)]
         with open(raw_indel_vcf, 'w') as outfile:                              # :370-388

@@ -88,12 +88,15 @@ def device_indel_reads(ctg, flag, dp, device):
 
 
 def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, win_size, small_win_size, ins_t, del_t, window_after,
-                       haploid=False, excl=None, fetch=True, impute=False, mates=None, scoring=None):
+                       haploid=False, excl=None, fetch=True, impute=False, mates=None, scoring=None, sites=None, sites_long=None, sites_only=False):
     """nc_indel_sites_plan + _run (+ _fetch) for a list of (start, end) chunks of one contig -> dict: n, x (device float32
     [n, sets * 5, 128, 2]: the CNN input), and with fetch: pos / chunk / type / phase int32 [n], ref_len / alt_len int32 [n, sets],
     alt (uint8 codes, the ALT prefixes back to back in (site, set) order).  mates: indel_mate_table's (key, rec) when kept alignments share read
     names.  scoring: the star alignment's (gap open, gap extend, match, mismatch), default _lib.STAR_SCORING; nc_indel_sites_scoring refuses values
-    the 16-bit aligners do not cover.  Raises NanoCallerHipError with .status."""
+    the 16-bit aligners do not cover.  sites: indel columns to genotype (1-based, an array or an int32 device tensor; None: no list, every launch is
+    the plain one), sites_long: their class (nonzero = long window; None: all small), sites_only: the list is the only source of candidates
+    (nc_indel_set_sites); the fetched dict then also holds src, the listed column behind every site (0: none).  Raises NanoCallerHipError with
+    .status."""
     L, check = eng.L, eng._check
     prm = _lib.IndelScanParamsC(mincov=int(mincov), win_size=int(win_size), small_win_size=int(small_win_size), ins_t=float(ins_t),
                                 del_t=float(del_t), haploid=1 if haploid else 0, impute=1 if (impute and not haploid) else 0)
@@ -101,13 +104,29 @@ def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, w
     ends = np.ascontiguousarray([c[1] for c in chunks], np.int32)
     pc = dp.c_struct()
     n, na = C.c_int32(), C.c_int64()
+    S = 1 if haploid else 3
+    # the list is checked and uploaded before the context borrows anything
+    listed = sites is not None
+    t_pos = t_long = None
+    if listed:
+        t_pos = sites if torch.is_tensor(sites) else torch.from_numpy(np.ascontiguousarray(sites, np.int32)).to(eng.device)
+        if sites_long is not None:
+            t_long = sites_long if torch.is_tensor(sites_long) else torch.from_numpy((np.asarray(sites_long) != 0).astype(np.uint8)).to(eng.device)
+            if t_long.numel() != t_pos.numel():
+                raise ValueError("indel_sites_device: %d listed columns with %d class flags" % (t_pos.numel(), t_long.numel()))
+        if t_pos.dtype != torch.int32 or (t_long is not None and t_long.dtype != torch.uint8):
+            raise ValueError("indel_sites_device: listed columns are int32, their classes uint8")
     check(L.nc_indel_sites_scoring(eng.ctx, *[int(v) for v in (_lib.STAR_SCORING if scoring is None else scoring)]), "nc_indel_sites_scoring")
     # alignments that share read names: the plan keys them by name from this table (none: no table, the plain kernels run).  The context borrows
-    # the pointers, so the table is cleared again once the plan's and the run's launches are enqueued, whatever their outcome
-    check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,
-                               C.c_void_p(mates[1].data_ptr()) if mates else None), "nc_indel_set_mates")
-    S = 1 if haploid else 3
+    # the pointers of the table and of the list, so both are cleared again once the plan's and the run's launches are enqueued, whatever their
+    # outcome -- that of the set calls included
     try:
+        check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,
+                                   C.c_void_p(mates[1].data_ptr()) if mates else None), "nc_indel_set_mates")
+        if listed:
+            ns = int(t_pos.numel())
+            check(L.nc_indel_set_sites(eng.ctx, ns, C.c_void_p(t_pos.data_ptr()) if ns else None,
+                                       C.c_void_p(t_long.data_ptr()) if (ns and t_long is not None) else None, 1 if sites_only else 0), "nc_indel_set_sites")
         check(L.nc_indel_sites_plan(eng.ctx, C.byref(pc), C.c_void_p(dp.ref_code.data_ptr()), dp.tile_pos0, dp.ref_code.numel(), int(chrom_len),
                                     C.byref(reads_c), C.c_void_p(excl.data_ptr()) if excl is not None else None, len(chunks), _lib.npp(starts),
                                     _lib.npp(ends), C.byref(prm), int(window_after), int(maxcov), C.byref(n), C.byref(na)), "nc_indel_sites_plan")
@@ -117,13 +136,16 @@ def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, w
     finally:
         if mates:
             L.nc_indel_set_mates(eng.ctx, 0, None, None)
+        if listed:
+            L.nc_indel_set_sites(eng.ctx, 0, None, None, 0)
     out = dict(n=N, sets=S, x=x, n_alignments=na.value)
     if fetch:
-        out.update(indel_sites_fetch(eng, N, S))
+        out.update(indel_sites_fetch(eng, N, S, src=listed))
     return out
 
 
-def indel_sites_fetch(eng, N, S):
+def indel_sites_fetch(eng, N, S, src=False):
+    """nc_indel_sites_fetch (+ _fetch_alt) of the last plan + run; src (a list was set): also the listed column behind every site"""
     L = eng.L
     pos, chunk, typ, phase = (np.empty(max(N, 1), np.int32) for _ in range(4))
     rl, al = np.empty((max(N, 1), S), np.int32), np.empty((max(N, 1), S), np.int32)
@@ -133,7 +155,12 @@ def indel_sites_fetch(eng, N, S):
     alt = np.empty(max(int(nb.value), 1), np.uint8)
     if nb.value:
         eng._check(L.nc_indel_sites_fetch_alt(eng.ctx, _lib.npp(alt), int(nb.value)), "nc_indel_sites_fetch_alt")
-    return dict(pos=pos[:N], chunk=chunk[:N], type=typ[:N], phase=phase[:N], ref_len=rl[:N], alt_len=al[:N], alt=alt[:int(nb.value)])
+    out = dict(pos=pos[:N], chunk=chunk[:N], type=typ[:N], phase=phase[:N], ref_len=rl[:N], alt_len=al[:N], alt=alt[:int(nb.value)])
+    if src:
+        sc = np.zeros(max(N, 1), np.int32)
+        eng._check(L.nc_indel_sites_fetch_src(eng.ctx, _lib.npp(sc)), "nc_indel_sites_fetch_src")
+        out["src"] = sc[:N]
+    return out
 
 
 MATE_RING_CAP = 64           # alignments of one read name that k_hap_depth_b, k_event_tiles and k_sets<.., true> walk (their `guard` loops)
@@ -290,7 +317,60 @@ def sites_to_vcf_text(eng, r, probs, chrom, n_chunks, ctg, haploid):
         raise _lib.NanoCallerHipError("nc_indel_vcf_format failed (%d)" % rc, status=rc)
     raw = buf[:nb.value].tobytes()
     co = coff.tolist()
-    return [raw[a:b] for a, b in zip(co, co[1:])]
+    texts = [raw[a:b] for a, b in zip(co, co[1:])]
+    if "src" in r:
+        texts = _with_reference_calls(r, probs, chrom, texts, ctg, haploid)
+    return texts
+
+
+def reference_call_line(chrom, p, ref_base, prob, haploid):
+    """The line of a listed indel column `p` whose site got no variant record: the model calls reference (diploid prob[0] > 0.95, haploid
+    prob < 0.5: FILTER REF, Q = min(99, -10 log10(1e-6 + the probability of a variant))) or no allele was found (LOW, Q 0.00).  chrom: bytes."""
+    if haploid:
+        pv = float(np.asarray(prob).reshape(-1)[0])
+        is_ref, q = pv < 0.5, pv
+    else:
+        p0 = float(np.asarray(prob).reshape(-1)[0])
+        is_ref, q = p0 > 0.95, 1.0 - p0
+    qv = min(99.0, -10.0 * float(np.log10(1e-6 + q))) if is_ref else 0.0
+    return b"%s\t%d\t.\t%s\t.\t%.2f\t%s\t.\tGT:GQ\t./.:%.2f\n" % (chrom, p, ref_base, qv, b"REF" if is_ref else b"LOW", qv)
+
+
+def _with_reference_calls(r, probs, chrom, texts, ctg, haploid):
+    """nc_indel_vcf_format's text of every chunk + one reference_call_line per site whose anchor a listed column wrote (r['src'] > 0) and that got
+    no record, merged by position.  A forced site the rules skipped by `pos <= prev` lies inside the previous record: no line, counted
+    (r['genotype_inside']).  The lines never move the rules' `prev`: the rules ran before them.  Sets r['genotype_recorded']."""
+    pos, chunk, src = r["pos"].tolist(), r["chunk"].tolist(), r["src"].tolist()
+    fasta_b = ctg["fasta_b"]
+    recorded, inside = set(), 0
+    out = []
+    k = 0
+    for ci, text in enumerate(texts):
+        lines = text.splitlines(keepends=True)
+        rec = {}                                                     # a record's POS -> the `prev` it leaves: POS + its longest allele
+        for ln in lines:
+            f = ln.split(b"\t", 5)
+            rec[int(f[1])] = int(f[1]) + max(len(f[3]), max(len(a) for a in f[4].split(b",")))
+        extra, prev = [], 0
+        while k < len(pos) and chunk[k] == ci:
+            pj, sj = pos[k], src[k]
+            if not pj > prev:
+                inside += sj > 0
+            elif pj in rec:
+                prev = rec[pj]
+                if sj > 0:
+                    recorded.add((ci, sj))
+            elif sj > 0:
+                extra.append((sj, reference_call_line(chrom, sj, fasta_b[sj - 1:sj].upper(), probs[k], haploid)))
+                recorded.add((ci, sj))
+            k += 1
+        if extra:
+            keyed = [(int(ln.split(b"\t", 2)[1]), 0, i, ln) for i, ln in enumerate(lines)] + [(p, 1, i, ln) for i, (p, ln) in enumerate(extra)]
+            text = b"".join(t[3] for t in sorted(keyed))
+        out.append(text)
+    r["genotype_recorded"] = len({s for _, s in recorded})
+    r["genotype_inside"] = inside
+    return out
 
 
 def sites_to_tuples(r, n_chunks, fasta, haploid, device_x):
