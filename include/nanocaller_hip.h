@@ -1004,6 +1004,36 @@ int nc_bamidx_fields(nc_ctx *ctx, const uint8_t *d_raw, int64_t n_rec, const int
                      int32_t n_mem, const int64_t *d_mem_ooff, const int64_t *d_mem_foff, int32_t has_prev, int32_t prev_refid, int32_t prev_pos,
                      int32_t min_shift, int32_t depth, int64_t *d_voff, int32_t *d_fields, int32_t *d_status);
 
+/* Training of the diploid SNP model on the device (csrc/nc_train.hip; nanocaller_amd/train.py): what the reference's
+ * misc/training/model_run.py + model_architect.py do under TensorFlow 1.  The trained function is nc_snp_forward's for NC_MODEL_SNP (the allele
+ * heads feed fc3 as softmax outputs); dropout sits behind fc1's SELU: keep_mask_dev [n][48] bytes (non-zero = kept, kept units are multiplied
+ * by 1 / keep; NULL or keep == 1: no mask).  cost = CE_A + CE_G + CE_T + CE_C + CE_GT + gamma * sum over the 14 kernels of |W|^2 / 2, each CE
+ * the batch mean of a 2-way softmax cross-entropy; label_dev [n][5] bytes = the classes of A, G, T, C, GT.  x_dev float32 [n][5][41][5],
+ * ref_code_dev and scale_dev (may be NULL) as in nc_snp_forward with scale_mode 0.  All state (weights, Adam's m and v) is fp32 in blob order.
+ * Sums over sites run in a fixed order (no atomics): two calls on the same inputs give the same bits.  A trainer belongs to its context,
+ * runs on the context's stream and is freed before it.  Only NC_MODEL_SNP is accepted (NC_ERR_UNSUPPORTED otherwise).
+ *   nc_train_set_weights   canonical host blob (109,370 floats); zeroes m, v and the step count.
+ *   nc_train_forward       probs_dev [n][4] class-1 probabilities of A, G, T, C, gt_dev [n][2] (may be NULL).
+ *   nc_train_loss_grad     loss6_host (may be NULL; waits) = cost, GT, A, G, T, C; grad_dev (may be NULL) = the gradient blob, regulariser
+ *                          included.  n <= max_batch; batches above the workspace's slice are accumulated slice by slice.
+ *   nc_train_adam          one step with the gradient of the last nc_train_loss_grad, in TensorFlow's form: lr_t = lr sqrt(1 - beta2^t) /
+ *                          (1 - beta1^t), m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2, w -= lr_t m / (sqrt(v) + eps).
+ *   nc_train_info          sites per workspace slice, workspace bytes, steps taken (each may be NULL).
+ *   nc_train_stage_ms      on != 0: later nc_train_loss_grad calls record events between their stages; ms7 (may be NULL; read before `on` is
+ *                          applied) = the last call's forward trunk, heads, fc1, conv3, conv2, conv1 gradients, parameter kernels. */
+typedef struct nc_train nc_train;
+int nc_train_create(nc_ctx *ctx, int32_t model_kind, int64_t max_batch, nc_train **out);
+int nc_train_free(nc_train *tr);
+int nc_train_set_weights(nc_train *tr, const float *blob_host, size_t n_floats);
+int nc_train_get_weights(nc_train *tr, float *blob_host, size_t n_floats);
+int nc_train_forward(nc_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                     float keep, float *probs_dev, float *gt_dev);
+int nc_train_loss_grad(nc_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                       float keep, const uint8_t *label_dev, float gamma, float *loss6_host, float *grad_dev);
+int nc_train_adam(nc_train *tr, float lr, float beta1, float beta2, float eps);
+int nc_train_info(nc_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
+int nc_train_stage_ms(nc_train *tr, int32_t on, float *ms7);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,941 @@
+// Training of the diploid SNP model (gfx950): forward with stored activations, backward, TensorFlow-form Adam.  DESIGN.md section 17.
+//
+// The function is the deployed model's (model_architect.py:36-64, what nc_snp_forward computes for NC_MODEL_SNP): the four allele heads feed fc3 as
+// softmax outputs, dropout sits behind fc1's SELU.  Everything is fp32 with fp32 accumulation; v_mfma_f32_16x16x4_f32 is bit for bit an fmaf chain.
+// lane l of an MFMA: A[row l&15][k l>>4], B[k l>>4][col l&15], C/D col l&15, row 4*(l>>4)+r (the lane maps of nc_cnn_fp32.hip).
+//
+//   forward     k_scale_x, k_conv1_fwd, k_conv23_fwd x 2 (k7_conv23_mfma's form), k_fc1_fwd (k3_fc1<48, 1>'s form), k_heads
+//   backward    k_heads (losses -> d fc1, one site per lane), k_small_wgrad (fc1 bias + the layers behind fc1),
+//               k_fc1_wgrad / k_fc1_dgrad, k_conv_wgrad / k_conv_dgrad x 2, k_bias_grad x 2, k_conv1_wgrad (all MFMA but the bias sums)
+//   parameters  k_loss_reduce (the six loss terms), k_params (slab sum + gamma w on kernel entries + Adam step)
+//
+// Sums over sites run in a fixed order: a slab = the gradient of SLAB = 64 consecutive sites in blob order, written by one workgroup per
+// parameter range (the four waves of a workgroup combine through LDS in wave order); k_params adds the slabs in slab order.  No atomics.
+// Sites past n are never read: their operands enter every product as zeros.
+#include "nc_cnn.h"
+
+namespace {
+
+constexpr int SLAB = 64;                                   // sites per slab = 4 MFMA tiles of 16
+constexpr int64_t MAX_SLICE = 4096;                        // sites whose activations the workspace holds at once
+constexpr int NPAR = 109370;
+// canonical blob offsets (weights.LAYER_SPECS[KIND_SNP]: kernel then bias of every layer)
+constexpr int O_K11 = 0, O_B11 = 400, O_K12 = 416, O_B12 = 816, O_K13 = 832, O_B13 = 2832, O_K2 = 2848, O_B2 = 12064, O_K3 = 12096, O_B3 = 24384;
+constexpr int O_KF = 24448, O_BF = 107392, O_FA = 107440, O_FAB = 108208, O_HEAD = 108224, O_FC2 = 108368, O_FC2B = 109136;
+constexpr int O_FC3 = 109152, O_FC3B = 109344, O_GT = 109352, O_GTB = 109368;
+constexpr int N1 = 205 * 48, N2 = 80 * 32, N3 = 27 * 64, XS = 1028;   // floats per site: conv1 - conv3 outputs, the scaled input (padded)
+// per-site record of the layers behind fc1: activations [f1 masked 48 | fa 16 | head logits 8 | head softmax 8 | fc2 16 | fc3 8] ...
+constexpr int TA = 104, TA_FA = 48, TA_Z = 64, TA_P = 72, TA_FC2 = 80, TA_FC3 = 96;
+// ... and gradients at the pre-activations [fa 16 | head logits 8 | fc2 16 | fc3 8 | GT logits 2 | pad 2]
+constexpr int TD = 52, TD_H = 16, TD_FC2 = 24, TD_FC3 = 40, TD_GT = 48;
+
+__device__ __forceinline__ float selud(float y) { return y > 0.0f ? SELU_L : y + SELU_LA; }   // SELU' from SELU's output
+// SELU' from the pre-activation, for the dense layers (fc1, fa, fc2, fc3), whose units can sit at -lambda alpha on every site of a batch: there
+// y + lambda alpha cancels to rounding noise of 1e-7 where the derivative is 1e-6, the unit's bias gradient is that noise, and Adam's division by
+// sqrt(v) turns it into full-size steps (measured: five steps on ONT-HG002, fc1's bias off by 7.6e-4 against 9e-6 with this form).  192 bytes per
+// site for fc1; the other three are in registers anyway.  The convolutions, 99.7 % of the stored activations, take SELU' from the output.
+__device__ __forceinline__ float selud_pre(float x) { return x > 0.0f ? SELU_L : SELU_LA * expf(x); }
+
+__device__ __forceinline__ bool is_bias(int i)
+{
+    if (i < O_K2) return (i >= O_B11 && i < O_K12) || (i >= O_B12 && i < O_K13) || i >= O_B13;
+    if (i < O_KF) return (i >= O_B2 && i < O_K3) || i >= O_B3;
+    if (i < O_FAB) return i >= O_BF && i < O_FA;
+    if (i < O_HEAD) return true;
+    if (i < O_FC2) return (i - O_HEAD) % 36 >= 34;
+    if (i < O_FC3) return i >= O_FC2B;
+    return (i >= O_FC3B && i < O_GT) || i >= O_GTB;
+}
+
+// the coverage scale of nc_snp_forward, mode 0 (snpCaller.py:93-96): rows 1..4, channels 0..3
+__global__ __launch_bounds__(256) void k_scale_x(const float *__restrict__ x, const double *__restrict__ scale, float *__restrict__ xs, int64_t n)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n * 1025) return;
+    const int64_t s = g / 1025;
+    const int i = (int)(g - s * 1025), h = i / 205, c = i % 5;
+    float v = x[g];
+    if (h > 0 && c < 4) v *= (float)scale[s];
+    xs[s * XS + i] = v;
+}
+
+// conv1 (1x5, 5x1, 5x5, same padding) of one output position per lane; weights are wave-uniform operands.  x: [site][pitch]
+__global__ __launch_bounds__(256) void k_conv1_fwd(const float *__restrict__ x, int pitch, const float *__restrict__ w, float *__restrict__ a1, int64_t npos)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= npos) return;
+    const int64_t site = g / 205;
+    const int r = (int)(g - site * 205), h = r / 41, x0 = r - h * 41;
+    const float *xs = x + site * pitch;
+    float acc[48];
+#pragma unroll
+    for (int o = 0; o < 16; o++) { acc[o] = w[O_B11 + o]; acc[16 + o] = w[O_B12 + o]; acc[32 + o] = w[O_B13 + o]; }
+#pragma unroll 1
+    for (int dy = 0; dy < 5; dy++) {
+        const int iy = h + dy - 2;
+#pragma unroll 1
+        for (int dx = 0; dx < 5; dx++) {
+            const int ix = x0 + dx - 2;
+            const bool in = iy >= 0 && iy < 5 && ix >= 0 && ix < 41;
+#pragma unroll
+            for (int c = 0; c < 5; c++) {
+                const float xv = in ? xs[(iy * 41 + ix) * 5 + c] : 0.0f;
+                const float *w3 = w + O_K13 + ((dy * 5 + dx) * 5 + c) * 16;
+#pragma unroll
+                for (int o = 0; o < 16; o++) acc[32 + o] = fmaf(xv, w3[o], acc[32 + o]);
+                if (dy == 2) {
+                    const float *w1 = w + O_K11 + (dx * 5 + c) * 16;
+#pragma unroll
+                    for (int o = 0; o < 16; o++) acc[o] = fmaf(xv, w1[o], acc[o]);
+                }
+                if (dx == 2) {
+                    const float *w2 = w + O_K12 + (dy * 5 + c) * 16;
+#pragma unroll
+                    for (int o = 0; o < 16; o++) acc[16 + o] = fmaf(xv, w2[o], acc[16 + o]);
+                }
+            }
+        }
+    }
+    float4 *op = reinterpret_cast<float4 *>(a1 + g * 48);
+#pragma unroll
+    for (int o = 0; o < 48; o += 4) op[o / 4] = make_float4(selu_acc(acc[o]), selu_acc(acc[o + 1]), selu_acc(acc[o + 2]), selu_acc(acc[o + 3]));
+}
+
+// conv2 / conv3 forward: k7_conv23_mfma of nc_cnn_fp32.hip (implicit GEMM, M = output positions, N = CO, K = 6 CI tap-major in groups of 16,
+// weights in LDS in fragment order) with the accurate exponential in the SELU.
+template <int HI, int WI, int CI, int CO>
+__global__ __launch_bounds__(256) void k_conv23_fwd(const float *__restrict__ in, const float *__restrict__ wk, const float *__restrict__ wb,
+                                                    float *__restrict__ out, int64_t npos)
+{
+    constexpr int HO = HI - 1, WO = (WI - 3) / 2 + 1, K = 6 * CI, NG = K / 16, TN = CO / 16;
+    static_assert(CI % 4 == 0 && K % 16 == 0 && CO % 16 == 0, "k_conv23_fwd: shape");
+    __shared__ float4 wf[NG][TN][64];
+    for (int idx = threadIdx.x; idx < NG * TN * 64; idx += 256) {
+        const int l = idx & 63, tn = (idx >> 6) % TN, G = (idx >> 6) / TN;
+        const int k0 = 16 * G + 4 * (l >> 4), col = tn * 16 + (l & 15);
+        wf[G][tn][l] = make_float4(wk[(k0 + 0) * CO + col], wk[(k0 + 1) * CO + col], wk[(k0 + 2) * CO + col], wk[(k0 + 3) * CO + col]);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kq = lane >> 4, c16 = lane & 15;
+    const int64_t ntiles = (npos + 15) / 16;
+    float bias[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; tn++) bias[tn] = wb[tn * 16 + c16];
+    for (int64_t tile = (int64_t)blockIdx.x * 4 + wv; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
+        int64_t m = tile * 16 + c16;
+        if (m >= npos) m = npos - 1;
+        const int64_t site = m / (HO * WO);
+        const int r = (int)(m - site * (HO * WO));
+        const int y = r / WO, xq = r - y * WO;
+        const float *ip = in + ((site * HI + y) * WI + 2 * xq) * CI;
+        f32x4v acc[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; tn++) acc[tn] = (f32x4v){bias[tn], bias[tn], bias[tn], bias[tn]};
+#pragma unroll
+        for (int G = 0; G < NG; G++) {
+            const int k0 = 16 * G + 4 * kq, tap = k0 / CI, ci = k0 - tap * CI;
+            const float4 a = *reinterpret_cast<const float4 *>(ip + ((tap / 3) * WI + (tap % 3)) * CI + ci);
+#pragma unroll
+            for (int tn = 0; tn < TN; tn++) {
+                const float4 b = wf[G][tn][lane];
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[tn], 0, 0, 0);
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[tn], 0, 0, 0);
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[tn], 0, 0, 0);
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[tn], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; rr++) {
+            const int64_t pos = tile * 16 + 4 * kq + rr;
+            if (pos < npos) {
+#pragma unroll
+                for (int tn = 0; tn < TN; tn++) out[pos * CO + tn * 16 + c16] = selu_acc(acc[tn][rr]);
+            }
+        }
+    }
+}
+
+// fc1 forward: k3_fc1<48, 1> of nc_cnn_fp32.hip (M = 16 sites, split-K over the four waves, combined through LDS) without its load pipeline.
+// It also writes SELU' of its 48 units, taken from the pre-activation it holds (see selud_pre).
+__global__ __launch_bounds__(256) void k_fc1_fwd(const float *__restrict__ in, const float *__restrict__ wk, const float *__restrict__ wb,
+                                                 float *__restrict__ out, float *__restrict__ dout, int64_t n)
+{
+    constexpr int F = 48, TN = 3, K = N3;
+    __shared__ float red[3][TN][4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = lane >> 4, c16 = lane & 15;
+    const int64_t tile0 = (int64_t)blockIdx.x * 16;
+    int64_t s = tile0 + c16;
+    if (s >= n) s = n - 1;
+    const float *ip = in + s * K + 4 * q;
+    const float *wl = wk + (4 * q) * F + c16;
+    f32x4v acc[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; tn++) {
+        const float b = wv == 0 ? wb[tn * 16 + c16] : 0.0f;
+        acc[tn] = (f32x4v){b, b, b, b};
+    }
+    constexpr int NG = K / 16;                                           // 108 groups of 16: 27 per wave
+    for (int j = wv * (NG / 4); j < (wv + 1) * (NG / 4); j++) {
+        const float4 a = *reinterpret_cast<const float4 *>(ip + 16 * j);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float av = i == 0 ? a.x : i == 1 ? a.y : i == 2 ? a.z : a.w;
+#pragma unroll
+            for (int tn = 0; tn < TN; tn++) acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wl[(16 * j + i) * F + tn * 16], acc[tn], 0, 0, 0);
+        }
+    }
+    if (wv > 0) {
+#pragma unroll
+        for (int tn = 0; tn < TN; tn++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) red[wv - 1][tn][r][lane] = acc[tn][r];
+    }
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int64_t so = tile0 + 4 * q + r;
+#pragma unroll
+            for (int tn = 0; tn < TN; tn++) {
+                const float v = acc[tn][r] + red[0][tn][r][lane] + red[1][tn][r][lane] + red[2][tn][r][lane];
+                if (so < n) {
+                    out[so * F + tn * 16 + c16] = selu_acc(v);
+                    dout[so * F + tn * 16 + c16] = selud_pre(v);
+                }
+            }
+        }
+    }
+}
+
+template <int NI, int NO>
+__device__ __forceinline__ void dense(const float (&in)[NI], const float *__restrict__ k, const float *__restrict__ b, float (&out)[NO], bool act,
+                                      float *deriv = nullptr)
+{
+#pragma unroll
+    for (int o = 0; o < NO; o++) out[o] = b[o];
+#pragma unroll
+    for (int i = 0; i < NI; i++)
+#pragma unroll
+        for (int o = 0; o < NO; o++) out[o] = fmaf(in[i], k[i * NO + o], out[o]);
+    if (act) {
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            if (deriv) deriv[o] = selud_pre(out[o]);
+            out[o] = selu_acc(out[o]);
+        }
+    }
+}
+
+// softmax of a pair of logits; returns log(exp z0 + exp z1)
+__device__ __forceinline__ float softmax2(float z0, float z1, float &p0, float &p1)
+{
+    const float m = fmaxf(z0, z1), e0 = expf(z0 - m), e1 = expf(z1 - m), sum = e0 + e1;
+    p0 = e0 / sum;
+    p1 = e1 / sum;
+    return m + logf(sum);
+}
+
+// Everything behind fc1 of one site per lane: dropout, fa, the four heads, fc2, fc3, GT (model_architect.py:53-62); with labels also the five
+// cross-entropies and the chain back to fc1's pre-activation: softmax Jacobians of the heads into fc3, the mask, SELU' (f1d: fc1's).  inv_n = 1 / batch.
+__global__ __launch_bounds__(64) void k_heads(const float *__restrict__ f1, const float *__restrict__ f1d, const float *__restrict__ w, const int32_t *__restrict__ ref_code,
+                                              const uint8_t *__restrict__ mask, float inv_keep, const uint8_t *__restrict__ label, float inv_n, int64_t n,
+                                              float *__restrict__ probs, float *__restrict__ gt, float *__restrict__ tact, float *__restrict__ tdel,
+                                              float *__restrict__ df1, float *__restrict__ loss)
+{
+    const int64_t s = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (s >= n) return;
+    float f1m[48], fa[16], in17[17], z[8], p[8], fc2[16], in24[24], fc3[8], g[2], pg[2], fad[16], fc2d[16], fc3d[8];
+#pragma unroll
+    for (int i = 0; i < 48; i++) f1m[i] = mask ? f1[s * 48 + i] * (mask[s * 48 + i] ? inv_keep : 0.0f) : f1[s * 48 + i];
+    dense<48, 16>(f1m, w + O_FA, w + O_FAB, fa, true, fad);
+#pragma unroll
+    for (int i = 0; i < 16; i++) in17[i] = fa[i];
+    const int rc = ref_code[s];
+    float lse[5];
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+        in17[16] = rc == h ? 1.0f : 0.0f;
+        float zz[2];
+        dense<17, 2>(in17, w + O_HEAD + 36 * h, w + O_HEAD + 36 * h + 34, zz, false);
+        z[2 * h] = zz[0];
+        z[2 * h + 1] = zz[1];
+        lse[h] = softmax2(zz[0], zz[1], p[2 * h], p[2 * h + 1]);
+        if (probs) probs[s * 4 + h] = p[2 * h + 1];
+    }
+    dense<48, 16>(f1m, w + O_FC2, w + O_FC2B, fc2, true, fc2d);
+#pragma unroll
+    for (int i = 0; i < 16; i++) in24[i] = fc2[i];
+#pragma unroll
+    for (int i = 0; i < 8; i++) in24[16 + i] = p[i];
+    dense<24, 8>(in24, w + O_FC3, w + O_FC3B, fc3, true, fc3d);
+    dense<8, 2>(fc3, w + O_GT, w + O_GTB, g, false);
+    lse[4] = softmax2(g[0], g[1], pg[0], pg[1]);
+    if (gt) { gt[s * 2] = pg[0]; gt[s * 2 + 1] = pg[1]; }
+    if (!label) return;
+    float *ta = tact + s * TA;
+#pragma unroll
+    for (int i = 0; i < 48; i++) ta[i] = f1m[i];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { ta[TA_FA + i] = fa[i]; ta[TA_FC2 + i] = fc2[i]; }
+#pragma unroll
+    for (int i = 0; i < 8; i++) { ta[TA_Z + i] = z[i]; ta[TA_P + i] = p[i]; ta[TA_FC3 + i] = fc3[i]; }
+
+    float dz[8], dg[2], dfc3[8], din24[24], dfc2[16], dfa[16];
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+        const int lab = label[s * 5 + h] ? 1 : 0;
+        loss[s * 5 + h] = lse[h] - (lab ? z[2 * h + 1] : z[2 * h]);
+        dz[2 * h] = (p[2 * h] - (lab ? 0.0f : 1.0f)) * inv_n;
+        dz[2 * h + 1] = (p[2 * h + 1] - (lab ? 1.0f : 0.0f)) * inv_n;
+    }
+    {
+        const int lab = label[s * 5 + 4] ? 1 : 0;
+        loss[s * 5 + 4] = lse[4] - (lab ? g[1] : g[0]);
+        dg[0] = (pg[0] - (lab ? 0.0f : 1.0f)) * inv_n;
+        dg[1] = (pg[1] - (lab ? 1.0f : 0.0f)) * inv_n;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) dfc3[i] = fmaf(w[O_GT + 2 * i], dg[0], w[O_GT + 2 * i + 1] * dg[1]) * fc3d[i];
+#pragma unroll
+    for (int i = 0; i < 24; i++) {
+        float a = 0.0f;
+#pragma unroll
+        for (int o = 0; o < 8; o++) a = fmaf(w[O_FC3 + i * 8 + o], dfc3[o], a);
+        din24[i] = a;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) dfc2[i] = din24[i] * fc2d[i];
+#pragma unroll
+    for (int h = 0; h < 4; h++) {                                       // the GT loss through the softmax of head h
+        const float d0 = din24[16 + 2 * h], d1 = din24[17 + 2 * h], dot = fmaf(p[2 * h], d0, p[2 * h + 1] * d1);
+        dz[2 * h] = fmaf(p[2 * h], d0 - dot, dz[2 * h]);
+        dz[2 * h + 1] = fmaf(p[2 * h + 1], d1 - dot, dz[2 * h + 1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        float a = 0.0f;
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+            a = fmaf(w[O_HEAD + 36 * h + 2 * i], dz[2 * h], a);
+            a = fmaf(w[O_HEAD + 36 * h + 2 * i + 1], dz[2 * h + 1], a);
+        }
+        dfa[i] = a * fad[i];
+    }
+    float *td = tdel + s * TD;
+#pragma unroll
+    for (int i = 0; i < 16; i++) { td[i] = dfa[i]; td[TD_FC2 + i] = dfc2[i]; }
+#pragma unroll
+    for (int i = 0; i < 8; i++) { td[TD_H + i] = dz[i]; td[TD_FC3 + i] = dfc3[i]; }
+    td[TD_GT] = dg[0];
+    td[TD_GT + 1] = dg[1];
+#pragma unroll
+    for (int i = 0; i < 48; i++) {
+        float a = 0.0f;
+#pragma unroll
+        for (int o = 0; o < 16; o++) {
+            a = fmaf(w[O_FA + i * 16 + o], dfa[o], a);
+            a = fmaf(w[O_FC2 + i * 16 + o], dfc2[o], a);
+        }
+        const float mk = mask ? (mask[s * 48 + i] ? inv_keep : 0.0f) : 1.0f;
+        df1[s * 48 + i] = a * mk * f1d[s * 48 + i];
+    }
+}
+
+// weight gradients of fc1's bias and of every layer behind fc1 (1978 parameters), one parameter per lane, the slab's sites in order
+__global__ __launch_bounds__(256) void k_small_wgrad(const float *__restrict__ tact, const float *__restrict__ tdel, const float *__restrict__ df1,
+                                                     const int32_t *__restrict__ ref_code, int64_t n, float *__restrict__ slabs)
+{
+    const int t = blockIdx.y * 256 + threadIdx.x;
+    if (t >= 48 + NPAR - O_FA) return;
+    const int gi = t < 48 ? O_BF + t : O_FA + (t - 48);
+    // in: -1 the constant 1 (bias), -2 - h the reference one-hot of head h, else an offset in the activation record; del: an offset in
+    // the gradient record, or -1 - o for d fc1
+    int in = -1, del = 0;
+    if (gi < O_FA) del = -1 - t;
+    else if (gi < O_FAB) { in = (gi - O_FA) / 16; del = (gi - O_FA) % 16; }
+    else if (gi < O_HEAD) del = gi - O_FAB;
+    else if (gi < O_FC2) {
+        const int h = (gi - O_HEAD) / 36, r = (gi - O_HEAD) % 36;
+        if (r < 34) { in = r / 2 < 16 ? TA_FA + r / 2 : -2 - h; del = TD_H + 2 * h + r % 2; }
+        else del = TD_H + 2 * h + (r - 34);
+    }
+    else if (gi < O_FC2B) { in = (gi - O_FC2) / 16; del = TD_FC2 + (gi - O_FC2) % 16; }
+    else if (gi < O_FC3) del = TD_FC2 + gi - O_FC2B;
+    else if (gi < O_FC3B) { const int i = (gi - O_FC3) / 8; in = i < 16 ? TA_FC2 + i : TA_P + i - 16; del = TD_FC3 + (gi - O_FC3) % 8; }
+    else if (gi < O_GT) del = TD_FC3 + gi - O_FC3B;
+    else if (gi < O_GTB) { in = TA_FC3 + (gi - O_GT) / 2; del = TD_GT + (gi - O_GT) % 2; }
+    else del = TD_GT + gi - O_GTB;
+    const int64_t s0 = (int64_t)blockIdx.x * SLAB, s1 = s0 + SLAB < n ? s0 + SLAB : n;
+    float acc = 0.0f;
+    for (int64_t s = s0; s < s1; s++) {
+        const float d = del < 0 ? df1[s * 48 + (-1 - del)] : tdel[s * TD + del];
+        const float a = in >= 0 ? tact[s * TA + in] : in == -1 ? 1.0f : (ref_code[s] == -2 - in ? 1.0f : 0.0f);
+        acc = fmaf(a, d, acc);
+    }
+    slabs[(int64_t)blockIdx.x * NPAR + gi] = acc;
+}
+
+// fc1 weight gradient dW[k][o] = sum_s a3[s][k] d[s][o] of one slab: M = k (108 tiles of 16), N = 48, K = the slab's 64 sites (16 steps).
+// grid (slabs, 9): 36 waves per slab, three k tiles each; a wave holds the slab's d fragments in registers.
+__global__ __launch_bounds__(256) void k_fc1_wgrad(const float *__restrict__ a3, const float *__restrict__ df1, int64_t n, float *__restrict__ slabs)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = lane >> 4, c16 = lane & 15;
+    const int64_t sb = (int64_t)blockIdx.x * SLAB;
+    float b[16][3];
+#pragma unroll
+    for (int st = 0; st < 16; st++) {
+        const int64_t s = sb + 4 * st + q;
+#pragma unroll
+        for (int tn = 0; tn < 3; tn++) b[st][tn] = s < n ? df1[s * 48 + tn * 16 + c16] : 0.0f;
+    }
+    float *out = slabs + (int64_t)blockIdx.x * NPAR + O_KF;
+    for (int kt = blockIdx.y * 4 + wv; kt < 108; kt += 36) {
+        f32x4v acc[3] = {(f32x4v){0, 0, 0, 0}, (f32x4v){0, 0, 0, 0}, (f32x4v){0, 0, 0, 0}};
+#pragma unroll
+        for (int st = 0; st < 16; st++) {
+            const int64_t s = sb + 4 * st + q;
+            const float a = s < n ? a3[s * N3 + kt * 16 + c16] : 0.0f;
+#pragma unroll
+            for (int tn = 0; tn < 3; tn++) acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[st][tn], acc[tn], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int tn = 0; tn < 3; tn++) out[(kt * 16 + 4 * q + r) * 48 + tn * 16 + c16] = acc[tn][r];
+    }
+}
+
+// fc1 data gradient d3[s][k] = SELU'(a3[s][k]) sum_o W[k][o] d[s][o]: M = k (the weights as the A operand, so a lane's four results are four
+// consecutive k of one site: one dwordx4 store), N = 16 sites, K = 48 in float4 pieces (slot q of step (j, i) is o = 16 j + 4 q + i).
+__global__ __launch_bounds__(256) void k_fc1_dgrad(const float *__restrict__ wk, const float *__restrict__ df1, const float *__restrict__ a3, int64_t n,
+                                                   float *__restrict__ d3)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = lane >> 4, c16 = lane & 15;
+    const int64_t s = (int64_t)blockIdx.x * 16 + c16, sc = s < n ? s : n - 1;
+    float4 bd[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) bd[j] = *reinterpret_cast<const float4 *>(df1 + sc * 48 + 16 * j + 4 * q);
+    for (int kt = wv * 27; kt < wv * 27 + 27; kt++) {
+        f32x4v acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const float4 a = *reinterpret_cast<const float4 *>(wk + (kt * 16 + c16) * 48 + 16 * j + 4 * q);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bd[j].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bd[j].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bd[j].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bd[j].w, acc, 0, 0, 0);
+        }
+        if (s < n) {
+            const int64_t o = s * N3 + kt * 16 + 4 * q;
+            const float4 y = *reinterpret_cast<const float4 *>(a3 + o);
+            *reinterpret_cast<float4 *>(d3 + o) = make_float4(acc[0] * selud(y.x), acc[1] * selud(y.y), acc[2] * selud(y.z), acc[3] * selud(y.w));
+        }
+    }
+}
+
+// Weight gradient of a 2x3 stride-(1,2) valid convolution, dW[tap][ci][co] = sum over output positions of in[.. tap ..][ci] d[pos][co], of one
+// slab: M = (tap, ci) in tiles of 16 (a tile lies inside one tap), N = CO, K = output positions, four per MFMA.  grid (slabs, M tiles / MW):
+// the four waves of a workgroup take 16 sites of the slab each and combine through LDS in wave order.
+template <int HI, int WI, int CI, int CO, int MW>
+__global__ __launch_bounds__(256) void k_conv_wgrad(const float *__restrict__ in, const float *__restrict__ d, int64_t n, int koff, float *__restrict__ slabs)
+{
+    constexpr int HO = HI - 1, WO = (WI - 3) / 2 + 1, NPOS = HO * WO, TN = CO / 16;
+    static_assert(CI % 16 == 0 && CO % 16 == 0 && (6 * CI / 16) % MW == 0, "k_conv_wgrad: shape");
+    __shared__ float red[3][MW][TN][4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = lane >> 4, c16 = lane & 15;
+    const int64_t p0 = ((int64_t)blockIdx.x * SLAB + 16 * wv) * NPOS, pend = n * NPOS;
+    int aoff[MW];
+#pragma unroll
+    for (int mw = 0; mw < MW; mw++) {
+        const int m0 = (blockIdx.y * MW + mw) * 16, tap = m0 / CI, ci = m0 - tap * CI;
+        aoff[mw] = ((tap / 3) * WI + (tap % 3)) * CI + ci + c16;
+    }
+    f32x4v acc[MW][TN];
+#pragma unroll
+    for (int mw = 0; mw < MW; mw++)
+#pragma unroll
+        for (int tn = 0; tn < TN; tn++) acc[mw][tn] = (f32x4v){0, 0, 0, 0};
+#pragma unroll 2
+    for (int st = 0; st < 4 * NPOS; st++) {
+        const int64_t p = p0 + 4 * st + q;
+        const bool ok = p < pend;
+        const int64_t site = p / NPOS;
+        const int r = (int)(p - site * NPOS), y = r / WO, x = r - y * WO;
+        const float *ip = in + ((site * HI + y) * WI + 2 * x) * CI;
+        float a[MW], b[TN];
+#pragma unroll
+        for (int mw = 0; mw < MW; mw++) a[mw] = ok ? ip[aoff[mw]] : 0.0f;
+#pragma unroll
+        for (int tn = 0; tn < TN; tn++) b[tn] = ok ? d[p * CO + tn * 16 + c16] : 0.0f;
+#pragma unroll
+        for (int mw = 0; mw < MW; mw++)
+#pragma unroll
+            for (int tn = 0; tn < TN; tn++) acc[mw][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mw], b[tn], acc[mw][tn], 0, 0, 0);
+    }
+    if (wv > 0) {
+#pragma unroll
+        for (int mw = 0; mw < MW; mw++)
+#pragma unroll
+            for (int tn = 0; tn < TN; tn++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) red[wv - 1][mw][tn][r][lane] = acc[mw][tn][r];
+    }
+    __syncthreads();
+    if (wv == 0) {
+        float *out = slabs + (int64_t)blockIdx.x * NPAR + koff;
+#pragma unroll
+        for (int mw = 0; mw < MW; mw++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = (blockIdx.y * MW + mw) * 16 + 4 * q + r;
+#pragma unroll
+                for (int tn = 0; tn < TN; tn++)
+                    out[m * CO + tn * 16 + c16] = ((acc[mw][tn][r] + red[0][mw][tn][r][lane]) + red[1][mw][tn][r][lane]) + red[2][mw][tn][r][lane];
+            }
+    }
+}
+
+// Data gradient of the same convolution (the transposed convolution), times SELU' of the layer below: M = input positions, N = CI,
+// K = (tap, co) in groups of 16; a tap that does not reach an output position from this input position enters as zeros.  The weights
+// sit in LDS in fragment order, transposed: wf[G][tn][lane] = W[tap][ci = 16 tn + (lane & 15)][co0 .. co0 + 3].
+template <int HI, int WI, int CI, int CO>
+__global__ __launch_bounds__(256) void k_conv_dgrad(const float *__restrict__ d, const float *__restrict__ wk, const float *__restrict__ act,
+                                                    float *__restrict__ out, int64_t npos)
+{
+    constexpr int HO = HI - 1, WO = (WI - 3) / 2 + 1, K = 6 * CO, NG = K / 16, TN = CI / 16;
+    static_assert(CI % 16 == 0 && CO % 16 == 0, "k_conv_dgrad: shape");
+    __shared__ float4 wf[NG][TN][64];
+    for (int idx = threadIdx.x; idx < NG * TN * 64; idx += 256) {
+        const int l = idx & 63, tn = (idx >> 6) % TN, G = (idx >> 6) / TN;
+        const int k0 = 16 * G + 4 * (l >> 4), tap = k0 / CO, co = k0 - tap * CO, ci = tn * 16 + (l & 15);
+        wf[G][tn][l] = *reinterpret_cast<const float4 *>(wk + (tap * CI + ci) * CO + co);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kq = lane >> 4, c16 = lane & 15;
+    const int64_t ntiles = (npos + 15) / 16;
+    for (int64_t tile = (int64_t)blockIdx.x * 4 + wv; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
+        int64_t m = tile * 16 + c16;
+        if (m >= npos) m = npos - 1;
+        const int64_t site = m / (HI * WI);
+        const int r = (int)(m - site * (HI * WI)), yi = r / WI, xi = r - yi * WI;
+        const float *dp = d + site * (HO * WO * CO);
+        f32x4v acc[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; tn++) acc[tn] = (f32x4v){0, 0, 0, 0};
+#pragma unroll
+        for (int G = 0; G < NG; G++) {
+            const int tap = (16 * G) / CO, co = 16 * G - tap * CO + 4 * kq;
+            const int y = yi - tap / 3, xx = xi - tap % 3;
+            const bool ok = y >= 0 && y < HO && xx >= 0 && (xx & 1) == 0 && (xx >> 1) < WO;
+            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (ok) a = *reinterpret_cast<const float4 *>(dp + (y * WO + (xx >> 1)) * CO + co);
+#pragma unroll
+            for (int tn = 0; tn < TN; tn++) {
+                const float4 b = wf[G][tn][lane];
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[tn], 0, 0, 0);
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[tn], 0, 0, 0);
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[tn], 0, 0, 0);
+                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[tn], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; rr++) {
+            const int64_t pos = tile * 16 + 4 * kq + rr;
+            if (pos < npos) {
+#pragma unroll
+                for (int tn = 0; tn < TN; tn++) {
+                    const int64_t o = pos * CI + tn * 16 + c16;
+                    out[o] = acc[tn][rr] * selud(act[o]);
+                }
+            }
+        }
+    }
+}
+
+// bias gradient of a convolution, db[c] = sum over the slab's positions of d[pos][c]: 256 / C strided partial sums per channel,
+// combined in order
+template <int C, int NPOS>
+__global__ __launch_bounds__(256) void k_bias_grad(const float *__restrict__ d, int64_t n, int boff, float *__restrict__ slabs)
+{
+    constexpr int NP = 256 / C;
+    __shared__ float red[NP][C];
+    const int c = threadIdx.x % C, part = threadIdx.x / C;
+    const int64_t s0 = (int64_t)blockIdx.x * SLAB, s1 = s0 + SLAB < n ? s0 + SLAB : n;
+    float acc = 0.0f;
+    for (int64_t p = s0 * NPOS + part; p < s1 * NPOS; p += NP) acc += d[p * C + c];
+    red[part][c] = acc;
+    __syncthreads();
+    if (part == 0) {
+        float v = red[0][c];
+        for (int k = 1; k < NP; k++) v += red[k][c];
+        slabs[(int64_t)blockIdx.x * NPAR + boff + c] = v;
+    }
+}
+
+// conv1's three kernels (1x5, 5x1, 5x5, same padding) and their biases of one slab: M = (tap, ci) rows of one kernel, 25 or 125 of them, N = its 16
+// output channels, K = output positions, four per MFMA; a tap outside the image enters as zero.  A kernel's bias follows it in the blob, so
+// the bias is row 25 / 125: its A operand is the constant 1.  grid (slabs, 6): y = 0..3 the 5x5 kernel's rows 32 y .. 32 y + 31, y = 4 the 1x5,
+// y = 5 the 5x1 kernel; the four waves take 16 sites of the slab each and combine through LDS in wave order.  x: [site][pitch]
+__global__ __launch_bounds__(256) void k_conv1_wgrad(const float *__restrict__ x, int pitch, const float *__restrict__ d1, int64_t n, float *__restrict__ slabs)
+{
+    __shared__ float red[3][2][4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = lane >> 4, c16 = lane & 15;
+    const int br = blockIdx.y < 4 ? 2 : blockIdx.y - 4;                                     // 0: 1x5, 1: 5x1, 2: 5x5 = channels 16 br .. 16 br + 15
+    const int nrows = br == 2 ? 125 : 25, base = br == 0 ? O_K11 : br == 1 ? O_K12 : O_K13, m0 = blockIdx.y < 4 ? 32 * blockIdx.y : 0;
+    int kind[2], off[2], dyo[2], dxo[2];                                                    // kind 0: a tap, 1: the bias row, 2: padding
+#pragma unroll
+    for (int mw = 0; mw < 2; mw++) {
+        const int m = m0 + 16 * mw + c16, tap = m / 5;
+        kind[mw] = m < nrows ? 0 : m == nrows ? 1 : 2;
+        dyo[mw] = (br == 2 ? tap / 5 : br == 1 ? tap : 2) - 2;
+        dxo[mw] = (br == 2 ? tap % 5 : br == 0 ? tap : 2) - 2;
+        off[mw] = (dyo[mw] * 41 + dxo[mw]) * 5 + m % 5;
+    }
+    const int64_t p0 = ((int64_t)blockIdx.x * SLAB + 16 * wv) * 205, pend = n * 205;
+    f32x4v acc[2] = {(f32x4v){0, 0, 0, 0}, (f32x4v){0, 0, 0, 0}};
+#pragma unroll 4
+    for (int st = 0; st < 4 * 205; st++) {
+        const int64_t p = p0 + 4 * st + q;
+        const bool ok = p < pend;
+        const int64_t site = p / 205;
+        const int r = (int)(p - site * 205), h = r / 41, w = r - h * 41;
+        const float *xs = x + site * pitch + r * 5;
+        float a[2];
+#pragma unroll
+        for (int mw = 0; mw < 2; mw++) {
+            const int iy = h + dyo[mw], ix = w + dxo[mw];
+            a[mw] = 0.0f;
+            if (ok && kind[mw] == 1) a[mw] = 1.0f;
+            if (ok && kind[mw] == 0 && iy >= 0 && iy < 5 && ix >= 0 && ix < 41) a[mw] = xs[off[mw]];
+        }
+        const float b = ok ? d1[p * 48 + 16 * br + c16] : 0.0f;
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b, acc[1], 0, 0, 0);
+    }
+    if (wv > 0) {
+#pragma unroll
+        for (int mw = 0; mw < 2; mw++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) red[wv - 1][mw][r][lane] = acc[mw][r];
+    }
+    __syncthreads();
+    if (wv == 0) {
+        float *out = slabs + (int64_t)blockIdx.x * NPAR + base;
+#pragma unroll
+        for (int mw = 0; mw < 2; mw++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = m0 + 16 * mw + 4 * q + r;
+                if (m <= nrows) out[m * 16 + c16] = ((acc[mw][r] + red[0][mw][r][lane]) + red[1][mw][r][lane]) + red[2][mw][r][lane];
+            }
+    }
+}
+
+// the six loss terms [cost, GT, A, G, T, C]: batch means of the per-site cross-entropies and gamma * sum over kernel entries of w^2 / 2; one
+// workgroup, strided partial sums combined by a fixed tree
+__global__ __launch_bounds__(256) void k_loss_reduce(const float *__restrict__ loss, int64_t n, const float *__restrict__ w, float gamma, float *__restrict__ out6)
+{
+    __shared__ double red[6][256];
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t s = threadIdx.x; s < n; s += 256)
+#pragma unroll
+        for (int j = 0; j < 5; j++) acc[j] += (double)loss[s * 5 + j];
+    for (int i = threadIdx.x; i < NPAR; i += 256)
+        if (!is_bias(i)) acc[5] += (double)w[i] * (double)w[i];
+#pragma unroll
+    for (int j = 0; j < 6; j++) red[j][threadIdx.x] = acc[j];
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (threadIdx.x < k)
+#pragma unroll
+            for (int j = 0; j < 6; j++) red[j][threadIdx.x] += red[j][threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double a = red[0][0] / (double)n, g = red[1][0] / (double)n, t = red[2][0] / (double)n, c = red[3][0] / (double)n, gt = red[4][0] / (double)n;
+        out6[0] = (float)(a + g + t + c + gt + 0.5 * (double)gamma * red[5][0]);
+        out6[1] = (float)gt;
+        out6[2] = (float)a;
+        out6[3] = (float)g;
+        out6[4] = (float)t;
+        out6[5] = (float)c;
+    }
+}
+
+// One parameter per lane: gradient = g_in (earlier slices, may be NULL) + the slabs in slab order (+ gamma w on kernel entries with `reg`);
+// written to g_out (may be NULL); with `step` the Adam update in TensorFlow's form, w -= lr_t m / (sqrt(v) + eps).
+__global__ __launch_bounds__(256) void k_params(const float *__restrict__ g_in, const float *__restrict__ slabs, int ns, int reg, float gamma,
+                                                float *__restrict__ g_out, int step, float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                float lr_t, float b1, float b2, float eps)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= NPAR) return;
+    float g = g_in ? g_in[i] : 0.0f;
+    for (int k = 0; k < ns; k++) g += slabs[(int64_t)k * NPAR + i];
+    const float wi = w[i];
+    if (reg && !is_bias(i)) g = fmaf(gamma, wi, g);
+    if (g_out) g_out[i] = g;
+    if (step) {
+        const float mi = fmaf(b1, m[i], (1.0f - b1) * g), vi = fmaf(b2, v[i], (1.0f - b2) * g * g);
+        m[i] = mi;
+        v[i] = vi;
+        w[i] = wi - lr_t * mi / (sqrtf(vi) + eps);
+    }
+}
+
+}   // namespace
+
+enum { TS_FWD = 0, TS_HEADS, TS_FC1, TS_CONV3, TS_CONV2, TS_CONV1, TS_PARAMS, TS_N };
+
+struct nc_train {
+    nc_ctx *ctx = nullptr;
+    int64_t max_batch = 0, slice = 0;
+    size_t ws_bytes = 0;
+    float *w = nullptr, *m = nullptr, *v = nullptr, *g = nullptr;      // fp32 state in blob order
+    float *ws = nullptr;                                               // one allocation: the buffers below
+    float *xs, *a1, *a2, *a3, *f1, *f1d, *tact, *tdel, *df1, *d1, *d2, *d3, *slabs, *loss, *loss6;
+    int64_t t = 0;                                                     // Adam steps taken
+    // the gradient of the last nc_train_loss_grad = (partial ? g : 0) + the pending slabs + gamma w: summed by nc_train_adam's own kernel
+    bool have_grad = false, partial = false;
+    int pending_ns = 0;
+    float pending_gamma = 0.0f;
+    int timing = 0;
+    hipEvent_t ev[TS_N + 1] = {nullptr};
+    float stage_ms[TS_N] = {0};
+};
+
+namespace {
+
+void mark(nc_train *tr, int i)
+{
+    if (tr->timing) (void)hipEventRecord(tr->ev[i], tr->ctx->stream);
+}
+
+int check_call(nc_train *tr, const char *what, int64_t n, const void *x, const void *rc)
+{
+    if (!tr) return NC_ERR_ARG;
+    if (n < 1 || n > tr->max_batch) return nc_fail(tr->ctx, NC_ERR_ARG, "%s: n = %lld outside 1 .. max_batch = %lld", what, (long long)n, (long long)tr->max_batch);
+    if (!x || !rc) return nc_fail(tr->ctx, NC_ERR_ARG, "%s: null argument", what);
+    return NC_OK;
+}
+
+// conv1 - fc1 of `nb` sites (a slice) into the workspace
+void forward_trunk(nc_train *tr, int64_t nb, const float *x, const double *scale)
+{
+    hipStream_t st = tr->ctx->stream;
+    int pitch = 1025;
+    if (scale) {
+        hipLaunchKernelGGL(k_scale_x, dim3(blocks_for(nb * 1025)), dim3(256), 0, st, x, scale, tr->xs, nb);
+        x = tr->xs;
+        pitch = XS;
+    }
+    auto grid = [](int64_t npos) { const int64_t t = (npos + 63) / 64; return dim3((unsigned)(t < 2048 ? t : 2048)); };
+    hipLaunchKernelGGL(k_conv1_fwd, dim3(blocks_for(nb * 205)), dim3(256), 0, st, x, pitch, tr->w, tr->a1, nb * 205);
+    hipLaunchKernelGGL((k_conv23_fwd<5, 41, 48, 32>), grid(nb * 80), dim3(256), 0, st, tr->a1, tr->w + O_K2, tr->w + O_B2, tr->a2, nb * 80);
+    hipLaunchKernelGGL((k_conv23_fwd<4, 20, 32, 64>), grid(nb * 27), dim3(256), 0, st, tr->a2, tr->w + O_K3, tr->w + O_B3, tr->a3, nb * 27);
+    hipLaunchKernelGGL(k_fc1_fwd, dim3(blocks_for(nb, 16)), dim3(256), 0, st, tr->a3, tr->w + O_KF, tr->w + O_BF, tr->f1, tr->f1d, nb);
+}
+
+}   // namespace
+
+extern "C" {
+
+int nc_train_create(nc_ctx *ctx, int32_t kind, int64_t max_batch, nc_train **out)
+{
+    if (!ctx || !out) return NC_ERR_ARG;
+    *out = nullptr;
+    if (kind != NC_MODEL_SNP)
+        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_train_create: only the diploid SNP model (kind %d) is trained, not kind %d", NC_MODEL_SNP, kind);
+    if (max_batch < 1) return nc_fail(ctx, NC_ERR_ARG, "nc_train_create: max_batch");
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    nc_train *tr = new nc_train;
+    tr->ctx = ctx;
+    tr->max_batch = max_batch;
+    tr->slice = max_batch < MAX_SLICE ? max_batch : MAX_SLICE;
+    const int64_t ns = (tr->slice + SLAB - 1) / SLAB;
+    size_t sizes[] = {(size_t)tr->slice * XS, (size_t)tr->slice * N1, (size_t)tr->slice * N2, (size_t)tr->slice * N3, (size_t)tr->slice * 48,
+                      (size_t)tr->slice * 48, (size_t)tr->slice * TA, (size_t)tr->slice * TD, (size_t)tr->slice * 48, (size_t)tr->slice * N1, (size_t)tr->slice * N2,
+                      (size_t)tr->slice * N3, (size_t)ns * NPAR, (size_t)max_batch * 5, 8};
+    float **ptrs[] = {&tr->xs, &tr->a1, &tr->a2, &tr->a3, &tr->f1, &tr->f1d, &tr->tact, &tr->tdel, &tr->df1, &tr->d1, &tr->d2, &tr->d3, &tr->slabs, &tr->loss, &tr->loss6};
+    size_t total = 0;
+    for (size_t s : sizes) total += (s + 63) & ~size_t(63);
+    tr->ws_bytes = total * 4;
+    hipError_t e = hipMalloc((void **)&tr->ws, tr->ws_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&tr->w, (size_t)NPAR * 4 * 4);
+    if (e != hipSuccess) {
+        if (tr->ws) (void)hipFree(tr->ws);
+        delete tr;
+        return nc_fail(ctx, NC_ERR_NOMEM, "nc_train_create: hipMalloc of %zu bytes: %s", total * 4, hipGetErrorString(e));
+    }
+    tr->m = tr->w + NPAR;
+    tr->v = tr->m + NPAR;
+    tr->g = tr->v + NPAR;
+    size_t off = 0;
+    for (size_t i = 0; i < sizeof sizes / sizeof sizes[0]; i++) {
+        *ptrs[i] = tr->ws + off;
+        off += (sizes[i] + 63) & ~size_t(63);
+    }
+    NC_HIP(ctx, hipMemsetAsync(tr->w, 0, (size_t)NPAR * 4 * 4, ctx->stream));
+    for (int i = 0; i <= TS_N; i++) NC_HIP(ctx, hipEventCreate(&tr->ev[i]));
+    *out = tr;
+    return NC_OK;
+}
+
+int nc_train_free(nc_train *tr)
+{
+    if (!tr) return NC_OK;
+    (void)hipSetDevice(tr->ctx->device);
+    (void)hipStreamSynchronize(tr->ctx->stream);
+    for (int i = 0; i <= TS_N; i++)
+        if (tr->ev[i]) (void)hipEventDestroy(tr->ev[i]);
+    if (tr->ws) (void)hipFree(tr->ws);
+    if (tr->w) (void)hipFree(tr->w);
+    delete tr;
+    return NC_OK;
+}
+
+int nc_train_set_weights(nc_train *tr, const float *blob_host, size_t n_floats)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (!blob_host || n_floats != (size_t)NPAR) return nc_fail(ctx, NC_ERR_ARG, "nc_train_set_weights: expects %d floats", NPAR);
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    NC_HIP(ctx, hipMemcpyAsync(tr->w, blob_host, (size_t)NPAR * 4, hipMemcpyHostToDevice, ctx->stream));
+    NC_HIP(ctx, hipMemsetAsync(tr->m, 0, (size_t)NPAR * 4 * 3, ctx->stream));
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    tr->t = 0;
+    tr->have_grad = false;
+    return NC_OK;
+}
+
+int nc_train_get_weights(nc_train *tr, float *blob_host, size_t n_floats)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (!blob_host || n_floats != (size_t)NPAR) return nc_fail(ctx, NC_ERR_ARG, "nc_train_get_weights: expects %d floats", NPAR);
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    NC_HIP(ctx, hipMemcpyAsync(blob_host, tr->w, (size_t)NPAR * 4, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NC_OK;
+}
+
+int nc_train_forward(nc_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                     float keep, float *probs_dev, float *gt_dev)
+{
+    NC_TRY(check_call(tr, "nc_train_forward", n, x_dev, ref_code_dev));
+    nc_ctx *ctx = tr->ctx;
+    if (!probs_dev || !(keep > 0.0f && keep <= 1.0f)) return nc_fail(ctx, NC_ERR_ARG, "nc_train_forward: bad argument");
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    if (keep == 1.0f) keep_mask_dev = nullptr;
+    for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
+        const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
+        forward_trunk(tr, nb, x_dev + s0 * NC_SNP_TENSOR, scale_dev ? scale_dev + s0 : nullptr);
+        hipLaunchKernelGGL(k_heads, dim3(blocks_for(nb, 64)), dim3(64), 0, ctx->stream, tr->f1, tr->f1d, tr->w, ref_code_dev + s0,
+                           keep_mask_dev ? keep_mask_dev + s0 * 48 : nullptr, 1.0f / keep, (const uint8_t *)nullptr, 0.0f, nb, probs_dev + s0 * 4,
+                           gt_dev ? gt_dev + s0 * 2 : nullptr, tr->tact, tr->tdel, tr->df1, tr->loss);
+    }
+    NC_HIP(ctx, hipGetLastError());
+    return NC_OK;
+}
+
+int nc_train_loss_grad(nc_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                       float keep, const uint8_t *label_dev, float gamma, float *loss6_host, float *grad_dev)
+{
+    NC_TRY(check_call(tr, "nc_train_loss_grad", n, x_dev, ref_code_dev));
+    nc_ctx *ctx = tr->ctx;
+    if (!label_dev || !(keep > 0.0f && keep <= 1.0f)) return nc_fail(ctx, NC_ERR_ARG, "nc_train_loss_grad: bad argument");
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (keep == 1.0f) keep_mask_dev = nullptr;
+    tr->have_grad = tr->partial = false;
+    auto grid = [](int64_t npos) { const int64_t t = (npos + 63) / 64; return dim3((unsigned)(t < 2048 ? t : 2048)); };
+    for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
+        const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
+        const unsigned ns = (unsigned)((nb + SLAB - 1) / SLAB);
+        const float *x = x_dev + s0 * NC_SNP_TENSOR;
+        mark(tr, TS_FWD);
+        forward_trunk(tr, nb, x, scale_dev ? scale_dev + s0 : nullptr);
+        const float *xin = scale_dev ? tr->xs : x;
+        const int pitch = scale_dev ? XS : 1025;
+        mark(tr, TS_HEADS);
+        hipLaunchKernelGGL(k_heads, dim3(blocks_for(nb, 64)), dim3(64), 0, st, tr->f1, tr->f1d, tr->w, ref_code_dev + s0,
+                           keep_mask_dev ? keep_mask_dev + s0 * 48 : nullptr, 1.0f / keep, label_dev + s0 * 5, 1.0f / (float)n, nb, (float *)nullptr,
+                           (float *)nullptr, tr->tact, tr->tdel, tr->df1, tr->loss + s0 * 5);
+        hipLaunchKernelGGL(k_small_wgrad, dim3(ns, blocks_for(48 + NPAR - O_FA)), dim3(256), 0, st, tr->tact, tr->tdel, tr->df1, ref_code_dev + s0, nb, tr->slabs);
+        mark(tr, TS_FC1);
+        hipLaunchKernelGGL(k_fc1_wgrad, dim3(ns, 9), dim3(256), 0, st, tr->a3, tr->df1, nb, tr->slabs);
+        hipLaunchKernelGGL(k_fc1_dgrad, dim3(blocks_for(nb, 16)), dim3(256), 0, st, tr->w + O_KF, tr->df1, tr->a3, nb, tr->d3);
+        mark(tr, TS_CONV3);
+        hipLaunchKernelGGL((k_conv_wgrad<4, 20, 32, 64, 2>), dim3(ns, 6), dim3(256), 0, st, tr->a2, tr->d3, nb, (int)O_K3, tr->slabs);
+        hipLaunchKernelGGL((k_bias_grad<64, 27>), dim3(ns), dim3(256), 0, st, tr->d3, nb, (int)O_B3, tr->slabs);
+        hipLaunchKernelGGL((k_conv_dgrad<4, 20, 32, 64>), grid(nb * 80), dim3(256), 0, st, tr->d3, tr->w + O_K3, tr->a2, tr->d2, nb * 80);
+        mark(tr, TS_CONV2);
+        hipLaunchKernelGGL((k_conv_wgrad<5, 41, 48, 32, 3>), dim3(ns, 6), dim3(256), 0, st, tr->a1, tr->d2, nb, (int)O_K2, tr->slabs);
+        hipLaunchKernelGGL((k_bias_grad<32, 80>), dim3(ns), dim3(256), 0, st, tr->d2, nb, (int)O_B2, tr->slabs);
+        hipLaunchKernelGGL((k_conv_dgrad<5, 41, 48, 32>), grid(nb * 205), dim3(256), 0, st, tr->d2, tr->w + O_K2, tr->a1, tr->d1, nb * 205);
+        mark(tr, TS_CONV1);
+        hipLaunchKernelGGL(k_conv1_wgrad, dim3(ns, 6), dim3(256), 0, st, xin, pitch, tr->d1, nb, tr->slabs);
+        mark(tr, TS_PARAMS);
+        if (s0 + nb < n) {                                              // not the last slice: fold its slabs into g, the workspace is reused
+            hipLaunchKernelGGL(k_params, dim3(blocks_for(NPAR)), dim3(256), 0, st, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, (int)ns, 0, 0.0f,
+                               tr->g, 0, tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
+            tr->partial = true;
+        } else {
+            tr->pending_ns = (int)ns;
+            tr->pending_gamma = gamma;
+        }
+    }
+    if (grad_dev)
+        hipLaunchKernelGGL(k_params, dim3(blocks_for(NPAR)), dim3(256), 0, st, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, tr->pending_ns, 1, gamma,
+                           grad_dev, 0, tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
+    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, st, tr->loss, n, tr->w, gamma, tr->loss6);
+    mark(tr, TS_N);
+    NC_HIP(ctx, hipGetLastError());
+    tr->have_grad = true;
+    if (loss6_host) {
+        NC_HIP(ctx, hipMemcpyAsync(loss6_host, tr->loss6, 6 * 4, hipMemcpyDeviceToHost, st));
+        NC_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return NC_OK;
+}
+
+int nc_train_adam(nc_train *tr, float lr, float beta1, float beta2, float eps)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (!tr->have_grad) return nc_fail(ctx, NC_ERR_STATE, "nc_train_adam: no gradient (nc_train_loss_grad comes first, once per step)");
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    tr->t++;
+    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)tr->t)) / (1.0 - std::pow((double)beta1, (double)tr->t)));
+    hipLaunchKernelGGL(k_params, dim3(blocks_for(NPAR)), dim3(256), 0, ctx->stream, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, tr->pending_ns, 1,
+                       tr->pending_gamma, (float *)nullptr, 1, tr->w, tr->m, tr->v, lr_t, beta1, beta2, eps);
+    NC_HIP(ctx, hipGetLastError());
+    tr->have_grad = false;
+    return NC_OK;
+}
+
+int nc_train_info(nc_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps)
+{
+    if (!tr) return NC_ERR_ARG;
+    if (slice_sites) *slice_sites = tr->slice;
+    if (workspace_bytes) *workspace_bytes = (int64_t)tr->ws_bytes;
+    if (steps) *steps = tr->t;
+    return NC_OK;
+}
+
+int nc_train_stage_ms(nc_train *tr, int32_t on, float *ms7)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (ms7 && tr->timing) {
+        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < TS_N; i++) {
+            ms7[i] = 0.0f;
+            NC_HIP(ctx, hipEventElapsedTime(&ms7[i], tr->ev[i], tr->ev[i + 1]));
+        }
+    }
+    tr->timing = on;
+    return NC_OK;
+}
+
+}   // extern "C"
