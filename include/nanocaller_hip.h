@@ -1034,6 +1034,35 @@ int nc_train_adam(nc_train *tr, float lr, float beta1, float beta2, float eps);
 int nc_train_info(nc_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
 int nc_train_stage_ms(nc_train *tr, int32_t on, float *ms7);
 
+/* Training of the diploid indel model on the device (csrc/nc_train_indel.hip; nanocaller_amd/train_indel.py): what the
+ * reference's misc/training/model_run_indels.py + model_architect_indel.py do under TensorFlow 1.  The trained function is nc_indel_forward's
+ * for NC_MODEL_INDEL with dropout behind fc1's SELU (keep_mask_dev uint8 [n][32], 1 = kept, kept units times 1 / keep; keep == 1: no mask, the
+ * pointer may be NULL); cost = batch mean of the 4-way softmax cross-entropy + gamma * sum over the 8 kernels of |W|^2 / 2 (no bias).
+ * x_dev: float32 [n][15][128][2] as nc_indel_sites_run / nc_indel_tensor leave it; label_dev: uint8 [n], 0 no indel or 0/0, 1 = 1/1,
+ * 2 = 0/1, 3 = 1/2.  fp32 throughout; sums over sites in a fixed order (no atomics): the same bits on every run.  A handle belongs to one
+ * context, runs on the context's stream and is freed before it.  Only NC_MODEL_INDEL is accepted (NC_ERR_UNSUPPORTED otherwise).
+ *   nc_indel_train_create       n <= max_batch per call; a batch is processed in slices of slice_sites sites (765 KB of workspace each) whose
+ *                               gradients are accumulated in slice order; 0 = min(max_batch, 1024).
+ *   nc_indel_train_set_weights  canonical host blob (634,420 floats); zeroes m, v and the step count.
+ *   nc_indel_train_forward      probs_dev [n][4].
+ *   nc_indel_train_loss_grad    loss2_host (may be NULL; waits) = cost, cross-entropy; grad_dev (may be NULL) = the gradient blob, regulariser
+ *                               included.
+ *   nc_indel_train_adam         one step with the gradient of the last nc_indel_train_loss_grad, in TensorFlow's form (see nc_train_adam);
+ *                               NC_ERR_STATE without one.
+ *   nc_indel_train_info         sites per workspace slice, workspace bytes, steps taken (each may be NULL).
+ *   nc_indel_train_stage_ms     as nc_train_stage_ms: forward trunk, heads, fc1, conv3, conv2, conv1 gradients, parameters (of the last slice). */
+typedef struct nc_indel_train nc_indel_train;
+int nc_indel_train_create(nc_ctx *ctx, int32_t model_kind, int64_t max_batch, int64_t slice_sites, nc_indel_train **out);
+int nc_indel_train_free(nc_indel_train *tr);
+int nc_indel_train_set_weights(nc_indel_train *tr, const float *blob_host, size_t n_floats);
+int nc_indel_train_get_weights(nc_indel_train *tr, float *blob_host, size_t n_floats);
+int nc_indel_train_forward(nc_indel_train *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, float *probs_dev);
+int nc_indel_train_loss_grad(nc_indel_train *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, const uint8_t *label_dev,
+                             float gamma, float *loss2_host, float *grad_dev);
+int nc_indel_train_adam(nc_indel_train *tr, float lr, float beta1, float beta2, float eps);
+int nc_indel_train_info(nc_indel_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
+int nc_indel_train_stage_ms(nc_indel_train *tr, int32_t on, float *ms7);
+
 #ifdef __cplusplus
 }
 #endif

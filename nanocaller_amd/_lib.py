@@ -52,6 +52,8 @@ EXPORTS = [
     "nc_bamidx_candidates", "nc_bamidx_chain", "nc_bamidx_collect", "nc_bamidx_verify", "nc_bamidx_serial", "nc_bamidx_fields",
     "nc_train_create", "nc_train_free", "nc_train_set_weights", "nc_train_get_weights", "nc_train_forward", "nc_train_loss_grad", "nc_train_adam",
     "nc_train_info", "nc_train_stage_ms",
+    "nc_indel_train_create", "nc_indel_train_free", "nc_indel_train_set_weights", "nc_indel_train_get_weights", "nc_indel_train_forward",
+    "nc_indel_train_loss_grad", "nc_indel_train_adam", "nc_indel_train_info", "nc_indel_train_stage_ms",
 ]
 
 
@@ -304,6 +306,15 @@ def lib():
         L.nc_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
         L.nc_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.nc_train_stage_ms.argtypes = [vp, i32, vp]
+        L.nc_indel_train_create.argtypes = [vp, i32, i64, i64, C.POINTER(vp)]
+        L.nc_indel_train_free.argtypes = [vp]
+        L.nc_indel_train_set_weights.argtypes = [vp, vp, C.c_size_t]
+        L.nc_indel_train_get_weights.argtypes = [vp, vp, C.c_size_t]
+        L.nc_indel_train_forward.argtypes = [vp, i64, vp, vp, C.c_float, vp]
+        L.nc_indel_train_loss_grad.argtypes = [vp, i64, vp, vp, C.c_float, vp, C.c_float, vp, vp]
+        L.nc_indel_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
+        L.nc_indel_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.nc_indel_train_stage_ms.argtypes = [vp, i32, vp]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

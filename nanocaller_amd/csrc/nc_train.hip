@@ -4,7 +4,7 @@
 // softmax outputs, dropout sits behind fc1's SELU.  Everything is fp32 with fp32 accumulation; v_mfma_f32_16x16x4_f32 is bit for bit an fmaf chain.
 // lane l of an MFMA: A[row l&15][k l>>4], B[k l>>4][col l&15], C/D col l&15, row 4*(l>>4)+r (the lane maps of nc_cnn_fp32.hip).
 //
-//   forward     k_scale_x, k_conv1_fwd, k_conv23_fwd x 2 (k7_conv23_mfma's form), k_fc1_fwd (k3_fc1<48, 1>'s form), k_heads
+//   forward     k_scale_x, k_conv1_fwd, k_conv23_fwd x 2 (k7_conv23_mfma's form; nc_train.h), k_fc1_fwd (k3_fc1<48, 1>'s form), k_heads
 //   backward    k_heads (losses -> d fc1, one site per lane), k_small_wgrad (fc1 bias + the layers behind fc1),
 //               k_fc1_wgrad / k_fc1_dgrad, k_conv_wgrad / k_conv_dgrad x 2, k_bias_grad x 2, k_conv1_wgrad (all MFMA but the bias sums)
 //   parameters  k_loss_reduce (the six loss terms), k_params (slab sum + gamma w on kernel entries + Adam step)
@@ -12,7 +12,7 @@
 // Sums over sites run in a fixed order: a slab = the gradient of SLAB = 64 consecutive sites in blob order, written by one workgroup per
 // parameter range (the four waves of a workgroup combine through LDS in wave order); k_params adds the slabs in slab order.  No atomics.
 // Sites past n are never read: their operands enter every product as zeros.
-#include "nc_cnn.h"
+#include "nc_train.h"
 
 namespace {
 
@@ -28,13 +28,6 @@ constexpr int N1 = 205 * 48, N2 = 80 * 32, N3 = 27 * 64, XS = 1028;   // floats 
 constexpr int TA = 104, TA_FA = 48, TA_Z = 64, TA_P = 72, TA_FC2 = 80, TA_FC3 = 96;
 // ... and gradients at the pre-activations [fa 16 | head logits 8 | fc2 16 | fc3 8 | GT logits 2 | pad 2]
 constexpr int TD = 52, TD_H = 16, TD_FC2 = 24, TD_FC3 = 40, TD_GT = 48;
-
-__device__ __forceinline__ float selud(float y) { return y > 0.0f ? SELU_L : y + SELU_LA; }   // SELU' from SELU's output
-// SELU' from the pre-activation, for the dense layers (fc1, fa, fc2, fc3), whose units can sit at -lambda alpha on every site of a batch: there
-// y + lambda alpha cancels to rounding noise of 1e-7 where the derivative is 1e-6, the unit's bias gradient is that noise, and Adam's division by
-// sqrt(v) turns it into full-size steps (measured: five steps on ONT-HG002, fc1's bias off by 7.6e-4 against 9e-6 with this form).  192 bytes per
-// site for fc1; the other three are in registers anyway.  The convolutions, 99.7 % of the stored activations, take SELU' from the output.
-__device__ __forceinline__ float selud_pre(float x) { return x > 0.0f ? SELU_L : SELU_LA * expf(x); }
 
 __device__ __forceinline__ bool is_bias(int i)
 {
@@ -99,60 +92,6 @@ __global__ __launch_bounds__(256) void k_conv1_fwd(const float *__restrict__ x, 
     float4 *op = reinterpret_cast<float4 *>(a1 + g * 48);
 #pragma unroll
     for (int o = 0; o < 48; o += 4) op[o / 4] = make_float4(selu_acc(acc[o]), selu_acc(acc[o + 1]), selu_acc(acc[o + 2]), selu_acc(acc[o + 3]));
-}
-
-// conv2 / conv3 forward: k7_conv23_mfma of nc_cnn_fp32.hip (implicit GEMM, M = output positions, N = CO, K = 6 CI tap-major in groups of 16,
-// weights in LDS in fragment order) with the accurate exponential in the SELU.
-template <int HI, int WI, int CI, int CO>
-__global__ __launch_bounds__(256) void k_conv23_fwd(const float *__restrict__ in, const float *__restrict__ wk, const float *__restrict__ wb,
-                                                    float *__restrict__ out, int64_t npos)
-{
-    constexpr int HO = HI - 1, WO = (WI - 3) / 2 + 1, K = 6 * CI, NG = K / 16, TN = CO / 16;
-    static_assert(CI % 4 == 0 && K % 16 == 0 && CO % 16 == 0, "k_conv23_fwd: shape");
-    __shared__ float4 wf[NG][TN][64];
-    for (int idx = threadIdx.x; idx < NG * TN * 64; idx += 256) {
-        const int l = idx & 63, tn = (idx >> 6) % TN, G = (idx >> 6) / TN;
-        const int k0 = 16 * G + 4 * (l >> 4), col = tn * 16 + (l & 15);
-        wf[G][tn][l] = make_float4(wk[(k0 + 0) * CO + col], wk[(k0 + 1) * CO + col], wk[(k0 + 2) * CO + col], wk[(k0 + 3) * CO + col]);
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kq = lane >> 4, c16 = lane & 15;
-    const int64_t ntiles = (npos + 15) / 16;
-    float bias[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; tn++) bias[tn] = wb[tn * 16 + c16];
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wv; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
-        int64_t m = tile * 16 + c16;
-        if (m >= npos) m = npos - 1;
-        const int64_t site = m / (HO * WO);
-        const int r = (int)(m - site * (HO * WO));
-        const int y = r / WO, xq = r - y * WO;
-        const float *ip = in + ((site * HI + y) * WI + 2 * xq) * CI;
-        f32x4v acc[TN];
-#pragma unroll
-        for (int tn = 0; tn < TN; tn++) acc[tn] = (f32x4v){bias[tn], bias[tn], bias[tn], bias[tn]};
-#pragma unroll
-        for (int G = 0; G < NG; G++) {
-            const int k0 = 16 * G + 4 * kq, tap = k0 / CI, ci = k0 - tap * CI;
-            const float4 a = *reinterpret_cast<const float4 *>(ip + ((tap / 3) * WI + (tap % 3)) * CI + ci);
-#pragma unroll
-            for (int tn = 0; tn < TN; tn++) {
-                const float4 b = wf[G][tn][lane];
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[tn], 0, 0, 0);
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[tn], 0, 0, 0);
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[tn], 0, 0, 0);
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[tn], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-            const int64_t pos = tile * 16 + 4 * kq + rr;
-            if (pos < npos) {
-#pragma unroll
-                for (int tn = 0; tn < TN; tn++) out[pos * CO + tn * 16 + c16] = selu_acc(acc[tn][rr]);
-            }
-        }
-    }
 }
 
 // fc1 forward: k3_fc1<48, 1> of nc_cnn_fp32.hip (M = 16 sites, split-K over the four waves, combined through LDS) without its load pipeline.
@@ -430,145 +369,6 @@ __global__ __launch_bounds__(256) void k_fc1_dgrad(const float *__restrict__ wk,
             const float4 y = *reinterpret_cast<const float4 *>(a3 + o);
             *reinterpret_cast<float4 *>(d3 + o) = make_float4(acc[0] * selud(y.x), acc[1] * selud(y.y), acc[2] * selud(y.z), acc[3] * selud(y.w));
         }
-    }
-}
-
-// Weight gradient of a 2x3 stride-(1,2) valid convolution, dW[tap][ci][co] = sum over output positions of in[.. tap ..][ci] d[pos][co], of one
-// slab: M = (tap, ci) in tiles of 16 (a tile lies inside one tap), N = CO, K = output positions, four per MFMA.  grid (slabs, M tiles / MW):
-// the four waves of a workgroup take 16 sites of the slab each and combine through LDS in wave order.
-template <int HI, int WI, int CI, int CO, int MW>
-__global__ __launch_bounds__(256) void k_conv_wgrad(const float *__restrict__ in, const float *__restrict__ d, int64_t n, int koff, float *__restrict__ slabs)
-{
-    constexpr int HO = HI - 1, WO = (WI - 3) / 2 + 1, NPOS = HO * WO, TN = CO / 16;
-    static_assert(CI % 16 == 0 && CO % 16 == 0 && (6 * CI / 16) % MW == 0, "k_conv_wgrad: shape");
-    __shared__ float red[3][MW][TN][4][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = lane >> 4, c16 = lane & 15;
-    const int64_t p0 = ((int64_t)blockIdx.x * SLAB + 16 * wv) * NPOS, pend = n * NPOS;
-    int aoff[MW];
-#pragma unroll
-    for (int mw = 0; mw < MW; mw++) {
-        const int m0 = (blockIdx.y * MW + mw) * 16, tap = m0 / CI, ci = m0 - tap * CI;
-        aoff[mw] = ((tap / 3) * WI + (tap % 3)) * CI + ci + c16;
-    }
-    f32x4v acc[MW][TN];
-#pragma unroll
-    for (int mw = 0; mw < MW; mw++)
-#pragma unroll
-        for (int tn = 0; tn < TN; tn++) acc[mw][tn] = (f32x4v){0, 0, 0, 0};
-#pragma unroll 2
-    for (int st = 0; st < 4 * NPOS; st++) {
-        const int64_t p = p0 + 4 * st + q;
-        const bool ok = p < pend;
-        const int64_t site = p / NPOS;
-        const int r = (int)(p - site * NPOS), y = r / WO, x = r - y * WO;
-        const float *ip = in + ((site * HI + y) * WI + 2 * x) * CI;
-        float a[MW], b[TN];
-#pragma unroll
-        for (int mw = 0; mw < MW; mw++) a[mw] = ok ? ip[aoff[mw]] : 0.0f;
-#pragma unroll
-        for (int tn = 0; tn < TN; tn++) b[tn] = ok ? d[p * CO + tn * 16 + c16] : 0.0f;
-#pragma unroll
-        for (int mw = 0; mw < MW; mw++)
-#pragma unroll
-            for (int tn = 0; tn < TN; tn++) acc[mw][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mw], b[tn], acc[mw][tn], 0, 0, 0);
-    }
-    if (wv > 0) {
-#pragma unroll
-        for (int mw = 0; mw < MW; mw++)
-#pragma unroll
-            for (int tn = 0; tn < TN; tn++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) red[wv - 1][mw][tn][r][lane] = acc[mw][tn][r];
-    }
-    __syncthreads();
-    if (wv == 0) {
-        float *out = slabs + (int64_t)blockIdx.x * NPAR + koff;
-#pragma unroll
-        for (int mw = 0; mw < MW; mw++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int m = (blockIdx.y * MW + mw) * 16 + 4 * q + r;
-#pragma unroll
-                for (int tn = 0; tn < TN; tn++)
-                    out[m * CO + tn * 16 + c16] = ((acc[mw][tn][r] + red[0][mw][tn][r][lane]) + red[1][mw][tn][r][lane]) + red[2][mw][tn][r][lane];
-            }
-    }
-}
-
-// Data gradient of the same convolution (the transposed convolution), times SELU' of the layer below: M = input positions, N = CI,
-// K = (tap, co) in groups of 16; a tap that does not reach an output position from this input position enters as zeros.  The weights
-// sit in LDS in fragment order, transposed: wf[G][tn][lane] = W[tap][ci = 16 tn + (lane & 15)][co0 .. co0 + 3].
-template <int HI, int WI, int CI, int CO>
-__global__ __launch_bounds__(256) void k_conv_dgrad(const float *__restrict__ d, const float *__restrict__ wk, const float *__restrict__ act,
-                                                    float *__restrict__ out, int64_t npos)
-{
-    constexpr int HO = HI - 1, WO = (WI - 3) / 2 + 1, K = 6 * CO, NG = K / 16, TN = CI / 16;
-    static_assert(CI % 16 == 0 && CO % 16 == 0, "k_conv_dgrad: shape");
-    __shared__ float4 wf[NG][TN][64];
-    for (int idx = threadIdx.x; idx < NG * TN * 64; idx += 256) {
-        const int l = idx & 63, tn = (idx >> 6) % TN, G = (idx >> 6) / TN;
-        const int k0 = 16 * G + 4 * (l >> 4), tap = k0 / CO, co = k0 - tap * CO, ci = tn * 16 + (l & 15);
-        wf[G][tn][l] = *reinterpret_cast<const float4 *>(wk + (tap * CI + ci) * CO + co);
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kq = lane >> 4, c16 = lane & 15;
-    const int64_t ntiles = (npos + 15) / 16;
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wv; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
-        int64_t m = tile * 16 + c16;
-        if (m >= npos) m = npos - 1;
-        const int64_t site = m / (HI * WI);
-        const int r = (int)(m - site * (HI * WI)), yi = r / WI, xi = r - yi * WI;
-        const float *dp = d + site * (HO * WO * CO);
-        f32x4v acc[TN];
-#pragma unroll
-        for (int tn = 0; tn < TN; tn++) acc[tn] = (f32x4v){0, 0, 0, 0};
-#pragma unroll
-        for (int G = 0; G < NG; G++) {
-            const int tap = (16 * G) / CO, co = 16 * G - tap * CO + 4 * kq;
-            const int y = yi - tap / 3, xx = xi - tap % 3;
-            const bool ok = y >= 0 && y < HO && xx >= 0 && (xx & 1) == 0 && (xx >> 1) < WO;
-            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (ok) a = *reinterpret_cast<const float4 *>(dp + (y * WO + (xx >> 1)) * CO + co);
-#pragma unroll
-            for (int tn = 0; tn < TN; tn++) {
-                const float4 b = wf[G][tn][lane];
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[tn], 0, 0, 0);
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[tn], 0, 0, 0);
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[tn], 0, 0, 0);
-                acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[tn], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-            const int64_t pos = tile * 16 + 4 * kq + rr;
-            if (pos < npos) {
-#pragma unroll
-                for (int tn = 0; tn < TN; tn++) {
-                    const int64_t o = pos * CI + tn * 16 + c16;
-                    out[o] = acc[tn][rr] * selud(act[o]);
-                }
-            }
-        }
-    }
-}
-
-// bias gradient of a convolution, db[c] = sum over the slab's positions of d[pos][c]: 256 / C strided partial sums per channel,
-// combined in order
-template <int C, int NPOS>
-__global__ __launch_bounds__(256) void k_bias_grad(const float *__restrict__ d, int64_t n, int boff, float *__restrict__ slabs)
-{
-    constexpr int NP = 256 / C;
-    __shared__ float red[NP][C];
-    const int c = threadIdx.x % C, part = threadIdx.x / C;
-    const int64_t s0 = (int64_t)blockIdx.x * SLAB, s1 = s0 + SLAB < n ? s0 + SLAB : n;
-    float acc = 0.0f;
-    for (int64_t p = s0 * NPOS + part; p < s1 * NPOS; p += NP) acc += d[p * C + c];
-    red[part][c] = acc;
-    __syncthreads();
-    if (part == 0) {
-        float v = red[0][c];
-        for (int k = 1; k < NP; k++) v += red[k][c];
-        slabs[(int64_t)blockIdx.x * NPAR + boff + c] = v;
     }
 }
 
@@ -866,12 +666,12 @@ int nc_train_loss_grad(nc_train *tr, int64_t n, const float *x_dev, const int32_
         hipLaunchKernelGGL(k_fc1_wgrad, dim3(ns, 9), dim3(256), 0, st, tr->a3, tr->df1, nb, tr->slabs);
         hipLaunchKernelGGL(k_fc1_dgrad, dim3(blocks_for(nb, 16)), dim3(256), 0, st, tr->w + O_KF, tr->df1, tr->a3, nb, tr->d3);
         mark(tr, TS_CONV3);
-        hipLaunchKernelGGL((k_conv_wgrad<4, 20, 32, 64, 2>), dim3(ns, 6), dim3(256), 0, st, tr->a2, tr->d3, nb, (int)O_K3, tr->slabs);
-        hipLaunchKernelGGL((k_bias_grad<64, 27>), dim3(ns), dim3(256), 0, st, tr->d3, nb, (int)O_B3, tr->slabs);
+        hipLaunchKernelGGL((k_conv_wgrad<4, 20, 32, 64, 2, SLAB, NPAR>), dim3(ns, 6), dim3(256), 0, st, tr->a2, tr->d3, nb, (int)O_K3, tr->slabs);
+        hipLaunchKernelGGL((k_bias_grad<64, 27, SLAB, NPAR>), dim3(ns), dim3(256), 0, st, tr->d3, nb, (int)O_B3, tr->slabs);
         hipLaunchKernelGGL((k_conv_dgrad<4, 20, 32, 64>), grid(nb * 80), dim3(256), 0, st, tr->d3, tr->w + O_K3, tr->a2, tr->d2, nb * 80);
         mark(tr, TS_CONV2);
-        hipLaunchKernelGGL((k_conv_wgrad<5, 41, 48, 32, 3>), dim3(ns, 6), dim3(256), 0, st, tr->a1, tr->d2, nb, (int)O_K2, tr->slabs);
-        hipLaunchKernelGGL((k_bias_grad<32, 80>), dim3(ns), dim3(256), 0, st, tr->d2, nb, (int)O_B2, tr->slabs);
+        hipLaunchKernelGGL((k_conv_wgrad<5, 41, 48, 32, 3, SLAB, NPAR>), dim3(ns, 6), dim3(256), 0, st, tr->a1, tr->d2, nb, (int)O_K2, tr->slabs);
+        hipLaunchKernelGGL((k_bias_grad<32, 80, SLAB, NPAR>), dim3(ns), dim3(256), 0, st, tr->d2, nb, (int)O_B2, tr->slabs);
         hipLaunchKernelGGL((k_conv_dgrad<5, 41, 48, 32>), grid(nb * 205), dim3(256), 0, st, tr->d2, tr->w + O_K2, tr->a1, tr->d1, nb * 205);
         mark(tr, TS_CONV1);
         hipLaunchKernelGGL(k_conv1_wgrad, dim3(ns, 6), dim3(256), 0, st, xin, pitch, tr->d1, nb, tr->slabs);

@@ -225,6 +225,7 @@ def add_indels(world: World, seed: int = SEED, het_rate: float = 1 / 1500.0, noi
         for p, ln in e:
             deco[(r, p - 1)] = ("+%d%s" % (ln, "ACGT"[p % 4] * ln)) if ln > 0 else ("-%d%s" % (-ln, "N" * (-ln)))
     world.meta["events"] = (ev_off, ev_pos, ev_len)
+    world.meta["indel_sites"] = (sites.astype(np.int64), site_len.astype(np.int64))     # the planted heterozygous events: column, signed length
     world.meta["hap"] = hp
     world.meta["ps"] = ps
     world.meta["deco"] = deco
