@@ -1063,6 +1063,57 @@ int nc_indel_train_adam(nc_indel_train *tr, float lr, float beta1, float beta2, 
 int nc_indel_train_info(nc_indel_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
 int nc_indel_train_stage_ms(nc_indel_train *tr, int32_t on, float *ms7);
 
+/* Training of the haploid SNP model on the device (csrc/nc_train_hap.hip; nanocaller_amd/train_haploid.py).  The trained
+ * function is nc_snp_forward's for NC_MODEL_SNP_HAP: the diploid SNP model's trunk through fc1, dropout behind fc1's SELU (keep_mask_dev as in
+ * nc_train_forward), fc2, fc3 on [fc2 | reference one-hot] with its SELU, softmax.  cost = batch mean of the 4-way softmax cross-entropy +
+ * gamma * sum over the 8 kernels of |W|^2 / 2 (no bias); label_dev: uint8 [n], the site's base A0 G1 T2 C3.  x_dev, ref_code_dev, scale_dev as in
+ * nc_train_forward.  fp32 throughout; sums over sites in a fixed order (no atomics): the same bits on every run.  A handle belongs to one
+ * context, runs on the context's stream and is freed before it.  Only NC_MODEL_SNP_HAP is accepted (NC_ERR_UNSUPPORTED otherwise, before any
+ * allocation); nc_train_create goes on refusing it.
+ *   nc_hap_train_set_weights  canonical host blob (108,308 floats); zeroes m, v and the step count.
+ *   nc_hap_train_forward      probs_dev [n][4] = the probabilities of A, G, T, C.
+ *   nc_hap_train_loss_grad    waits.  loss2_host (may be NULL) = cost, cross-entropy; grad_dev (may be NULL) = the gradient blob, regulariser
+ *                             included.  n <= max_batch (NC_ERR_ARG otherwise); batches above the workspace's slice are accumulated slice by
+ *                             slice.  A label above 3: NC_ERR_ARG, and no gradient is left for nc_hap_train_adam.
+ *   nc_hap_train_adam         one step with the gradient of the last nc_hap_train_loss_grad, in TensorFlow's form (see nc_train_adam);
+ *                             NC_ERR_STATE without one.
+ *   nc_hap_train_info         sites per workspace slice, workspace bytes, steps taken (each may be NULL).
+ *   nc_hap_train_stage_ms     as nc_train_stage_ms: forward trunk, heads, fc1, conv3, conv2, conv1 gradients, parameters (of the last slice). */
+typedef struct nc_hap_train nc_hap_train;
+int nc_hap_train_create(nc_ctx *ctx, int32_t model_kind, int64_t max_batch, nc_hap_train **out);
+int nc_hap_train_free(nc_hap_train *tr);
+int nc_hap_train_set_weights(nc_hap_train *tr, const float *blob_host, size_t n_floats);
+int nc_hap_train_get_weights(nc_hap_train *tr, float *blob_host, size_t n_floats);
+int nc_hap_train_forward(nc_hap_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                         float keep, float *probs_dev);
+int nc_hap_train_loss_grad(nc_hap_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                           float keep, const uint8_t *label_dev, float gamma, float *loss2_host, float *grad_dev);
+int nc_hap_train_adam(nc_hap_train *tr, float lr, float beta1, float beta2, float eps);
+int nc_hap_train_info(nc_hap_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
+int nc_hap_train_stage_ms(nc_hap_train *tr, int32_t on, float *ms7);
+
+/* Training of the haploid indel model on the device (csrc/nc_train_hap_indel.hip, csrc/nc_train_indel.h; nanocaller_amd/train_haploid.py; DESIGN.md
+ * section 19).  The trained function is nc_indel_forward's for NC_MODEL_INDEL_HAP ([5][128][2] -> ... -> fc3 24 -> 1 -> sigmoid) with dropout
+ * behind fc1's SELU (keep_mask_dev uint8 [n][32] as in nc_indel_train_forward); cost = batch mean of the binary cross-entropy, taken from the
+ * logit (softplus(z) - y z), + gamma * sum over the 8 kernels of |W|^2 / 2 (no bias).  x_dev: float32 [n][5][128][2] as the haploid pipeline
+ * leaves it; label_dev: uint8 [n], 1 = the site holds an indel, 0 = it does not; probs_dev: float32 [n].  The same set of calls, arguments,
+ * fixed-order sums and slices as the nc_indel_train_* family (a slice of slice_sites sites takes 228 KB of workspace per site; 0 =
+ * min(max_batch, 1024)).  Only NC_MODEL_INDEL_HAP is accepted (NC_ERR_UNSUPPORTED otherwise, before any allocation); nc_indel_train_create
+ * goes on refusing it.  n > max_batch, keep outside (0, 1] and a label above 1 are NC_ERR_ARG; the labels live on the device, so
+ * nc_hap_indel_train_loss_grad always waits, and after a refused label no gradient is pending.  nc_hap_indel_train_adam without a pending
+ * gradient: NC_ERR_STATE. */
+typedef struct nc_hap_indel_train nc_hap_indel_train;
+int nc_hap_indel_train_create(nc_ctx *ctx, int32_t model_kind, int64_t max_batch, int64_t slice_sites, nc_hap_indel_train **out);
+int nc_hap_indel_train_free(nc_hap_indel_train *tr);
+int nc_hap_indel_train_set_weights(nc_hap_indel_train *tr, const float *blob_host, size_t n_floats);
+int nc_hap_indel_train_get_weights(nc_hap_indel_train *tr, float *blob_host, size_t n_floats);
+int nc_hap_indel_train_forward(nc_hap_indel_train *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, float *probs_dev);
+int nc_hap_indel_train_loss_grad(nc_hap_indel_train *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, const uint8_t *label_dev,
+                                 float gamma, float *loss2_host, float *grad_dev);
+int nc_hap_indel_train_adam(nc_hap_indel_train *tr, float lr, float beta1, float beta2, float eps);
+int nc_hap_indel_train_info(nc_hap_indel_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
+int nc_hap_indel_train_stage_ms(nc_hap_indel_train *tr, int32_t on, float *ms7);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,10 @@ EXPORTS = [
     "nc_train_info", "nc_train_stage_ms",
     "nc_indel_train_create", "nc_indel_train_free", "nc_indel_train_set_weights", "nc_indel_train_get_weights", "nc_indel_train_forward",
     "nc_indel_train_loss_grad", "nc_indel_train_adam", "nc_indel_train_info", "nc_indel_train_stage_ms",
+    "nc_hap_train_create", "nc_hap_train_free", "nc_hap_train_set_weights", "nc_hap_train_get_weights", "nc_hap_train_forward",
+    "nc_hap_train_loss_grad", "nc_hap_train_adam", "nc_hap_train_info", "nc_hap_train_stage_ms",
+    "nc_hap_indel_train_create", "nc_hap_indel_train_free", "nc_hap_indel_train_set_weights", "nc_hap_indel_train_get_weights",
+    "nc_hap_indel_train_forward", "nc_hap_indel_train_loss_grad", "nc_hap_indel_train_adam", "nc_hap_indel_train_info", "nc_hap_indel_train_stage_ms",
 ]
 
 
@@ -315,6 +319,18 @@ def lib():
         L.nc_indel_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
         L.nc_indel_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.nc_indel_train_stage_ms.argtypes = [vp, i32, vp]
+        L.nc_hap_train_create.argtypes = [vp, i32, i64, C.POINTER(vp)]
+        L.nc_hap_train_free.argtypes = [vp]
+        L.nc_hap_train_set_weights.argtypes = [vp, vp, C.c_size_t]
+        L.nc_hap_train_get_weights.argtypes = [vp, vp, C.c_size_t]
+        L.nc_hap_train_forward.argtypes = [vp, i64, vp, vp, vp, vp, C.c_float, vp]
+        L.nc_hap_train_loss_grad.argtypes = [vp, i64, vp, vp, vp, vp, C.c_float, vp, C.c_float, vp, vp]
+        L.nc_hap_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
+        L.nc_hap_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.nc_hap_train_stage_ms.argtypes = [vp, i32, vp]
+        for fam in ("nc_hap_indel_train",):                             # the nc_indel_train_* family's signatures
+            for fn in ("create", "free", "set_weights", "get_weights", "forward", "loss_grad", "adam", "info", "stage_ms"):
+                getattr(L, "%s_%s" % (fam, fn)).argtypes = getattr(L, "nc_indel_train_" + fn).argtypes
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

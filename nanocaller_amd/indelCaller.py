@@ -19,9 +19,11 @@ from __future__ import annotations
 
 import numpy as np
 
-from .weights import get_indel_model  # noqa: F401  (same name as indelCaller.py:26)
+from .weights import get_haploid_indel_model, get_indel_model  # noqa: F401  (same name as indelCaller.py:26)
 
 # keys of the `params` dict this module and the indel featurisers read (all of them are in the dict NanoCaller:45-53 builds)
+# (opt-in keys of this project that the reference's dict does not have are read with .get and are not listed here: 'genotype_indel_sites',
+# 'genotype_indel_only', 'haploid_indel_model' -- 'haploid' or an .ncw of kind KIND_INDEL_HAP, weights.get_haploid_indel_model)
 PARAM_KEYS = frozenset(['chunks_list', 'mode', 'snp_vcf', 'regions_list', 'sam_path', 'fasta_path', 'mincov', 'maxcov', 'indel_model',
                         'vcf_path', 'prefix', 'sample', 'seq', 'del_t', 'ins_t', 'impute_indel_phase', 'supplementary', 'exclude_bed',
                         'win_size', 'small_win_size', 'enable_whatshap', 'suppress_progress', 'phase_qual_score', 'verbose'])
@@ -181,7 +183,7 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
     eng = get_engine(device)
     eng.use_torch_stream()
     eng.load_weights(_lib.MODEL_INDEL, Weights(model_path))
-    eng.load_weights(_lib.MODEL_INDEL_HAP, Weights(get_indel_model('haploid')))
+    eng.load_weights(_lib.MODEL_INDEL_HAP, Weights(get_haploid_indel_model(params)))   # the shipped file or params['haploid_indel_model']
     batch_size = 100
 
     def forward(ploidy, tuples):

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .engine import get_engine
 from .generate_SNP_pileups import device_pack_for, release_contig
-from .weights import Weights, get_SNP_model  # noqa: F401  (re-exported, same name as the reference)
+from .weights import Weights, get_haploid_SNP_model, get_SNP_model  # noqa: F401  (re-exported, same name as the reference)
 
 num_to_base_map = {0: 'A', 1: 'G', 2: 'T', 3: 'C'}                 # snpCaller.py:14
 _B = "AGTC"
@@ -165,6 +165,8 @@ VCF_HEADER = (                                                      # snpCaller.
 
 
 # keys of the `params` dict this module reads (all of them are in the dict NanoCaller:28-35 builds)
+# (opt-in keys of this project that the reference's dict does not have are read with .get and are not listed: 'genotype_sites',
+# 'genotype_only', 'haploid_snp_model'; tests/test_boundary.py holds this set to the reference's keys)
 PARAM_KEYS = frozenset(['chunks_list', 'regions_list', 'sam_path', 'fasta_path', 'mincov', 'maxcov', 'min_allele_freq', 'min_nbr_sites',
                         'threshold', 'snp_model', 'vcf_path', 'prefix', 'sample', 'seq', 'supplementary', 'exclude_bed',
                         'suppress_progress', 'disable_coverage_normalization'])
@@ -197,6 +199,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     -> dict of host arrays (pos, chunk, ref, probs, gt, dp, freq, fwd_dp, rev_dp, chunk_depth).
     params['genotype_sites'] / params['genotype_only'] (genotype_sites.py; both optional): positions to genotype whatever their allele
     frequency; the result then counts them: genotype_listed = listed positions inside these chunks, genotype_emitted = those with a record.
+    params['haploid_snp_model'] (optional; else NC_HAPLOID_SNP_MODEL): 'haploid' or an .ncw of kind KIND_SNP_HAP for haploid chunks; a file brings
+    its own train_coverage for the coverage scale (weights.get_haploid_SNP_model; a missing file or another kind raises).
     defer=True -> PendingCall: returns once the group's work is handed over; the caller starts the next group and collects result() afterwards.
     pipeline: None or False.  True asked for a removed path (a group's CNN enqueued inside the next call's scan; measured slower, 10.55 ->
     11.2 ms per contig: profiles/README.md, round 6) and raises."""
@@ -214,8 +218,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
             sys.exit(1)
         kind = _lib.MODEL_SNP
     else:
-        path, _ = get_SNP_model('haploid')
-        train_cov = 30                                              # hap_train_coverage, snpCaller.py:73
+        # the shipped CHM13 model with hap_train_coverage = 30 (snpCaller.py:73) unless params['haploid_snp_model'] names a trained file
+        path, train_cov = get_haploid_SNP_model(params)
         kind = _lib.MODEL_SNP_HAP
     eng.load_weights(kind, _weights(path))
     if dpk is None:

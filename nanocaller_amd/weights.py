@@ -142,6 +142,39 @@ def get_indel_model(indel_model):
     return None
 
 
+HAP_TRAIN_COVERAGE = 30                                     # hap_train_coverage of the shipped CHM13 model, snpCaller.py:73
+
+
+def _haploid_model(params, key, env, kind, builtin):
+    """params[key], else the environment variable `env` -> (path, Weights or None): the built-in name 'haploid' (or no key at all: Weights is
+    None then) gives the shipped file, anything else must be an existing .ncw of `kind`.  A given key is never ignored: it resolves or raises."""
+    val = params.get(key) if params is not None and params.get(key) is not None else os.environ.get(env)
+    if val is None or val == "":
+        return builtin, None
+    if val == "haploid":
+        return builtin, None
+    if not isinstance(val, str) or not val.endswith(".ncw"):
+        raise ValueError("%s = %r: expected 'haploid' or a path to an .ncw file" % (key, val))
+    if not os.path.exists(val):
+        raise FileNotFoundError("%s = %r: no such file" % (key, val))
+    w = Weights(val)
+    if w.kind != kind:
+        raise ValueError("%s = %r holds a model of kind %d, expected kind %d" % (key, val, w.kind, kind))
+    return val, w
+
+
+def get_haploid_SNP_model(params=None):
+    """The model of haploid contigs' SNP calls: params['haploid_snp_model'] / NC_HAPLOID_SNP_MODEL -> (path, train_coverage).  Absent or
+    'haploid': the shipped CHM13 file with the constant 30; a file: its own train_coverage."""
+    path, w = _haploid_model(params, "haploid_snp_model", "NC_HAPLOID_SNP_MODEL", KIND_SNP_HAP, os.path.join(WEIGHT_DIR, SNP_MODEL_FILES["haploid"]))
+    return path, (HAP_TRAIN_COVERAGE if w is None else float(w.train_coverage))
+
+
+def get_haploid_indel_model(params=None):
+    """params['haploid_indel_model'] / NC_HAPLOID_INDEL_MODEL -> path of the haploid indel model (absent or 'haploid': the shipped file)"""
+    return _haploid_model(params, "haploid_indel_model", "NC_HAPLOID_INDEL_MODEL", KIND_INDEL_HAP, os.path.join(WEIGHT_DIR, INDEL_MODEL_FILES["haploid"]))[0]
+
+
 def resolve_weight_file(path, kind):
     """What the model classes' load_weights() accepts: an .ncw file, or a path in the reference's layout -- a TF checkpoint
     prefix `.../release_data/<family>_models/<SNPs|indels>/<dir>/<model-N>` (snpCaller.py:16-34, indelCaller.py:17-24) or a
