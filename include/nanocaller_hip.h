@@ -426,6 +426,24 @@ int nc_indel_set_mates(nc_ctx *ctx, int32_t n_mates, const int64_t *d_mate_key, 
  * grid from the list on the context's stream (one bit per column); the list itself must stay valid until the scan's kernels have run. */
 int nc_snp_scan_set_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, int32_t only);
 
+/* Neighbour sites given as a list (known heterozygous sites: a first pass, a parent, a panel, a training truth; ABI 11: an added export).  d_pos as
+ * for nc_snp_scan_set_sites: 1-based positions on the device, any order, duplicates allowed, borrowed, read by the following nc_snp_scan /
+ * nc_snp_scan_begin calls (n_sites = 0 clears the list), positions outside the pack's tile grid ignored.  The neighbour test of
+ * generate_SNP_pileups.py:173 / :177 becomes `frequency rule or v_pos in list` (only = 0) or `v_pos in list` (only != 0), for the diploid and the
+ * haploid rule alike; the tests of :161,170 stay.  A listed neighbour is no candidate because of it, and a position of nc_snp_scan_set_sites is no
+ * neighbour because of that list: the two lists are independent and may both be set.  nc_snp_featurize's min_nbr_sites keeps the reference's
+ * meaning (:244, the site's own column counted); a caller that wants it to count the listed neighbours alone in only mode, as the Python engine
+ * does, passes one more. */
+int nc_snp_scan_set_nbr_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, int32_t only);
+
+/* Background sampling (ABI 11: an added export): a column that passes the tests of :161,170 and fails the candidate test of :183 (the list of
+ * nc_snp_scan_set_sites included) is a candidate all the same when mix(p, seed) < keep6[b], b = min(5, (20 * alt) / n) in integer division (the
+ * 5 % bins of its alternative allele frequency; 0 = never), with the 32-bit function of the 1-based position p
+ *   x = (uint32)p * 0x9E3779B1 ^ seed;  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16.
+ * keep6_host: six thresholds in host memory, copied by this call (NULL clears the table); read by the following nc_snp_scan / nc_snp_scan_begin
+ * calls.  The decision depends on the position alone, not on the pack's tile size. */
+int nc_snp_scan_set_sampling(nc_ctx *ctx, uint32_t seed, const uint32_t *keep6_host);
+
 /* Per-site coverage scale (snpCaller.py:93-96, 170-173) for the sites of the last scan:
  * mode 0: scale[s] = train_coverage / mean(site_depth over the site's chunk) (chunk constant, quirk E2)
  * mode 1: scale[s] = train_coverage / dp[s] (--disable_coverage_normalization).

@@ -74,6 +74,15 @@ struct nc_ctx {
     const int32_t *gsite_pos = nullptr;
     bool gsites_only = false;
     DevBuf site_bits;                       // one bit per column of the scanned pack's tile grid (k_site_bits)
+    // neighbour sites given as a list (nc_snp_scan_set_nbr_sites): the same contract, bitmap nbr_bits; background sampling of the columns under the
+    // candidate threshold (nc_snp_scan_set_sampling): the seed and the six thresholds, copied when set.  Either one selects k_scan_ext.
+    int32_t n_nsites = 0;
+    const int32_t *nsite_pos = nullptr;
+    bool nsites_only = false;
+    DevBuf nbr_bits;
+    bool sample_on = false;
+    uint32_t sample_seed = 0;
+    uint32_t sample_keep[6] = {0, 0, 0, 0, 0, 0};
     // indel columns to genotype (nc_indel_set_sites): borrowed device pointers, read by the next nc_indel_sites_plan calls
     int32_t n_isites = 0;
     const int32_t *isite_pos = nullptr;

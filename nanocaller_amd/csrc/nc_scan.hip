@@ -25,16 +25,39 @@ struct ScanP {
     int32_t scan_lo, scan_hi;
 };
 
+// What the opt-in form of the scan reads beside ScanP (nc_snp_scan_set_nbr_sites, nc_snp_scan_set_sampling)
+struct ScanX {
+    int32_t sample;                // background sampling is on
+    uint32_t seed;
+    uint32_t keep[6];              // per allele-frequency bin: a column is kept when mix(p, seed) < keep[bin]; 0 = never
+};
+
+// the 32-bit mixer of background sampling: a function of the 1-based position and the seed alone
+__device__ __forceinline__ uint32_t mix32(int32_t p, uint32_t seed)
+{
+    uint32_t x = ((uint32_t)p * 0x9E3779B1u) ^ seed;
+    x ^= x >> 16; x *= 0x85EBCA6Bu;
+    x ^= x >> 13; x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
 // SITES: a list of positions to genotype is set (nc_snp_scan_set_sites): site_bits holds one bit per column of the pack's tile grid (bit g = column
 // tile_pos0 + g, k_site_bits), a lane reads the 16 bits of its 16 positions as one aligned 16-bit load, and a listed column that passes every other
 // test of :161-170 is a candidate whatever its allele frequency.  The <.., false> form never reads site_bits and is the kernel of the plain scan.
-template <int BLOCK, bool SITES>
+// EXT: a list of neighbour sites and / or a sampling table is set (nc_snp_scan_set_nbr_sites, nc_snp_scan_set_sampling); the form is launched as
+// <.., false, true>.  site_bits and nbr_bits are each NULL or a bitmap as above: a column listed in nbr_bits that passes the tests of :161-170 is a
+// neighbour whatever its allele frequency (only mode: the host hands t0 = 2, the frequency rule never fires) and is no candidate because of it; a
+// column that fails the candidate test is a candidate all the same when mix32(p, seed) < keep[min(5, 20 * alt / n)].  The <.., false> forms read
+// neither nbr_bits nor sx: they are the kernels they were before EXT existed (tools/isa_diff.py --ignore-kernarg-size).
+template <int BLOCK, bool SITES, bool EXT>
 __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ codes, const int32_t *__restrict__ tile_off,
                                                 const nc_tile_entry *__restrict__ tile_ent, int32_t tile_pos0,
                                                 const uint8_t *__restrict__ ref_code, ScanP sp,
                                                 int32_t *__restrict__ stage_nbr, int32_t *__restrict__ stage_cpos,
                                                 int32_t *__restrict__ stage_cn, int32_t *__restrict__ stage_calt,
-                                                int2 *__restrict__ tile_cnt, const uint16_t *__restrict__ site_bits)
+                                                int2 *__restrict__ tile_cnt, const uint16_t *__restrict__ site_bits,
+                                                const uint16_t *__restrict__ nbr_bits, ScanX sx)
 {
     constexpr int TILE = BLOCK * 16;
     const int t = blockIdx.x;
@@ -82,8 +105,12 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ code
     const uint4 rv = *reinterpret_cast<const uint4 *>(ref_code + (int64_t)t * TILE + threadIdx.x * 16);
     const uint32_t rw[4] = {rv.x, rv.y, rv.z, rv.w};
     uint32_t nbr_mask = 0, cand_mask = 0;
-    uint32_t listed = 0;
+    uint32_t listed = 0, listed_nbr = 0;
     if constexpr (SITES) listed = site_bits[(int64_t)t * BLOCK + threadIdx.x];
+    if constexpr (EXT) {
+        if (site_bits) listed = site_bits[(int64_t)t * BLOCK + threadIdx.x];
+        if (nbr_bits) listed_nbr = nbr_bits[(int64_t)t * BLOCK + threadIdx.x];
+    }
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const int d = i >> 2, k = i & 3;
@@ -100,8 +127,25 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const uint8_t *__restrict__ code
             }
             const double f = (double)alt / (double)n;                 // alt_freq, float64 (:166)
             const bool nb = sp.haploid ? (sp.t0 <= f) : (sp.t0 <= f && f < sp.t1);   // :173 / :177
-            if (nb) nbr_mask |= 1u << i;
-            if (sp.min_af <= f || (SITES && ((listed >> i) & 1))) cand_mask |= 1u << i;   // :183 (chunk membership applied later)
+            if constexpr (!EXT) {
+                if (nb) nbr_mask |= 1u << i;
+                if (sp.min_af <= f || (SITES && ((listed >> i) & 1))) cand_mask |= 1u << i;   // :183 (chunk membership applied later)
+            } else {
+                if (nb || ((listed_nbr >> i) & 1)) nbr_mask |= 1u << i;
+                bool cd = sp.min_af <= f || ((listed >> i) & 1);
+                if (!cd && sx.sample) {
+                    // bin = min(5, 20 * alt / n) without the division: how many of n, 2n, .. 5n are <= 20 * alt
+                    const uint32_t a20 = 20u * alt;
+                    uint32_t thr = sx.keep[0];
+                    if (a20 >= n) thr = sx.keep[1];
+                    if (a20 >= 2 * n) thr = sx.keep[2];
+                    if (a20 >= 3 * n) thr = sx.keep[3];
+                    if (a20 >= 4 * n) thr = sx.keep[4];
+                    if (a20 >= 5 * n) thr = sx.keep[5];
+                    cd = mix32(p, sx.seed) < thr;
+                }
+                if (cd) cand_mask |= 1u << i;
+            }
         }
     }
 
@@ -333,24 +377,35 @@ int nc_selftest_device(nc_ctx *ctx)
     return NC_OK;
 }
 
-template <bool SITES>
-static void launch_scan(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_code_dev, const ScanP &sp)
+// SITES / EXT: the kernel's form.  sb / nb: the candidate and the neighbour bitmap, each NULL when its list is not set (the plain and the SITES form
+// read neither nb nor sx)
+template <bool SITES, bool EXT>
+static void launch_scan(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_code_dev, const ScanP &sp, const uint16_t *sb, const uint16_t *nb,
+                        const ScanX &sx)
 {
     auto *sn = (int32_t *)ctx->stage_nbr.p;
     auto *sc = (int32_t *)ctx->stage_cpos.p;
     auto *scn = (int32_t *)ctx->stage_cn.p;
     auto *sca = (int32_t *)ctx->stage_calt.p;
     auto *tc = (int2 *)ctx->tile_cnt.p;
-    const auto *sb = SITES ? (const uint16_t *)ctx->site_bits.p : nullptr;
     if (pack->tile_size == 1024)
-        hipLaunchKernelGGL((k_scan<64, SITES>), dim3(pack->n_tiles), dim3(64), 0, ctx->stream, pack->codes, pack->tile_off,
-                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb);
+        hipLaunchKernelGGL((k_scan<64, SITES, EXT>), dim3(pack->n_tiles), dim3(64), 0, ctx->stream, pack->codes, pack->tile_off,
+                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb, nb, sx);
     else if (pack->tile_size == 2048)
-        hipLaunchKernelGGL((k_scan<128, SITES>), dim3(pack->n_tiles), dim3(128), 0, ctx->stream, pack->codes, pack->tile_off,
-                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb);
+        hipLaunchKernelGGL((k_scan<128, SITES, EXT>), dim3(pack->n_tiles), dim3(128), 0, ctx->stream, pack->codes, pack->tile_off,
+                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb, nb, sx);
     else
-        hipLaunchKernelGGL((k_scan<256, SITES>), dim3(pack->n_tiles), dim3(256), 0, ctx->stream, pack->codes, pack->tile_off,
-                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb);
+        hipLaunchKernelGGL((k_scan<256, SITES, EXT>), dim3(pack->n_tiles), dim3(256), 0, ctx->stream, pack->codes, pack->tile_off,
+                           pack->tile_ent, pack->tile_pos0, ref_code_dev, sp, sn, sc, scn, sca, tc, sb, nb, sx);
+}
+
+// a position list as a zeroed bitmap on the pack's tile grid (npos columns, a multiple of 1024: whole 32-bit words)
+static int build_bits(nc_ctx *ctx, DevBuf &bits, int32_t n, const int32_t *d_pos, int32_t tile_pos0, int64_t npos)
+{
+    NC_HIP(ctx, hipMemsetAsync(bits.p, 0, (size_t)(npos / 8), ctx->stream));
+    hipLaunchKernelGGL(k_site_bits, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d_pos, tile_pos0, npos, (uint32_t *)bits.p);
+    NC_HIP(ctx, hipGetLastError());
+    return NC_OK;
 }
 
 extern "C" {
@@ -422,21 +477,29 @@ int nc_snp_scan_begin(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_c
     sp.scan_hi = scan_hi;
 
     const bool listed = ctx->n_gsites > 0;
+    const bool listed_nbr = ctx->n_nsites > 0;
+    const bool ext = listed_nbr || ctx->sample_on;                   // a neighbour list or a sampling table: the opt-in form of the kernel
     if (listed) {
         NC_TRY(nc_ensure(ctx, ctx->site_bits, (size_t)(npos / 8)));  // (npos is a multiple of 1024: whole 32-bit words)
         if (ctx->gsites_only) sp.min_af = 2.0;                       // alt <= n: the frequency test of :183 never fires, the list alone decides
     }
+    if (listed_nbr) {
+        NC_TRY(nc_ensure(ctx, ctx->nbr_bits, (size_t)(npos / 8)));
+        if (ctx->nsites_only) sp.t0 = 2.0;                           // the same for the neighbour rule of :173 / :177
+    }
     NcTimer tm(ctx, 0);
     auto *tc = (int2 *)ctx->tile_cnt.p;
-    if (listed) {
-        NC_HIP(ctx, hipMemsetAsync(ctx->site_bits.p, 0, (size_t)(npos / 8), ctx->stream));
-        hipLaunchKernelGGL(k_site_bits, dim3((ctx->n_gsites + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_gsites, ctx->gsite_pos,
-                           pack->tile_pos0, npos, (uint32_t *)ctx->site_bits.p);
-        NC_HIP(ctx, hipGetLastError());
-        launch_scan<true>(ctx, pack, ref_code_dev, sp);
-    } else {
-        launch_scan<false>(ctx, pack, ref_code_dev, sp);
-    }
+    ScanX sx;
+    sx.sample = ctx->sample_on ? 1 : 0;
+    sx.seed = ctx->sample_seed;
+    for (int b = 0; b < 6; b++) sx.keep[b] = ctx->sample_on ? ctx->sample_keep[b] : 0u;
+    const auto *sb = listed ? (const uint16_t *)ctx->site_bits.p : nullptr;
+    const auto *nb = listed_nbr ? (const uint16_t *)ctx->nbr_bits.p : nullptr;
+    if (listed) NC_TRY(build_bits(ctx, ctx->site_bits, ctx->n_gsites, ctx->gsite_pos, pack->tile_pos0, npos));
+    if (listed_nbr) NC_TRY(build_bits(ctx, ctx->nbr_bits, ctx->n_nsites, ctx->nsite_pos, pack->tile_pos0, npos));
+    if (ext) launch_scan<false, true>(ctx, pack, ref_code_dev, sp, sb, nb, sx);
+    else if (listed) launch_scan<true, false>(ctx, pack, ref_code_dev, sp, sb, nb, sx);
+    else launch_scan<false, false>(ctx, pack, ref_code_dev, sp, sb, nb, sx);
     NC_HIP(ctx, hipGetLastError());
     tm.stop();
     hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, ctx->stream, tc, (int2 *)ctx->tile_pre.p, pack->n_tiles,
@@ -530,6 +593,25 @@ int nc_snp_scan_set_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, in
     ctx->n_gsites = n_sites;
     ctx->gsite_pos = n_sites ? d_pos : nullptr;
     ctx->gsites_only = n_sites > 0 && only != 0;
+    return NC_OK;
+}
+
+int nc_snp_scan_set_nbr_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos, int32_t only)
+{
+    if (!ctx) return NC_ERR_ARG;
+    if (n_sites < 0 || (n_sites > 0 && !d_pos)) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_scan_set_nbr_sites: bad argument");
+    ctx->n_nsites = n_sites;
+    ctx->nsite_pos = n_sites ? d_pos : nullptr;
+    ctx->nsites_only = n_sites > 0 && only != 0;
+    return NC_OK;
+}
+
+int nc_snp_scan_set_sampling(nc_ctx *ctx, uint32_t seed, const uint32_t *keep6_host)
+{
+    if (!ctx) return NC_ERR_ARG;
+    ctx->sample_on = keep6_host != nullptr;
+    ctx->sample_seed = keep6_host ? seed : 0u;
+    for (int b = 0; b < 6; b++) ctx->sample_keep[b] = keep6_host ? keep6_host[b] : 0u;
     return NC_OK;
 }
 

@@ -23,6 +23,12 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def sample_thresholds(keep):
+    """probabilities in [0, 1) -> the uint32 thresholds of nc_snp_scan_set_sampling: a column is kept when its 32-bit hash is below
+    floor(keep * 2^32), that is with probability floor(keep * 2^32) / 2^32 over the hash values"""
+    return np.floor(np.asarray(keep, np.float64) * 4294967296.0).astype(np.uint32)
+
+
 @dataclass
 class DevicePack:
     codes: torch.Tensor
@@ -67,6 +73,7 @@ class SnpSites:
     rev_dp: torch.Tensor | None = None
     depth: torch.Tensor | None = None      # i32 [N]
     valid: torch.Tensor | None = None      # u8 [N]
+    nbr_only: bool = False                 # the scan took its neighbours from a list alone: the featuriser's min_nbr_sites counts them, not the site
 
 
 class _PinnedPool:
@@ -246,22 +253,42 @@ class Engine:
 
     # ------------------------------------------------------------------ K1
     def snp_scan(self, dp: DevicePack, chunks, *, mincov, min_allele_freq, threshold, haploid=False, async_fetch=False, sites=None,
-                 sites_only=False) -> SnpSites:
+                 sites_only=False, nbr_sites=None, nbr_only=False, sample=None) -> SnpSites:
         """chunks: list of (start, end) inclusive, same contig, ascending.
         sites (known-sites calling, nc_snp_scan_set_sites): 1-based positions of the contig (int array, or an int32 device tensor), any order,
         duplicates allowed -- a listed column that passes every other test is a candidate whatever its allele frequency; sites_only: the list
-        alone decides (with no position in it, nothing is a candidate).  The list is cleared when the scan's kernels are enqueued."""
-        d_sites = None
-        if sites is not None:
-            if isinstance(sites, torch.Tensor):
-                d_sites = sites.to(device=self.device, dtype=torch.int32).contiguous()
+        alone decides (with no position in it, nothing is a candidate).  The list is cleared when the scan's kernels are enqueued.
+        nbr_sites / nbr_only (nc_snp_scan_set_nbr_sites): the same for the neighbour rule -- a listed column that passes every other test is a
+        neighbour site whatever its allele frequency; nbr_only: the list alone decides (with no position in it, no column is a neighbour), and
+        snp_featurize then keeps a site that has min_nbr_sites such neighbours in reach, its own column not counted: a site none of the listed
+        sites reaches has no tensor, with no position for the contig nothing has.
+        sample = (seed, keep) (nc_snp_scan_set_sampling): keep = six probabilities in [0, 1), one per 5 % bin of the alternative allele
+        frequency (the last one: 25 % and above); a column under the candidate test is a candidate with that probability, decided by a hash of
+        its position and the seed.  Both are cleared with the list."""
+        def on_device(s):
+            if isinstance(s, torch.Tensor):
+                d = s.to(device=self.device, dtype=torch.int32).contiguous()
             else:
-                a = np.asarray(sites).astype(np.int64, copy=False).ravel()
+                a = np.asarray(s).astype(np.int64, copy=False).ravel()
                 a = a[(a >= 1) & (a <= np.iinfo(np.int32).max)]          # (no contig has other positions)
-                d_sites = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.device)
-            d_sites.record_stream(torch.cuda.current_stream(self.device))
+                d = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.device)
+            d.record_stream(torch.cuda.current_stream(self.device))
+            return d
+        d_sites = on_device(sites) if sites is not None else None
+        d_nbr = on_device(nbr_sites) if nbr_sites is not None else None
+        threshold = [float(threshold[0]), float(threshold[1])]
         if sites_only and (d_sites is None or d_sites.numel() == 0):
             min_allele_freq = 2.0                                    # alt <= n: no column passes the frequency test, none is listed
+        if nbr_only and (d_nbr is None or d_nbr.numel() == 0):
+            threshold[0] = 2.0                                       # the same for the neighbour rule: t0 <= alt_freq never holds
+        keep6 = None
+        if sample is not None:
+            seed, keep = sample
+            keep = np.asarray(keep, np.float64).ravel()
+            if keep.size != 6 or not np.all((keep >= 0.0) & (keep < 1.0)):
+                raise ValueError("snp_scan: sample = (seed, keep) needs six probabilities in [0, 1)")
+            keep6 = np.ascontiguousarray(sample_thresholds(keep))
+            seed = int(seed) & 0xFFFFFFFF
         cs = np.ascontiguousarray([c[0] for c in chunks], np.int32)
         ce = np.ascontiguousarray([c[1] for c in chunks], np.int32)
         scan_lo = max(1, int(cs.min()) - _lib.FLANK)
@@ -272,14 +299,23 @@ class Engine:
                                   nbr_t1=float(threshold[1]), haploid=1 if haploid else 0)
         pc = dp.c_struct()
         listed = d_sites is not None and d_sites.numel() > 0
-        if listed:
-            self._check(self.L.nc_snp_scan_set_sites(self.ctx, int(d_sites.numel()), _ptr(d_sites), 1 if sites_only else 0), "nc_snp_scan_set_sites")
+        listed_nbr = d_nbr is not None and d_nbr.numel() > 0
         try:
+            if listed:
+                self._check(self.L.nc_snp_scan_set_sites(self.ctx, int(d_sites.numel()), _ptr(d_sites), 1 if sites_only else 0), "nc_snp_scan_set_sites")
+            if listed_nbr:
+                self._check(self.L.nc_snp_scan_set_nbr_sites(self.ctx, int(d_nbr.numel()), _ptr(d_nbr), 1 if nbr_only else 0), "nc_snp_scan_set_nbr_sites")
+            if keep6 is not None:
+                self._check(self.L.nc_snp_scan_set_sampling(self.ctx, seed, _lib.npp(keep6)), "nc_snp_scan_set_sampling")
             self._check(self.L.nc_snp_scan_begin(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, dp.ref_code.numel(), scan_lo,
                                                  scan_hi, C.byref(params), len(chunks), _lib.npp(cs), _lib.npp(ce)), "nc_snp_scan_begin")
         finally:
-            if listed:                                               # the context never carries a list into a later call
+            if listed:                                               # the context never carries a list or a table into a later call
                 self.L.nc_snp_scan_set_sites(self.ctx, 0, None, 0)
+            if listed_nbr:
+                self.L.nc_snp_scan_set_nbr_sites(self.ctx, 0, None, 0)
+            if keep6 is not None:
+                self.L.nc_snp_scan_set_sampling(self.ctx, 0, None)
         n_nbr, n_cand, n_sites = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self.L.nc_snp_scan_end(self.ctx, C.byref(n_nbr), C.byref(n_cand), C.byref(n_sites)), "nc_snp_scan_end")
         N = n_sites.value
@@ -293,7 +329,7 @@ class Engine:
                         "nc_snp_scan_fetch_async")
         else:
             self._check(self.L.nc_snp_scan_fetch(self.ctx, None, ptr[0], ptr[1], ptr[2], ptr[3]), "nc_snp_scan_fetch")
-        return SnpSites(n_sites=N, n_nbr=n_nbr.value, pos=h[0, :N], chunk=h[1, :N], dp=h[2, :N], alt=h[3, :N])
+        return SnpSites(n_sites=N, n_nbr=n_nbr.value, pos=h[0, :N], chunk=h[1, :N], dp=h[2, :N], alt=h[3, :N], nbr_only=bool(nbr_only))
 
     def fetch_nbr_sites(self, n_nbr) -> np.ndarray:
         out = np.empty(n_nbr, np.int32)
@@ -302,7 +338,11 @@ class Engine:
 
     # ------------------------------------------------------------------ K2-K4
     def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1, int16=None) -> SnpSites:
-        """int16: sites.x as int16 (True) or as the reference's float32 (False); None: the engine's default (set_tensor_format)"""
+        """int16: sites.x as int16 (True) or as the reference's float32 (False); None: the engine's default (set_tensor_format).
+        min_nbr_sites: the reference's test of :244, which counts the site's own column; for sites of a scan in neighbour only mode
+        (sites.nbr_only) it counts the listed neighbours alone, so the kernel is asked for one column more."""
+        if sites.nbr_only:
+            min_nbr_sites = int(min_nbr_sites) + 1
         N = sites.n_sites
         dev = self.device
         want16 = self.x_int16 if int16 is None else bool(int16)

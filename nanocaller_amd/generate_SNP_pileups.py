@@ -254,10 +254,14 @@ def get_snp_testing_candidates(dct, region, device=0):
     eng.use_torch_stream()
     dp_ = device_pack_for(dct, chrom, device)
     # known-sites calling (genotype_sites.py): dct['genotype_sites'] / dct['genotype_only'], read with .get -- the reference's dct has neither
-    from .genotype_sites import sites_for
+    # listed neighbour sites: dct['neighbor_sites'] / dct['neighbor_only'], likewise; dct['background_sample'] = (seed, keep) is the trainer's
+    # (train.snp_training_examples: columns under the candidate threshold sampled by the scan)
+    from .genotype_sites import neighbor_sites_for, sites_for
     listed, only = sites_for(dct, chrom)
+    nbr_listed, nbr_only = neighbor_sites_for(dct, chrom)
     sites = eng.snp_scan(dp_, [(start, end)], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"],
-                         threshold=dct["threshold"], haploid=(ploidy == "haploid"), sites=listed, sites_only=only)
+                         threshold=dct["threshold"], haploid=(ploidy == "haploid"), sites=listed, sites_only=only,
+                         nbr_sites=nbr_listed, nbr_only=nbr_only, sample=dct.get("background_sample"))
     empty = ([], [], [], [], [], 0, [], [])
     if sites.n_sites == 0:
         return empty

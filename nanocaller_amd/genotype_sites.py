@@ -9,6 +9,11 @@ applies it (nc_snp_scan_set_sites), nothing downstream changes.
 The indel half ("Genotyping a given list of indel sites") has keys of its own, `genotype_indel_sites` / `genotype_indel_only`
 (NC_GENOTYPE_INDEL_SITES / NC_GENOTYPE_INDEL_ONLY=1): a listed column becomes a candidate of the indel window scan under its depth test
 (nc_indel_set_sites, device pipeline only).  The SNP keys and their parser do not read indel lines and are not touched by it.
+
+Neighbour sites given as a list ("Listed neighbour sites and background sampling"): `neighbor_sites` / `neighbor_only`
+(NC_NEIGHBOR_SITES / NC_NEIGHBOR_ONLY=1), a `{contig: positions}` dict or a VCF of which the heterozygous single-base records count.  The
+neighbour test of :173 / :177 then reads `frequency rule or v_pos in L` (or `v_pos in L` alone; nc_snp_scan_set_nbr_sites).  The two SNP lists
+are independent: a listed neighbour is no candidate because of it, a position to genotype no neighbour.
 """
 from __future__ import annotations
 
@@ -72,6 +77,79 @@ def sites_for(dct, chrom):
         a = np.unique(np.asarray(p).astype(np.int64, copy=False).ravel())
         return a[(a >= 1) & (a <= np.iinfo(np.int32).max)].astype(np.int32), only
     return load_sites_vcf(src)[0].get(chrom, _EMPTY), only
+
+
+_NBR_VCFS = {}                # (path, size, mtime) -> {contig: sorted unique int32 positions}
+_BASES = frozenset("AGTC")
+
+
+def parse_neighbor_vcf(path):
+    """-> {contig: sorted unique int32 POS} of the heterozygous single-base records, the test of the reference's training generator
+    (misc/training/generate_SNP_pileups.py:135-144): REF one of A, G, T, C, the first sample's GT two different allele indices ('/' or '|'),
+    both chosen alleles single bases.  A file without sample columns gives every record with a single-base REF and one single-base ALT."""
+    from .vcfio import read_vcf_gz
+    _, recs = read_vcf_gz(path)
+    by_contig = {}
+    for ln in recs:
+        f = ln.rstrip("\r\n").split("\t")
+        if len(f) < 5 or not f[1].isdigit() or f[3].upper() not in _BASES:
+            continue
+        alleles = [f[3].upper()] + [a.upper() for a in f[4].split(",")]
+        if len(f) >= 10:
+            fmt = f[8].split(":")
+            if "GT" not in fmt:
+                continue
+            g = f[9].split(":")[fmt.index("GT")].replace("|", "/").split("/")
+            if len(g) != 2 or not all(v.isdigit() for v in g) or g[0] == g[1] or max(int(g[0]), int(g[1])) >= len(alleles):
+                continue
+            chosen = (alleles[int(g[0])], alleles[int(g[1])])
+        elif len(alleles) == 2:
+            chosen = (alleles[0], alleles[1])
+        else:
+            continue
+        if chosen[0] in _BASES and chosen[1] in _BASES:
+            by_contig.setdefault(f[0], []).append(int(f[1]))
+    lim = np.iinfo(np.int32).max
+    out = {}
+    for c, p in by_contig.items():
+        a = np.unique(np.asarray(p, np.int64))
+        out[c] = a[(a >= 1) & (a <= lim)].astype(np.int32)
+    return out
+
+
+def load_neighbor_vcf(path):
+    """parse_neighbor_vcf, once per file (keyed by path, size and modification time)"""
+    path = str(path)
+    st = os.stat(path)
+    key = (path, st.st_size, st.st_mtime_ns)
+    with _LOCK:
+        hit = _NBR_VCFS.get(key)
+    if hit is None:
+        hit = parse_neighbor_vcf(path)
+        with _LOCK:
+            for k in [k for k in _NBR_VCFS if k[0] == path]:
+                del _NBR_VCFS[k]
+            _NBR_VCFS[key] = hit
+    return hit
+
+
+def neighbor_sites_for(dct, chrom):
+    """-> (positions, only): the neighbour sites listed for `chrom` as sorted unique int32 positions (None when no list is given at all) and
+    whether the list alone decides (nc_snp_scan_set_nbr_sites).  dct['neighbor_sites']: a {contig: positions} dict or a
+    VCF path (parse_neighbor_vcf); dct['neighbor_only']; without the keys NC_NEIGHBOR_SITES / NC_NEIGHBOR_ONLY=1.  A list that names no position
+    of `chrom` is an empty array: in only mode no column of that contig is a neighbour, and a site needs min_nbr_sites listed neighbours in
+    reach (its own column not counted), so that contig yields nothing."""
+    src = dct.get("neighbor_sites") if "neighbor_sites" in dct else (os.environ.get("NC_NEIGHBOR_SITES") or None)
+    if src is None or (isinstance(src, str) and not src):
+        return None, False
+    only = bool(dct["neighbor_only"]) if "neighbor_only" in dct else os.environ.get("NC_NEIGHBOR_ONLY") == "1"
+    if isinstance(src, dict):
+        p = src.get(chrom)
+        if p is None:
+            return _EMPTY, only
+        a = np.unique(np.asarray(p).astype(np.int64, copy=False).ravel())
+        return a[(a >= 1) & (a <= np.iinfo(np.int32).max)].astype(np.int32), only
+    return load_neighbor_vcf(src).get(chrom, _EMPTY), only
 
 
 LONG_INDEL = 10               # a listed indel is of the long-window class when an ALT differs from REF by more bases than this
@@ -165,4 +243,4 @@ def count_listed(sites, chunks, emitted_pos):
     return int(s.size), int(np.isin(s, np.asarray(emitted_pos)).sum()) if s.size else 0
 
 
-__all__ = ["parse_sites_vcf", "load_sites_vcf", "sites_for", "count_listed", "parse_indel_sites_vcf", "load_indel_sites_vcf", "indel_sites_for", "indel_list_given"]
+__all__ = ["parse_sites_vcf", "load_sites_vcf", "sites_for", "count_listed", "parse_neighbor_vcf", "load_neighbor_vcf", "neighbor_sites_for", "parse_indel_sites_vcf", "load_indel_sites_vcf", "indel_sites_for", "indel_list_given"]

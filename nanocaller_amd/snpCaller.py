@@ -166,7 +166,7 @@ VCF_HEADER = (                                                      # snpCaller.
 
 # keys of the `params` dict this module reads (all of them are in the dict NanoCaller:28-35 builds)
 # (opt-in keys of this project that the reference's dict does not have are read with .get and are not listed: 'genotype_sites',
-# 'genotype_only', 'haploid_snp_model'; tests/test_boundary.py holds this set to the reference's keys)
+# 'genotype_only', 'neighbor_sites', 'neighbor_only', 'haploid_snp_model'; tests/test_boundary.py holds this set to the reference's keys)
 PARAM_KEYS = frozenset(['chunks_list', 'regions_list', 'sam_path', 'fasta_path', 'mincov', 'maxcov', 'min_allele_freq', 'min_nbr_sites',
                         'threshold', 'snp_model', 'vcf_path', 'prefix', 'sample', 'seq', 'supplementary', 'exclude_bed',
                         'suppress_progress', 'disable_coverage_normalization'])
@@ -199,6 +199,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     -> dict of host arrays (pos, chunk, ref, probs, gt, dp, freq, fwd_dp, rev_dp, chunk_depth).
     params['genotype_sites'] / params['genotype_only'] (genotype_sites.py; both optional): positions to genotype whatever their allele
     frequency; the result then counts them: genotype_listed = listed positions inside these chunks, genotype_emitted = those with a record.
+    params['neighbor_sites'] / params['neighbor_only'] (genotype_sites.neighbor_sites_for; both optional): known heterozygous sites that are
+    neighbour sites whatever their allele frequency, beside the frequency rule or instead of it.
     params['haploid_snp_model'] (optional; else NC_HAPLOID_SNP_MODEL): 'haploid' or an .ncw of kind KIND_SNP_HAP for haploid chunks; a file brings
     its own train_coverage for the coverage scale (weights.get_haploid_SNP_model; a missing file or another kind raises).
     defer=True -> PendingCall: returns once the group's work is handed over; the caller starts the next group and collects result() afterwards.
@@ -228,12 +230,14 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
         dpk = device_pack_for(params, chrom, device, span=contig_span(params['sam_path'], chrom, chunks))
     # Results drain on a second stream while the GPU keeps computing: the candidate arrays right after the scan, the
     # featuriser's per-site arrays during the CNN, and every CNN batch's probabilities while the next batch runs.
-    from .genotype_sites import count_listed, sites_for
+    from .genotype_sites import count_listed, neighbor_sites_for, sites_for
     listed, only = sites_for(params, chrom)
+    nbr_listed, nbr_only = neighbor_sites_for(params, chrom)
     spans = [(c['start'], c['end']) for c in chunks]
     sites = eng.snp_scan(dpk, spans, mincov=params['mincov'],
                          min_allele_freq=params['min_allele_freq'], threshold=params['threshold'],
-                         haploid=(ploidy == 'haploid'), async_fetch=True, sites=listed, sites_only=only)
+                         haploid=(ploidy == 'haploid'), async_fetch=True, sites=listed, sites_only=only,
+                         nbr_sites=nbr_listed, nbr_only=nbr_only)
     res = dict(chrom=chrom, ploidy=ploidy, n=0, genotype_listed=count_listed(listed, spans, ())[0], genotype_emitted=0)
     if sites.n_sites == 0:
         eng.wait_copies()
@@ -242,7 +246,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     # trunk, which reads the reference's float32 layout, has been selected
     exact = eng.exact_fp32
     eng.snp_featurize(dpk, sites, seq=params['seq'], maxcov=params['maxcov'], min_nbr_sites=params['min_nbr_sites'], int16=not exact)
-    all_valid = bool(sites.valid.all().item()) if params['min_nbr_sites'] > 1 else True   # default 1 never filters (:244)
+    # default 1 never filters (:244), unless the neighbours come from a list alone (it then counts them, not the site's own column)
+    all_valid = bool(sites.valid.all().item()) if params['min_nbr_sites'] > 1 or sites.nbr_only else True
     per_site = bool(params.get('disable_coverage_normalization'))
     scale, chunk_depth = eng.snp_scale(sites, len(chunks), train_cov, per_site=per_site, async_fetch=True)
     scan_copied = eng.copy_event()                                 # candidate arrays + chunk depths are on the host behind this

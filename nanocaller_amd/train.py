@@ -9,7 +9,9 @@ csrc/nc_train.hip.  torch is plumbing only: device memory, the dropout mask's ra
     tr.step(x, ref_code, labels); tr.evaluate(x, ref_code, labels); tr.save("model-1.ncw", train_coverage)
     python -m nanocaller_amd.train -bam x.bam -ref x.fa -vcf truth.vcf.gz -bed confident.bed -o out_dir
 
-The result is used as snp_model='/path/model-N.ncw'.
+The result is used as snp_model='/path/model-N.ncw'.  Opt-in, the two further halves of the reference's generator:
+truth_neighbors (-truth_neighbors) adds every site a second time with the truth's heterozygous sites as its neighbours, background
+(-background) samples columns under the candidate threshold as further reference-call examples.
 """
 from __future__ import annotations
 
@@ -154,21 +156,68 @@ def _read_text(path):
     return (gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw).decode()
 
 
-def snp_training_examples(params, truth_vcf=None, confident_bed=None, neg_ratio=2.0, seed=0, device=0):
+BACKGROUND_GROUPS = 3         # the sampled columns' bins: alt_freq in [0, 5 %), [5 %, 10 %), [10 %, min_allele_freq)
+_KEEP_MAX = 1.0 - 2.0 ** -20  # the largest keep probability handed to the scan (its thresholds take [0, 1))
+
+
+def background_group(n, alt):
+    """the bin of a sampled column from its depth and its largest alternative count: min(2, (20 * alt) // n)"""
+    return np.minimum(2, (20 * np.asarray(alt, np.int64)) // np.asarray(n, np.int64))
+
+
+def background_caps(background, n_truth):
+    """caps of the three bins: T, T // 3, T // 3 of generate_SNP_pileups.py:260 (misc/training) with T truth sites, or the {bin: cap} given"""
+    caps = [n_truth, n_truth // 3, n_truth // 3]
+    if isinstance(background, dict):
+        unknown = set(background) - set(range(BACKGROUND_GROUPS))
+        if unknown:
+            raise ValueError("background: bins are 0, 1, 2, got %s" % sorted(unknown))
+        caps = [int(background.get(g, 0)) for g in range(BACKGROUND_GROUPS)]
+    return caps
+
+
+def _background_keep(eng, dpk, dct, start, end, caps, seed):
+    """the six keep probabilities of the scan (engine.snp_scan, sample=): per bin about twice its cap expected.  The bins' populations are
+    estimated by a scan that samples every bin alike and takes no candidate otherwise (about 2^16 columns come back)."""
+    q = min(0.5, 65536.0 / max(1, end - start + 1))
+    probe = eng.snp_scan(dpk, [(start, end)], mincov=dct["mincov"], min_allele_freq=dct["min_allele_freq"], threshold=dct["threshold"], sites_only=True,
+                         sample=(seed ^ 0x5bd1e995, [q] * 6))
+    under = probe.alt.astype(np.float64) / np.maximum(probe.dp, 1) < dct["min_allele_freq"]
+    count = np.bincount(background_group(np.maximum(probe.dp[under], 1), probe.alt[under]), minlength=BACKGROUND_GROUPS)
+    keep3 = [0.0 if caps[g] <= 0 else min(_KEEP_MAX, 2.0 * caps[g] * q / max(1, int(count[g]))) for g in range(BACKGROUND_GROUPS)]
+    return keep3[:2] + [keep3[2]] * 4                                # (columns at min_allele_freq and above are candidates, never sampled)
+
+
+def snp_training_examples(params, truth_vcf=None, confident_bed=None, neg_ratio=2.0, seed=0, device=0, truth_neighbors=False, background=None):
     """Labelled sites per contig: {chrom: (x int16-valued float32 [n][5][41][5] device tensor, ref_code int32 [n] device tensor,
     labels uint8 [n][5] numpy, pos int64 [n] numpy, mean depth)}.
 
     params: the SNP step's dict (sam_path, fasta_path, mincov, maxcov, min_allele_freq, min_nbr_sites, threshold, seq, ...), plus
     'chrom_list' = [(chrom, start, end)].  sam_path may be a synth.World or a key registered with register_alignments; with a World,
     truth_vcf=None takes its planted truth and confident_bed=None means everywhere.  Sites = the ordinary scan candidates + the truth
-    positions, the latter handed over as a genotype_sites list.  Deviations from the reference's generator: neighbours are chosen by the
-    inference rule only (no second example with ground-truth neighbours); columns under the candidate threshold are not sampled."""
+    positions, the latter handed over as a genotype_sites list.
+
+    background (True, or {bin: cap} with bins 0, 1, 2): columns under the candidate threshold are sampled too, in the bins alt_freq in
+    [0, 5 %), [5 %, 10 %) and [10 %, min_allele_freq) (generate_SNP_pileups.py:223-260 of misc/training): the scan keeps a column when a hash
+    of its position and the seed falls under the bin's probability (engine.snp_scan, sample=), chosen for about twice the bin's cap; of
+    those inside the confident regions (none is a truth position) a seeded uniform subset of at most T, T // 3, T // 3 is kept, T the
+    truth sites kept, labelled (0, ref, ref) like any other non-truth site.  They are not counted against neg_ratio.  Deviation: the
+    reference's np.take(pos_list, np.random.permutation(size)) keeps the first `size` positions, not a random subset.
+
+    truth_neighbors: every kept site a second time (:273), its neighbours the truth's heterozygous single-base sites alone
+    (nc_snp_scan_set_nbr_sites in only mode) instead of the columns the frequency rule picks; these examples follow the first ones with the
+    same labels, so pos holds a position twice.  A site with fewer than min_nbr_sites such neighbours in reach has no second example (in only
+    mode the site's own column is not counted, engine.snp_featurize).
+
+    The mean depth is that of the first pass's sites, sampled ones included.  snp_training_examples.plan[chrom] afterwards: n_first (examples
+    of the first pass), n_truth (T), and with background its sample = (seed, keep) and caps."""
     import torch
 
-    from .generate_SNP_pileups import get_snp_testing_candidates
+    from .engine import get_engine
+    from .generate_SNP_pileups import device_pack_for, get_snp_testing_candidates
     from .synth import World
     src = params["sam_path"]
-    out = {}
+    out, plan = {}, {}
     regions = params.get("chrom_list")
     if regions is None and isinstance(src, World):
         regions = [(src.chrom, 1, src.length)]
@@ -182,17 +231,66 @@ def snp_training_examples(params, truth_vcf=None, confident_bed=None, neg_ratio=
         else:
             raise ValueError("snp_training_examples: a truth VCF is needed unless sam_path is a synth.World")
         intervals = parse_bed(bed_text, chrom) if bed_text is not None else None
+        region = dict(chrom=chrom, start=start, end=end, ploidy="diploid")
+        truth_pos = np.fromiter(truth.keys(), np.int64, len(truth))
         dct = dict(params)
-        dct["genotype_sites"] = {chrom: np.fromiter(truth.keys(), np.int64, len(truth))}
+        dct["genotype_sites"] = {chrom: truth_pos}
         dct["genotype_only"] = False
-        pos, ref1h, mat, _, _, depth, _, _ = get_snp_testing_candidates(dct, dict(chrom=chrom, start=start, end=end, ploidy="diploid"), device)
+        dct["neighbor_sites"] = None                                 # (the first pass takes the inference rule's neighbours, whatever the environment says)
+        info = {}
+        if background:
+            inside = truth_pos[(truth_pos >= start) & (truth_pos <= end)]
+            caps = background_caps(background, int(in_bed(intervals, inside).sum()) if intervals is not None else int(inside.size))
+            eng = get_engine(device)
+            eng.use_torch_stream()
+            sample = ((seed + k) & 0xFFFFFFFF, _background_keep(eng, device_pack_for(dct, chrom, device), dct, start, end, caps, seed + k))
+            dct["background_sample"] = sample
+            info.update(sample=sample)
+        pos, ref1h, mat, n_all, freq, depth, _, _ = get_snp_testing_candidates(dct, region, device)
         if len(pos) == 0:
             continue
+        pos, n_all = np.asarray(pos), np.asarray(n_all, np.int64)
         ref_code = np.argmax(ref1h, 1).astype(np.int32)
-        idx, labels = label_sites(pos, ref_code, truth, intervals, neg_ratio, seed + k)
+        # a sampled column: under the candidate threshold and no truth position (it failed the candidate test)
+        sampled = (np.asarray(freq) < dct["min_allele_freq"]) & ~np.isin(pos, truth_pos) if background else np.zeros(pos.size, bool)
+        own = np.nonzero(~sampled)[0]
+        idx, labels = label_sites(pos[own], ref_code[own], truth, intervals, neg_ratio, seed + k)
+        idx = own[idx]
+        n_truth = int(np.isin(pos[idx], truth_pos).sum())
+        if background:
+            caps = background_caps(background, n_truth)
+            bg = np.nonzero(sampled)[0]
+            bi, bl = label_sites(pos[bg], ref_code[bg], {}, intervals, None)
+            bg = bg[bi]
+            grp = background_group(n_all[bg], np.rint(np.asarray(freq)[bg] * n_all[bg]))            # (freq = alt / n: the count back, exactly)
+            rng = np.random.default_rng([seed + k, 1])
+            take = np.zeros(bg.size, bool)
+            for g in range(BACKGROUND_GROUPS):
+                m = np.nonzero(grp == g)[0]
+                take[m if m.size <= caps[g] else rng.permutation(m)[:caps[g]]] = True
+            idx, labels = np.concatenate([idx, bg[take]]), np.concatenate([labels, bl[take]])
+            order = np.argsort(idx, kind="stable")
+            idx, labels = idx[order], labels[order]
+            info.update(caps=caps)
+        x_all, ref_all, pos_all = mat[idx], ref_code[idx], pos[idx]
+        info.update(n_first=int(idx.size), n_truth=n_truth)
+        if truth_neighbors and idx.size:
+            het = np.array(sorted(p for p, t in truth.items() if t[0] == 1), np.int64)
+            d2 = dict(params)
+            d2.update(genotype_sites={chrom: pos_all}, genotype_only=True, neighbor_sites={chrom: het}, neighbor_only=True)
+            pos2, ref2, mat2 = get_snp_testing_candidates(d2, region, device)[:3]
+            if len(pos2):
+                at = np.searchsorted(pos_all, pos2)                  # (pos_all ascends; every position of the second pass is one of it)
+                assert np.array_equal(pos_all[at], pos2)
+                x_all = np.concatenate([x_all, mat2])
+                ref_all = np.concatenate([ref_all, np.argmax(ref2, 1).astype(np.int32)])
+                labels = np.concatenate([labels, labels[at]])
+                pos_all = np.concatenate([pos_all, np.asarray(pos2)])
         dev = torch.device("cuda", device)
-        out[chrom] = (torch.from_numpy(np.ascontiguousarray(mat[idx], np.float32)).to(dev), torch.from_numpy(ref_code[idx]).to(dev), labels,
-                      np.asarray(pos)[idx], float(depth))
+        out[chrom] = (torch.from_numpy(np.ascontiguousarray(x_all, np.float32)).to(dev), torch.from_numpy(np.ascontiguousarray(ref_all)).to(dev), labels,
+                      pos_all, float(depth))
+        plan[chrom] = info
+    snp_training_examples.plan = plan
     return out
 
 
@@ -347,12 +445,13 @@ class SnpTrainer:
 def train_snp_model(params):
     """Epochs over the contigs of params['chrom_list'] with a validation split; writes <out_dir>/model-<epoch>.ncw.
     params: the SNP step's keys + truth_vcf, confident_bed, out_dir, and optionally epochs (10), batch (1024), lr (1e-3), gamma, keep, seed,
-    init (model to fine-tune), val_frac (0.1), neg_ratio (2).  -> list of per-epoch dicts (train cost, validation losses / accuracies, path)"""
+    init (model to fine-tune), val_frac (0.1), neg_ratio (2), truth_neighbors and background (snp_training_examples).  The file's train_coverage
+    is the mean depth of the training sites, sampled background columns included.  -> list of per-epoch dicts (train cost, validation losses / accuracies, path)"""
     import torch
     seed = int(params.get("seed", 0))
     batch = int(params.get("batch", 1024))
     ex = snp_training_examples(params, params.get("truth_vcf"), params.get("confident_bed"), params.get("neg_ratio", 2.0), seed,
-                               params.get("device", 0))
+                               params.get("device", 0), truth_neighbors=bool(params.get("truth_neighbors")), background=params.get("background"))
     if not ex:
         raise ValueError("train_snp_model: no labelled site")
     x = torch.cat([v[0] for v in ex.values()])
@@ -405,6 +504,8 @@ def main(argv=None):
     ap.add_argument("-mincov", type=int, default=4)
     ap.add_argument("-maxcov", type=int, default=160)
     ap.add_argument("-min_allele_freq", type=float, default=0.15)
+    ap.add_argument("-truth_neighbors", action="store_true", help="every site a second time with the truth's heterozygous sites as its neighbours")
+    ap.add_argument("-background", action="store_true", help="sample columns under the candidate threshold as further reference-call examples")
     a = ap.parse_args(argv)
     regions = []
     for c in a.chrom:
@@ -414,7 +515,8 @@ def main(argv=None):
     thr = {"ont": [0.4, 0.6], "ul_ont": [0.4, 0.6], "ul_ont_extreme": [0.4, 0.6], "pacbio": [0.3, 0.7]}.get(a.seq, [0.4, 0.6])
     params = dict(sam_path=a.bam, fasta_path=a.ref, truth_vcf=a.vcf, confident_bed=a.bed, out_dir=a.out_dir, chrom_list=regions, seq=a.seq,
                   mincov=a.mincov, maxcov=a.maxcov, min_allele_freq=a.min_allele_freq, min_nbr_sites=1, threshold=thr, supplementary=False,
-                  exclude_bed=None, init=a.init, epochs=a.epochs, batch=a.batch, lr=a.lr, gamma=a.gamma, keep=a.keep, seed=a.seed)
+                  exclude_bed=None, init=a.init, epochs=a.epochs, batch=a.batch, lr=a.lr, gamma=a.gamma, keep=a.keep, seed=a.seed,
+                  truth_neighbors=a.truth_neighbors, background=a.background)
     train_snp_model(params)
 
 
