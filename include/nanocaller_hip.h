@@ -444,6 +444,45 @@ int nc_snp_scan_set_nbr_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *d_pos
  * calls.  The decision depends on the position alone, not on the pack's tile size. */
 int nc_snp_scan_set_sampling(nc_ctx *ctx, uint32_t seed, const uint32_t *keep6_host);
 
+/* ---- Reference-confidence blocks of a gVCF (csrc/nc_refconf.hip; ABI 11: added exports).  All arithmetic is integer: the
+ * host turns the per-read error rate e into c_m = round(-10000 log10(1 - e)), c_x = round(-10000 log10(e)), c_h = round(-10000 log10(0.5)).
+ * A column with reference code r < 4, n pileup entries of code 0..4 (the scan's n), ref of them equal to r and alt = n - ref has
+ *   S00 = ref c_m + alt c_x,  S01 = n c_h,  S11 = ref c_x + alt c_m  (64-bit),  other = min(S01, S11) (haploid: S11, no S01),
+ * is a no-call when n == 0 or S00 > other (GQ 0), else has GQ = min(99, (other - S00) / 1000); PL_g = min(9999, (S_g - min S) / 1000).  Its band
+ * is the index of the last of the n_bands ascending lower edges band[] (band[0] = 0) that is <= GQ; no-call columns are a band of their own. */
+typedef struct {
+    int32_t c_m, c_x, c_h;
+    int32_t haploid;
+    int32_t n_bands;               /* 1..16 */
+    int32_t band[16];
+} nc_refconf_params;
+
+/* One uint32 per column of the pack's tile grid, n | alt << 16 (0xFFFFFFFF where the column's reference code is >= 4), into d_words [npos],
+ * npos = n_tiles * tile_size, 16-byte aligned.  d_ref_code [npos] as for nc_snp_scan (index 0 = tile_pos0).  Streams the pack once, on the
+ * context's stream, and does not wait.  n saturates nowhere below 65536 entries per column (the pileup's depth cap is 8000). */
+int nc_refconf_columns(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *d_ref_code, int32_t tile_pos0, int64_t npos, uint32_t *d_words);
+
+/* The blocks of the words of nc_refconf_columns (or any word array of that form: npos a multiple of 16, tile_pos0 a multiple of 16).  A column is
+ * open when it lies in one of the n_chunks intervals [chunk_start, chunk_end] (host arrays, both ends inclusive, any order, overlapping and
+ * abutting ones merge), its word is not 0xFFFFFFFF and it lies in none of the n_cut intervals [d_cut_start, d_cut_end] (device arrays, inclusive,
+ * any order, may overlap; columns outside the grid are ignored).  A block is a maximal run of consecutive open columns of one band.  This call
+ * counts them (*n_blocks; it waits for the count); nc_refconf_fetch then writes them in position order, six int32 each: start, end (1-based,
+ * inclusive), min n, min GQ, and n and alt of the leftmost column that attains that GQ.  Blocks of any length are joined on the device.  The
+ * inputs must stay valid and unchanged until nc_refconf_fetch has returned. */
+int nc_refconf_blocks(nc_ctx *ctx, const uint32_t *d_words, int32_t tile_pos0, int64_t npos, int32_t n_chunks, const int32_t *chunk_start_host,
+                      const int32_t *chunk_end_host, int32_t n_cut, const int32_t *d_cut_start, const int32_t *d_cut_end,
+                      const nc_refconf_params *params, int64_t *n_blocks);
+/* out [n_blocks][6] int32 in device or host memory; returns when it is complete */
+int nc_refconf_fetch(nc_ctx *ctx, int32_t *d_or_host_out);
+
+/* The blocks' records as text, written on the device:
+ *   CHROM \t start \t . \t R \t <*> \t 0 \t . \t END=end \t GT:GQ:MIN_DP:PL \t 0/0:gq:min_dp:pl0,pl1,pl2 \n
+ * R = "AGTC"[reference code of the start column]; a no-call block has ./. ; haploid: 0 or . and two PL values.  d_blocks [n_blocks][6] (device),
+ * d_line_off [n_blocks + 1] int64 (device).  With d_text == NULL the call computes every line's byte offset into d_line_off and the total into
+ * *n_bytes (it waits for it); with d_text [text_cap >= that total] it writes the bytes at the offsets d_line_off holds from such a call. */
+int nc_refconf_text(nc_ctx *ctx, int64_t n_blocks, const int32_t *d_blocks, const uint8_t *d_ref_code, int32_t tile_pos0, int64_t npos,
+                    const char *chrom, const nc_refconf_params *params, int64_t *d_line_off, uint8_t *d_text, int64_t text_cap, int64_t *n_bytes);
+
 /* Per-site coverage scale (snpCaller.py:93-96, 170-173) for the sites of the last scan:
  * mode 0: scale[s] = train_coverage / mean(site_depth over the site's chunk) (chunk constant, quirk E2)
  * mode 1: scale[s] = train_coverage / dp[s] (--disable_coverage_normalization).

@@ -58,6 +58,7 @@ EXPORTS = [
     "nc_hap_train_loss_grad", "nc_hap_train_adam", "nc_hap_train_info", "nc_hap_train_stage_ms",
     "nc_hap_indel_train_create", "nc_hap_indel_train_free", "nc_hap_indel_train_set_weights", "nc_hap_indel_train_get_weights",
     "nc_hap_indel_train_forward", "nc_hap_indel_train_loss_grad", "nc_hap_indel_train_adam", "nc_hap_indel_train_info", "nc_hap_indel_train_stage_ms",
+    "nc_refconf_columns", "nc_refconf_blocks", "nc_refconf_fetch", "nc_refconf_text",
 ]
 
 
@@ -77,6 +78,10 @@ class ReadPackC(C.Structure):
 class ScanParamsC(C.Structure):
     _fields_ = [("mincov", C.c_int32), ("min_allele_freq", C.c_double), ("nbr_t0", C.c_double), ("nbr_t1", C.c_double),
                 ("haploid", C.c_int32)]
+
+
+class RefconfParamsC(C.Structure):
+    _fields_ = [("c_m", C.c_int32), ("c_x", C.c_int32), ("c_h", C.c_int32), ("haploid", C.c_int32), ("n_bands", C.c_int32), ("band", C.c_int32 * 16)]
 
 
 class IndelEventsC(C.Structure):
@@ -333,6 +338,10 @@ def lib():
         for fam in ("nc_hap_indel_train",):                             # the nc_indel_train_* family's signatures
             for fn in ("create", "free", "set_weights", "get_weights", "forward", "loss_grad", "adam", "info", "stage_ms"):
                 getattr(L, "%s_%s" % (fam, fn)).argtypes = getattr(L, "nc_indel_train_" + fn).argtypes
+        L.nc_refconf_columns.argtypes = [vp, C.POINTER(ReadPackC), vp, i32, i64, vp]
+        L.nc_refconf_blocks.argtypes = [vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, C.POINTER(RefconfParamsC), C.POINTER(i64)]
+        L.nc_refconf_fetch.argtypes = [vp, vp]
+        L.nc_refconf_text.argtypes = [vp, i64, vp, vp, i32, i64, C.c_char_p, C.POINTER(RefconfParamsC), vp, vp, i64, C.POINTER(i64)]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

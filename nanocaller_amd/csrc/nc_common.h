@@ -127,6 +127,7 @@ struct nc_ctx {
 
     nc_weights w[4];
     struct nc_pipe_state *pipe = nullptr;   // device-resident indel pipeline (nc_pipe.hip): plan state, workspaces, results
+    struct nc_refconf_state *refconf = nullptr;   // reference-confidence blocks (nc_refconf.hip): what nc_refconf_blocks leaves for nc_refconf_fetch
     uint8_t *range_sites = nullptr;         // nc_cnn_range_watch: device byte per site of the next nc_snp_forward, set when the site's
                                             // scaled tensor exceeds the model's x_limit (the caller re-runs those sites on the exact trunk)
 
@@ -247,3 +248,4 @@ struct NcTimer {
 // implemented in the kernel translation units
 int nc_selftest_device(nc_ctx *ctx);
 void nc_pipe_destroy(nc_ctx *ctx);          // nc_pipe.hip
+void nc_refconf_destroy(nc_ctx *ctx);       // nc_refconf.hip

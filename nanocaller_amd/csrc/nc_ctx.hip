@@ -139,6 +139,7 @@ int nc_ctx_destroy(nc_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     nc_pipe_destroy(ctx);
+    nc_refconf_destroy(ctx);
     for (auto &w : ctx->w) {
         if (w.dev) (void)hipFree(w.dev);
         if (w.packed) (void)hipFree(w.packed);

@@ -336,6 +336,74 @@ class Engine:
         self._check(self.L.nc_snp_scan_fetch(self.ctx, _lib.npp(out), None, None, None, None), "nc_snp_scan_fetch")
         return out
 
+    # ------------------------------------------------------------------ reference-confidence blocks (csrc/nc_refconf.hip; gvcf.py)
+    REFCONF_TILE = 4096                                              # columns per workgroup of the blocks kernels (the tests put borders on it)
+
+    @staticmethod
+    def _refconf_params(error, bands, haploid):
+        from . import gvcf
+        c_m, c_x, c_h = gvcf.constants(error)
+        b = gvcf.gq_bands(bands)
+        prm = _lib.RefconfParamsC(c_m=c_m, c_x=c_x, c_h=c_h, haploid=1 if haploid else 0, n_bands=len(b))
+        for k, v in enumerate(b):
+            prm.band[k] = v
+        return prm
+
+    def refconf_columns(self, dp: DevicePack):
+        """-> (words, ref_code, tile_pos0): one int32 (the bits of a uint32: n | alt << 16, all ones where the reference code is >= 4) per column of
+        the pack's tile grid, the grid's reference codes (a copy: packs of an ingest pipeline share one buffer) and the grid's first position.
+        Enqueued on the context's stream while the pack is resident; nothing later needs the pack."""
+        npos = dp.n_tiles * dp.tile_size
+        if dp.ref_code.numel() < npos:
+            raise ValueError("refconf_columns: the pack's reference codes hold %d columns, its tile grid %d" % (dp.ref_code.numel(), npos))
+        words = torch.empty(npos, dtype=torch.int32, device=self.device)
+        pc = dp.c_struct()
+        self._check(self.L.nc_refconf_columns(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, npos, _ptr(words)), "nc_refconf_columns")
+        return words, dp.ref_code[:npos].clone(), dp.tile_pos0
+
+    def refconf_blocks(self, words, dpk, chunks, cuts, *, error, bands, haploid=False, device_out=False):
+        """The blocks of `words` (refconf_columns, or any int32 / uint32-bits device tensor of that form, a multiple of 16 long) -> int32 [n][6]:
+        start, end, min n, min GQ, n and alt of the leftmost column with that GQ (host array; device_out: a device tensor).
+        dpk: the pack (its tile_pos0 places column 0) or that position itself, a multiple of 16; chunks: (start, end) inclusive intervals whose union
+        is the region; cuts: None or an int array [k][2] of inclusive intervals (host or device) whose columns belong to no block."""
+        tile_pos0 = int(getattr(dpk, "tile_pos0", dpk))
+        prm = self._refconf_params(error, bands, haploid)
+        cs = np.ascontiguousarray([c[0] for c in chunks], np.int32)
+        ce = np.ascontiguousarray([c[1] for c in chunks], np.int32)
+        d_cs = d_ce = None
+        n_cut = 0
+        if cuts is not None and len(cuts):
+            d_cuts = cuts if isinstance(cuts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cuts, np.int32).reshape(-1, 2))
+            d_cuts = d_cuts.to(device=self.device, dtype=torch.int32)
+            d_cs, d_ce = d_cuts[:, 0].contiguous(), d_cuts[:, 1].contiguous()
+            n_cut = int(d_cs.numel())
+        nb = C.c_int64()
+        self._check(self.L.nc_refconf_blocks(self.ctx, _ptr(words), tile_pos0, int(words.numel()), len(chunks), _lib.npp(cs), _lib.npp(ce), n_cut,
+                                             _ptr(d_cs), _ptr(d_ce), C.byref(prm), C.byref(nb)), "nc_refconf_blocks")
+        n = int(nb.value)
+        if device_out:
+            out = torch.empty((n, 6), dtype=torch.int32, device=self.device)
+            self._check(self.L.nc_refconf_fetch(self.ctx, _ptr(out) if n else None), "nc_refconf_fetch")
+            return out
+        out = np.empty((n, 6), np.int32)
+        self._check(self.L.nc_refconf_fetch(self.ctx, _lib.npp(out) if n else None), "nc_refconf_fetch")
+        return out
+
+    def refconf_text(self, blocks, ref_code, tile_pos0, chrom, *, error, haploid=False):
+        """The records of `blocks` (refconf_blocks; host array or device tensor) written on the device -> (text uint8 host array, byte offset of
+        every line int64 [n + 1] host array).  ref_code: the grid's reference codes (device uint8, index 0 = tile_pos0)."""
+        prm = self._refconf_params(error, None, haploid)
+        d_blocks = blocks if isinstance(blocks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(blocks, np.int32).reshape(-1, 6))
+        d_blocks = d_blocks.to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(d_blocks.shape[0])
+        off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        nbytes = C.c_int64()
+        args = (self.ctx, n, _ptr(d_blocks) if n else None, _ptr(ref_code), int(tile_pos0), int(ref_code.numel()), str(chrom).encode(), C.byref(prm), _ptr(off))
+        self._check(self.L.nc_refconf_text(*args, None, 0, C.byref(nbytes)), "nc_refconf_text")
+        text = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.nc_refconf_text(*args, _ptr(text), int(nbytes.value), None), "nc_refconf_text")
+        return text[:int(nbytes.value)].cpu().numpy(), off.cpu().numpy()
+
     # ------------------------------------------------------------------ K2-K4
     def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1, int16=None) -> SnpSites:
         """int16: sites.x as int16 (True) or as the reference's float32 (False); None: the engine's default (set_tensor_format).

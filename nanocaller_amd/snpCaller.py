@@ -166,7 +166,8 @@ VCF_HEADER = (                                                      # snpCaller.
 
 # keys of the `params` dict this module reads (all of them are in the dict NanoCaller:28-35 builds)
 # (opt-in keys of this project that the reference's dict does not have are read with .get and are not listed: 'genotype_sites',
-# 'genotype_only', 'neighbor_sites', 'neighbor_only', 'haploid_snp_model'; tests/test_boundary.py holds this set to the reference's keys)
+# 'genotype_only', 'neighbor_sites', 'neighbor_only', 'haploid_snp_model', 'gvcf', 'gvcf_error', 'gvcf_gq_bands'; tests/test_boundary.py holds this set
+# to the reference's keys)
 PARAM_KEYS = frozenset(['chunks_list', 'regions_list', 'sam_path', 'fasta_path', 'mincov', 'maxcov', 'min_allele_freq', 'min_nbr_sites',
                         'threshold', 'snp_model', 'vcf_path', 'prefix', 'sample', 'seq', 'supplementary', 'exclude_bed',
                         'suppress_progress', 'disable_coverage_normalization'])
@@ -203,6 +204,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     neighbour sites whatever their allele frequency, beside the frequency rule or instead of it.
     params['haploid_snp_model'] (optional; else NC_HAPLOID_SNP_MODEL): 'haploid' or an .ncw of kind KIND_SNP_HAP for haploid chunks; a file brings
     its own train_coverage for the coverage scale (weights.get_haploid_SNP_model; a missing file or another kind raises).
+    params['gvcf'] (optional; else NC_GVCF=1; gvcf.py): the result then carries 'gvcf', the per-column counts of the group's pack on the device
+    (Engine.refconf_columns), from which caller() makes the reference-confidence blocks once the group's records are known.
     defer=True -> PendingCall: returns once the group's work is handed over; the caller starts the next group and collects result() afterwards.
     pipeline: None or False.  True asked for a removed path (a group's CNN enqueued inside the next call's scan; measured slower, 10.55 ->
     11.2 ms per contig: profiles/README.md, round 6) and raises."""
@@ -239,6 +242,11 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
                          haploid=(ploidy == 'haploid'), async_fetch=True, sites=listed, sites_only=only,
                          nbr_sites=nbr_listed, nbr_only=nbr_only)
     res = dict(chrom=chrom, ploidy=ploidy, n=0, genotype_listed=count_listed(listed, spans, ())[0], genotype_emitted=0)
+    from . import gvcf
+    if gvcf.enabled(params):
+        # the per-column counts of the gVCF's reference-confidence blocks, behind the scan while the pack is resident (4 B per column, held until
+        # the group's records are collected: gvcf.group_blocks)
+        res['gvcf'] = eng.refconf_columns(dpk)
     if sites.n_sites == 0:
         eng.wait_copies()
         return PendingCall(lambda: res) if defer else res
@@ -434,19 +442,27 @@ class _Records:
     """Host pipeline of caller(): the genotype rules + record text of one (contig, ploidy) group are produced and written by a worker
     thread (the formatter is native code: the GIL is released) while the GPU already works on the next group."""
 
-    def __init__(self, f, pool, counter_Q):
-        self.f, self.pool, self.counter_Q, self.scratch, self.pending = f, pool, counter_Q, None, None
+    def __init__(self, f, pool, counter_Q, gvcf_f=None):
+        self.f, self.pool, self.counter_Q, self.scratch, self.pending, self.gvcf_f = f, pool, counter_Q, None, None, gvcf_f
 
-    def emit(self, chrom, ploidy, r, grp):
+    def emit(self, chrom, ploidy, r, grp, blocks=None):
         f = self.f
+        text = b''
         if r['n']:
             need = (400 + len(chrom)) * r['n'] + 1024
             if self.scratch is None or self.scratch.size < need:
                 self.scratch = np.empty(need + need // 4, np.uint8)
-            f.write(snp_vcf_text(chrom, r['pos'], r['ref'], r['probs'], r['dp'], r['freq'], r['fwd_dp'], r['rev_dp'],
-                                 haploid=(ploidy != 'diploid'), as_array=True, out=self.scratch))
+            text = snp_vcf_text(chrom, r['pos'], r['ref'], r['probs'], r['dp'], r['freq'], r['fwd_dp'], r['rev_dp'],
+                                haploid=(ploidy != 'diploid'), as_array=True, out=self.scratch)
+            f.write(text)
         f.flush()
         os.fsync(f.fileno())
+        if blocks is not None:
+            # the group's share of the gVCF: its variant lines, as they are, between the blocks the device cut at them
+            from . import gvcf
+            for piece in gvcf.splice(blocks[0], blocks[1], blocks[2], text, r['pos'] if r['n'] else []):
+                self.gvcf_f.write(piece)
+            self.gvcf_f.flush()
         for _ in grp:
             self.counter_Q.put(1)
 
@@ -454,9 +470,9 @@ class _Records:
         if self.pending is not None:
             self.pending.result()                                    # keeps the records in group order; re-raises errors
 
-    def submit(self, chrom, ploidy, r, grp):
+    def submit(self, chrom, ploidy, r, grp, blocks=None):
         self.wait()
-        self.pending = self.pool.submit(self.emit, chrom, ploidy, r, grp)
+        self.pending = self.pool.submit(self.emit, chrom, ploidy, r, grp, blocks)
 
 
 def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
@@ -487,8 +503,12 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
     # GPU idle meanwhile)
     piped = isinstance(params['sam_path'], str) and os.path.exists(params['sam_path']) and not os.environ.get('NC_SERIAL_INGEST')
     depth = max(1, int(os.environ.get('NC_CALLER_DEPTH', 2 if piped else 1)))
-    with open(curr_vcf_path, 'wb') as f, ThreadPoolExecutor(max_workers=1) as pool:
-        records = _Records(f, pool, counter_Q)
+    from contextlib import ExitStack
+    from . import gvcf
+    gvcf_cfg = gvcf.settings(params) if gvcf.enabled(params) else None          # (opt-in: <prefix>.<worker>.snps.g.vcf beside the worker's VCF)
+    with open(curr_vcf_path, 'wb') as f, ThreadPoolExecutor(max_workers=1) as pool, ExitStack() as stack:
+        gvcf_f = stack.enter_context(open(gvcf.worker_path(params, worker_id), 'wb')) if gvcf_cfg else None
+        records = _Records(f, pool, counter_Q, gvcf_f)
         ingest = _Ingest(params, keys, groups, device) if piped and keys else None
         in_flight = []                                               # groups whose kernels are queued and whose results have not been collected
         unrecorded = {}                                              # contig -> listed positions (params['genotype_sites']) inside its chunks that got no record
@@ -498,7 +518,12 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
             r = call.result()
             if r.get('genotype_listed'):
                 unrecorded[chrom] = unrecorded.get(chrom, 0) + r['genotype_listed'] - r['genotype_emitted']
-            records.submit(chrom, ploidy, r, grp)
+            held, blocks = r.pop('gvcf', None), None
+            if gvcf_cfg is not None and held is not None:
+                # blocks and their text on the device, cut at the positions of the lines this group gets (PASS or not)
+                blocks = gvcf.group_blocks(get_engine(device), held, chrom, ploidy != 'diploid', [(c['start'], c['end']) for c in grp],
+                                           r['pos'] if r['n'] else None, gvcf_cfg)
+            records.submit(chrom, ploidy, r, grp, blocks)
             if last_use[chrom] == gi:
                 # a genome is walked contig by contig: drop the decoded alignments and the HBM pack of the one just finished (on an
                 # ingest thread when there is one: unmapping ~100 MB takes 8 ms this thread would not be launching kernels)
@@ -548,7 +573,7 @@ def call_manager(params, devices=None):
     Under torch.distributed (one process per GPU, e.g. torchrun) every rank calls this function: the chunk list
     is sharded over the ranks, each rank works on ITS GPU (engine.local_device: LOCAL_RANK, or devices[local rank]) and
     writes its own worker file, rank 0 merges (other ranks return the path)."""
-    from . import shard
+    from . import gvcf, shard
     from .engine import local_device
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if (dist.is_available() and dist.is_initialized()) else (0, 1)
@@ -602,5 +627,9 @@ def call_manager(params, devices=None):
         vcfio.write_vcf_gz_with_csi(path, header, body, contigs, np.array([k[0] for k in recs], np.int64),
                                     np.array([k[1] for k in recs], np.int64), np.array([k[2] for k in recs], np.int64),
                                     np.array([len(k[4].encode()) for k in recs], np.int64))   # + <path>.csi (tabix -p vcf --csi)
+    if gvcf.enabled(params):
+        # <prefix>.snps.g.vcf.gz + .csi: every rank's blocks and variant lines (a block never spans two ranks' chunk runs)
+        gvcf.merge_worker_files([gvcf.worker_path(params, r + 1) for r in range(world)],
+                                os.path.join(params['vcf_path'], '%s.snps.g.vcf.gz' % params['prefix']), contigs, params['sample'])
     shard.barrier()
     return pass_path
