@@ -308,36 +308,15 @@ def lib():
         L.nc_bamidx_verify.argtypes = [vp, vp, i64, i64, i64, vp, i32, vp]
         L.nc_bamidx_serial.argtypes = [vp, vp, i64, i64, i32, vp, vp]
         L.nc_bamidx_fields.argtypes = [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-        L.nc_train_create.argtypes = [vp, i32, i64, C.POINTER(vp)]
-        L.nc_train_free.argtypes = [vp]
-        L.nc_train_set_weights.argtypes = [vp, vp, C.c_size_t]
-        L.nc_train_get_weights.argtypes = [vp, vp, C.c_size_t]
-        L.nc_train_forward.argtypes = [vp, i64, vp, vp, vp, vp, C.c_float, vp, vp]
-        L.nc_train_loss_grad.argtypes = [vp, i64, vp, vp, vp, vp, C.c_float, vp, C.c_float, vp, vp]
-        L.nc_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
-        L.nc_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-        L.nc_train_stage_ms.argtypes = [vp, i32, vp]
-        L.nc_indel_train_create.argtypes = [vp, i32, i64, i64, C.POINTER(vp)]
-        L.nc_indel_train_free.argtypes = [vp]
-        L.nc_indel_train_set_weights.argtypes = [vp, vp, C.c_size_t]
-        L.nc_indel_train_get_weights.argtypes = [vp, vp, C.c_size_t]
-        L.nc_indel_train_forward.argtypes = [vp, i64, vp, vp, C.c_float, vp]
-        L.nc_indel_train_loss_grad.argtypes = [vp, i64, vp, vp, C.c_float, vp, C.c_float, vp, vp]
-        L.nc_indel_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
-        L.nc_indel_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-        L.nc_indel_train_stage_ms.argtypes = [vp, i32, vp]
-        L.nc_hap_train_create.argtypes = [vp, i32, i64, C.POINTER(vp)]
-        L.nc_hap_train_free.argtypes = [vp]
-        L.nc_hap_train_set_weights.argtypes = [vp, vp, C.c_size_t]
-        L.nc_hap_train_get_weights.argtypes = [vp, vp, C.c_size_t]
-        L.nc_hap_train_forward.argtypes = [vp, i64, vp, vp, vp, vp, C.c_float, vp]
-        L.nc_hap_train_loss_grad.argtypes = [vp, i64, vp, vp, vp, vp, C.c_float, vp, C.c_float, vp, vp]
-        L.nc_hap_train_adam.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
-        L.nc_hap_train_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-        L.nc_hap_train_stage_ms.argtypes = [vp, i32, vp]
-        for fam in ("nc_hap_indel_train",):                             # the nc_indel_train_* family's signatures
-            for fn in ("create", "free", "set_weights", "get_weights", "forward", "loss_grad", "adam", "info", "stage_ms"):
-                getattr(L, "%s_%s" % (fam, fn)).argtypes = getattr(L, "nc_indel_train_" + fn).argtypes
+        # the four trainers: the SNP family takes ref_code and scale behind x, the indel family slice_sites at create; nc_train_forward has gt_dev
+        f32 = C.c_float
+        for fam, snp in (("nc_train", True), ("nc_hap_train", True), ("nc_indel_train", False), ("nc_hap_indel_train", False)):
+            site = [vp, i64, vp] + ([vp, vp] if snp else []) + [vp, f32]        # handle, n, x (, ref_code, scale), keep mask, keep
+            sig = dict(create=[vp, i32, i64] + ([] if snp else [i64]) + [C.POINTER(vp)], free=[vp], set_weights=[vp, vp, C.c_size_t],
+                       get_weights=[vp, vp, C.c_size_t], forward=site + [vp] + ([vp] if fam == "nc_train" else []), loss_grad=site + [vp, f32, vp, vp],
+                       adam=[vp, f32, f32, f32, f32], info=[vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)], stage_ms=[vp, i32, vp])
+            for fn, argtypes in sig.items():
+                getattr(L, "%s_%s" % (fam, fn)).argtypes = argtypes
         L.nc_refconf_columns.argtypes = [vp, C.POINTER(ReadPackC), vp, i32, i64, vp]
         L.nc_refconf_blocks.argtypes = [vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, C.POINTER(RefconfParamsC), C.POINTER(i64)]
         L.nc_refconf_fetch.argtypes = [vp, vp]

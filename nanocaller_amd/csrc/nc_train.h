@@ -1,5 +1,7 @@
-// What the training units share (nc_train.hip: the diploid SNP model, nc_train_indel.hip: the diploid indel model): SELU's derivative and the
-// shape-templated kernels of the 2x3 stride-(1,2) convolutions.  Each unit instantiates them in its own anonymous namespace.
+// What the four training units share (nc_train.hip, nc_train_hap.hip: the diploid and haploid SNP models through nc_train_snp.h;
+// nc_train_indel.hip, nc_train_hap_indel.hip: the two indel models through nc_train_indel.h): SELU's derivative, the shape-templated kernels of the
+// 2x3 stride-(1,2) convolutions, and the family-independent host half of a handle (train_state and the train_* functions at the end).
+// Each unit instantiates the kernels in its own anonymous namespace.
 // SLAB = sites per gradient slab, NPAR = floats per slab (the stride of `slabs`): template parameters here, constants of the including unit.
 // lane l of an MFMA: A[row l&15][k l>>4], B[k l>>4][col l&15], C/D col l&15, row 4*(l>>4)+r (the lane maps of nc_cnn_fp32.hip).
 #pragma once
@@ -212,6 +214,184 @@ __global__ __launch_bounds__(256) void k_bias_grad(const float *__restrict__ d, 
         for (int k = 1; k < NP; k++) v += red[k][c];
         slabs[(int64_t)blockIdx.x * NPAR + boff + c] = v;
     }
+}
+
+// ------------------------------------------------------------------------------------- the host side of a handle, whatever the model family
+enum { TS_FWD = 0, TS_HEADS, TS_FC1, TS_CONV3, TS_CONV2, TS_CONV1, TS_PARAMS, TS_N };
+
+// A family derives its state from this and adds the pointers of its workspace buffers.
+struct train_state {
+    nc_ctx *ctx = nullptr;
+    int64_t max_batch = 0, slice = 0;
+    size_t ws_bytes = 0;
+    float *w = nullptr, *m = nullptr, *v = nullptr, *g = nullptr;      // fp32 state in blob order
+    float *ws = nullptr;                                               // one allocation: the family's buffers
+    int64_t t = 0;                                                     // Adam steps taken
+    // the gradient of the last loss_grad = g (what of it the family keeps there; with `partial` also the earlier slices' sums) + the pending
+    // slabs + gamma w: summed by the adam call's own kernel
+    bool have_grad = false, partial = false;
+    int pending_ns = 0;
+    float pending_gamma = 0.0f;
+    int timing = 0;
+    hipEvent_t ev[TS_N + 1] = {nullptr};
+};
+
+inline void train_mark(train_state *tr, int i)
+{
+    if (tr->timing) (void)hipEventRecord(tr->ev[i], tr->ctx->stream);
+}
+
+// The allocations and events of a handle whose ctx, max_batch and slice are set: *ptrs[i] = sizes[i] floats of one allocation, each piece
+// rounded up to 64 floats, and w | m | v | g = 4 npar zeroed floats of another.  After a failure the caller calls train_release.
+template <size_t N>
+inline int train_alloc(train_state *tr, const char *name, int npar, const size_t (&sizes)[N], float **const (&ptrs)[N])
+{
+    nc_ctx *ctx = tr->ctx;
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    size_t total = 0;
+    for (size_t s : sizes) total += (s + 63) & ~size_t(63);
+    tr->ws_bytes = total * 4;
+    hipError_t e = hipMalloc((void **)&tr->ws, tr->ws_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&tr->w, (size_t)npar * 4 * 4);
+    if (e != hipSuccess) return nc_fail(ctx, NC_ERR_NOMEM, "%s_create: hipMalloc of %zu bytes: %s", name, total * 4, hipGetErrorString(e));
+    tr->m = tr->w + npar;
+    tr->v = tr->m + npar;
+    tr->g = tr->v + npar;
+    size_t off = 0;
+    for (size_t i = 0; i < N; i++) {
+        *ptrs[i] = tr->ws + off;
+        off += (sizes[i] + 63) & ~size_t(63);
+    }
+    NC_HIP(ctx, hipMemsetAsync(tr->w, 0, (size_t)npar * 4 * 4, ctx->stream));
+    for (int i = 0; i <= TS_N; i++) NC_HIP(ctx, hipEventCreate(&tr->ev[i]));
+    return NC_OK;
+}
+
+// (also after a train_alloc that failed half way: every member is null or owned)
+inline void train_release(train_state *tr)
+{
+    (void)hipSetDevice(tr->ctx->device);
+    (void)hipStreamSynchronize(tr->ctx->stream);
+    for (int i = 0; i <= TS_N; i++)
+        if (tr->ev[i]) (void)hipEventDestroy(tr->ev[i]);
+    if (tr->ws) (void)hipFree(tr->ws);
+    if (tr->w) (void)hipFree(tr->w);
+}
+
+// What every create() does around train_alloc: H is the handle type of the ABI, a family's state and nothing more; init(tr) sets the slice
+// and allocates.
+template <class H, class Init>
+inline int train_create(nc_ctx *ctx, int64_t max_batch, H **out, Init init)
+{
+    H *tr = new H;
+    tr->ctx = ctx;
+    tr->max_batch = max_batch;
+    const int rc = init(tr);
+    if (rc != NC_OK) {
+        train_release(tr);
+        delete tr;
+        return rc;
+    }
+    *out = tr;
+    return NC_OK;
+}
+
+template <class H>
+inline int train_free(H *tr)
+{
+    if (!tr) return NC_OK;
+    train_release(tr);
+    delete tr;
+    return NC_OK;
+}
+
+inline int train_check_call(train_state *tr, const char *name, const char *fn, int64_t n, bool have_inputs, float keep)
+{
+    if (!tr) return NC_ERR_ARG;
+    if (n < 1 || n > tr->max_batch)
+        return nc_fail(tr->ctx, NC_ERR_ARG, "%s_%s: n = %lld outside 1 .. max_batch = %lld", name, fn, (long long)n, (long long)tr->max_batch);
+    if (!have_inputs) return nc_fail(tr->ctx, NC_ERR_ARG, "%s_%s: null argument", name, fn);
+    if (!(keep > 0.0f && keep <= 1.0f)) return nc_fail(tr->ctx, NC_ERR_ARG, "%s_%s: keep = %g outside (0, 1]", name, fn, (double)keep);
+    return NC_OK;
+}
+
+inline int train_set_weights(train_state *tr, const char *name, int npar, const float *blob_host, size_t n_floats)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (!blob_host || n_floats != (size_t)npar) return nc_fail(ctx, NC_ERR_ARG, "%s_set_weights: expects %d floats", name, npar);
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    NC_HIP(ctx, hipMemcpyAsync(tr->w, blob_host, (size_t)npar * 4, hipMemcpyHostToDevice, ctx->stream));
+    NC_HIP(ctx, hipMemsetAsync(tr->m, 0, (size_t)npar * 4 * 3, ctx->stream));
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    tr->t = 0;
+    tr->have_grad = false;
+    return NC_OK;
+}
+
+inline int train_get_weights(train_state *tr, const char *name, int npar, float *blob_host, size_t n_floats)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (!blob_host || n_floats != (size_t)npar) return nc_fail(ctx, NC_ERR_ARG, "%s_get_weights: expects %d floats", name, npar);
+    NC_HIP(ctx, hipSetDevice(ctx->device));
+    NC_HIP(ctx, hipMemcpyAsync(blob_host, tr->w, (size_t)npar * 4, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NC_OK;
+}
+
+// The end of a loss_grad whose kernels are enqueued: lossv = the `nloss` loss terms on the device.  With `bad_labels` (what a bad label is, for
+// the error text) lossv[nloss] is the flag the heads kernel sets for a label outside the classes: the labels are on the device, so the call
+// always waits, and a bad label leaves no gradient pending.  Without, it waits only when the caller wants the losses.
+inline int train_finish_loss_grad(train_state *tr, const char *name, const float *lossv, int nloss, const char *bad_labels, float *loss_host)
+{
+    nc_ctx *ctx = tr->ctx;
+    hipStream_t st = ctx->stream;
+    if (bad_labels) {
+        float l[8] = {0.0f};
+        NC_HIP(ctx, hipMemcpyAsync(l, lossv, (size_t)(nloss + 1) * 4, hipMemcpyDeviceToHost, st));
+        NC_HIP(ctx, hipStreamSynchronize(st));
+        if (l[nloss] != 0.0f) return nc_fail(ctx, NC_ERR_ARG, "%s_loss_grad: a label outside %s", name, bad_labels);
+        tr->have_grad = true;
+        for (int i = 0; loss_host && i < nloss; i++) loss_host[i] = l[i];
+        return NC_OK;
+    }
+    tr->have_grad = true;
+    if (loss_host) {
+        NC_HIP(ctx, hipMemcpyAsync(loss_host, lossv, (size_t)nloss * 4, hipMemcpyDeviceToHost, st));
+        NC_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return NC_OK;
+}
+
+// Adam's step size in TensorFlow's form after `t` steps
+inline float train_lr_t(float lr, float beta1, float beta2, int64_t t)
+{
+    return (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)t)) / (1.0 - std::pow((double)beta1, (double)t)));
+}
+
+inline int train_info(train_state *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps)
+{
+    if (!tr) return NC_ERR_ARG;
+    if (slice_sites) *slice_sites = tr->slice;
+    if (workspace_bytes) *workspace_bytes = (int64_t)tr->ws_bytes;
+    if (steps) *steps = tr->t;
+    return NC_OK;
+}
+
+inline int train_stage_ms(train_state *tr, int32_t on, float *ms7)
+{
+    if (!tr) return NC_ERR_ARG;
+    nc_ctx *ctx = tr->ctx;
+    if (ms7 && tr->timing) {
+        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < TS_N; i++) {
+            ms7[i] = 0.0f;
+            NC_HIP(ctx, hipEventElapsedTime(&ms7[i], tr->ev[i], tr->ev[i + 1]));
+        }
+    }
+    tr->timing = on;
+    return NC_OK;
 }
 
 }   // namespace

@@ -6,11 +6,12 @@
 //
 //   forward     the trunk of nc_train_snp.h (k_scale_x, k_conv1_fwd, k_conv23_fwd x 2, k_fc1_fwd), k_heads
 //   backward    k_heads (loss -> d fc1, one site per lane; through fc3's SELU), k_small_wgrad (fc1's bias, fc2, fc3: 916 parameters),
-//               the trunk's gradient kernels (snp_trunk_backward)
-//   parameters  k_loss_reduce (cost, CE), k_params (slab sum + gamma w on kernel entries + Adam step)
+//               the trunk's gradient kernels (nc_train_snp.h)
+//   parameters  k_loss_reduce (cost, CE), k_params (slab sum + gamma w on kernel entries + Adam step; nc_train_snp.h)
 //
 // Sums over sites run in a fixed order, as in nc_train.hip: slabs of SLAB = 64 sites in blob order, one lane of one workgroup per parameter,
 // waves combined through LDS in wave order, slabs and slices added in order.  No atomics.  Sites past n are never read.
+// The host side of a handle is snp_train<unit> of nc_train_snp.h; here are the kernels behind fc1 and the unit that names this blob.
 #include "nc_train_snp.h"
 
 namespace {
@@ -142,261 +143,57 @@ __global__ __launch_bounds__(256) void k_loss_reduce(const float *__restrict__ l
     }
 }
 
-// One parameter per lane, k_params of nc_train.hip for this blob: gradient = g_in (earlier slices, may be NULL) + the slabs in slab order
-// (+ gamma w on kernel entries with `reg`); written to g_out (may be NULL); with `step` the Adam update in TensorFlow's form.
-__global__ __launch_bounds__(256) void k_params(const float *__restrict__ g_in, const float *__restrict__ slabs, int ns, int reg, float gamma,
-                                                float *__restrict__ g_out, int step, float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
-                                                float lr_t, float b1, float b2, float eps)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= NPAR) return;
-    float g = g_in ? g_in[i] : 0.0f;
-    for (int k = 0; k < ns; k++) g += slabs[(int64_t)k * NPAR + i];
-    const float wi = w[i];
-    if (reg && !is_bias(i)) g = fmaf(gamma, wi, g);
-    if (g_out) g_out[i] = g;
-    if (step) {
-        const float mi = fmaf(b1, m[i], (1.0f - b1) * g), vi = fmaf(b2, v[i], (1.0f - b2) * g * g);
-        m[i] = mi;
-        v[i] = vi;
-        w[i] = wi - lr_t * mi / (sqrtf(vi) + eps);
+struct unit {
+    static constexpr const char *NAME = "nc_hap_train", *MODEL = "haploid SNP", *BAD_LABELS = "0 .. 3 (A0 G1 T2 C3)";
+    static constexpr int KIND = NC_MODEL_SNP_HAP, NPAR = ::NPAR, TA = ::TA, TD = ::TD, NSMALL = ::NSMALL, NLAB = 1, NLOSS = 2;
+    __device__ static __forceinline__ bool is_bias(int i) { return ::is_bias(i); }
+    static void heads(snp_train_state *tr, hipStream_t st, int64_t nb, const int32_t *ref_code, const uint8_t *mask, float inv_keep, const uint8_t *label,
+                      float inv_n, float *probs, float *, float *loss)
+    {
+        hipLaunchKernelGGL(k_heads, dim3(blocks_for(nb, 64)), dim3(64), 0, st, tr->f1, tr->f1d, tr->w, ref_code, mask, inv_keep, label, inv_n, nb, probs, tr->tact,
+                           tr->tdel, tr->df1, loss, tr->lossv + NLOSS);
     }
-}
-
-}   // namespace
-
-enum { TS_FWD = 0, TS_HEADS, TS_FC1, TS_CONV3, TS_CONV2, TS_CONV1, TS_PARAMS, TS_N };
-
-struct nc_hap_train {
-    nc_ctx *ctx = nullptr;
-    int64_t max_batch = 0, slice = 0;
-    size_t ws_bytes = 0;
-    float *w = nullptr, *m = nullptr, *v = nullptr, *g = nullptr;      // fp32 state in blob order
-    float *ws = nullptr;                                               // one allocation: the buffers below
-    float *xs, *a1, *a2, *a3, *f1, *f1d, *tact, *tdel, *df1, *d1, *d2, *d3, *slabs, *loss, *loss2;   // loss2: cost, CE, bad-label flag
-    int64_t t = 0;                                                     // Adam steps taken
-    // the gradient of the last nc_hap_train_loss_grad = (partial ? g : 0) + the pending slabs + gamma w: summed by nc_hap_train_adam's own kernel
-    bool have_grad = false, partial = false;
-    int pending_ns = 0;
-    float pending_gamma = 0.0f;
-    int timing = 0;
-    hipEvent_t ev[TS_N + 1] = {nullptr};
+    static void small_wgrad(snp_train_state *tr, hipStream_t st, unsigned ns, const int32_t *ref_code, int64_t nb)
+    {
+        hipLaunchKernelGGL(k_small_wgrad, dim3(ns, blocks_for(NSMALL)), dim3(256), 0, st, tr->tact, tr->tdel, tr->df1, ref_code, nb, tr->slabs);
+    }
+    static void loss_reduce(snp_train_state *tr, hipStream_t st, int64_t n, float gamma)
+    {
+        hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, st, tr->loss, n, tr->w, gamma, tr->lossv);
+    }
 };
-
-namespace {
-
-void mark(nc_hap_train *tr, int i)
-{
-    if (tr->timing) (void)hipEventRecord(tr->ev[i], tr->ctx->stream);
-}
-
-int check_call(nc_hap_train *tr, const char *what, int64_t n, const void *x, const void *rc, float keep)
-{
-    if (!tr) return NC_ERR_ARG;
-    if (n < 1 || n > tr->max_batch) return nc_fail(tr->ctx, NC_ERR_ARG, "%s: n = %lld outside 1 .. max_batch = %lld", what, (long long)n, (long long)tr->max_batch);
-    if (!x || !rc) return nc_fail(tr->ctx, NC_ERR_ARG, "%s: null argument", what);
-    if (!(keep > 0.0f && keep <= 1.0f)) return nc_fail(tr->ctx, NC_ERR_ARG, "%s: keep = %g outside (0, 1]", what, (double)keep);
-    return NC_OK;
-}
-
-snp_trunk_ws trunk_of(nc_hap_train *tr)
-{
-    return {tr->w, tr->xs, tr->a1, tr->a2, tr->a3, tr->f1, tr->f1d, tr->df1, tr->d1, tr->d2, tr->d3, tr->slabs};
-}
+using T = snp_train<unit>;
 
 }   // namespace
+
+struct nc_hap_train : snp_train_state {};
 
 extern "C" {
 
-int nc_hap_train_create(nc_ctx *ctx, int32_t kind, int64_t max_batch, nc_hap_train **out)
-{
-    if (!ctx || !out) return NC_ERR_ARG;
-    *out = nullptr;
-    if (kind != NC_MODEL_SNP_HAP)
-        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_hap_train_create: only the haploid SNP model (kind %d) is trained here, not kind %d", NC_MODEL_SNP_HAP, kind);
-    if (max_batch < 1) return nc_fail(ctx, NC_ERR_ARG, "nc_hap_train_create: max_batch");
-    NC_HIP(ctx, hipSetDevice(ctx->device));
-    nc_hap_train *tr = new nc_hap_train;
-    tr->ctx = ctx;
-    tr->max_batch = max_batch;
-    tr->slice = max_batch < MAX_SLICE ? max_batch : MAX_SLICE;
-    const size_t sl = (size_t)tr->slice, ns = (sl + SLAB - 1) / SLAB;
-    size_t sizes[] = {sl * XS, sl * N1, sl * N2, sl * N3, sl * 48, sl * 48, sl * TA, sl * TD, sl * 48, sl * N1, sl * N2, sl * N3, ns * NPAR, (size_t)max_batch, 8};
-    float **ptrs[] = {&tr->xs, &tr->a1, &tr->a2, &tr->a3, &tr->f1, &tr->f1d, &tr->tact, &tr->tdel, &tr->df1, &tr->d1, &tr->d2, &tr->d3, &tr->slabs, &tr->loss, &tr->loss2};
-    size_t total = 0;
-    for (size_t s : sizes) total += (s + 63) & ~size_t(63);
-    tr->ws_bytes = total * 4;
-    hipError_t e = hipMalloc((void **)&tr->ws, tr->ws_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&tr->w, (size_t)NPAR * 4 * 4);
-    if (e != hipSuccess) {
-        if (tr->ws) (void)hipFree(tr->ws);
-        delete tr;
-        return nc_fail(ctx, NC_ERR_NOMEM, "nc_hap_train_create: hipMalloc of %zu bytes: %s", total * 4, hipGetErrorString(e));
-    }
-    tr->m = tr->w + NPAR;
-    tr->v = tr->m + NPAR;
-    tr->g = tr->v + NPAR;
-    size_t off = 0;
-    for (size_t i = 0; i < sizeof sizes / sizeof sizes[0]; i++) {
-        *ptrs[i] = tr->ws + off;
-        off += (sizes[i] + 63) & ~size_t(63);
-    }
-    e = hipMemsetAsync(tr->w, 0, (size_t)NPAR * 4 * 4, ctx->stream);
-    for (int i = 0; i <= TS_N && e == hipSuccess; i++) e = hipEventCreate(&tr->ev[i]);
-    if (e != hipSuccess) {
-        (void)nc_hap_train_free(tr);                                    // (frees what exists: the two allocations and the events made so far)
-        return nc_fail(ctx, NC_ERR_HIP, "nc_hap_train_create: %s", hipGetErrorString(e));
-    }
-    *out = tr;
-    return NC_OK;
-}
-
-int nc_hap_train_free(nc_hap_train *tr)
-{
-    if (!tr) return NC_OK;
-    (void)hipSetDevice(tr->ctx->device);
-    (void)hipStreamSynchronize(tr->ctx->stream);
-    for (int i = 0; i <= TS_N; i++)
-        if (tr->ev[i]) (void)hipEventDestroy(tr->ev[i]);
-    if (tr->ws) (void)hipFree(tr->ws);
-    if (tr->w) (void)hipFree(tr->w);
-    delete tr;
-    return NC_OK;
-}
-
-int nc_hap_train_set_weights(nc_hap_train *tr, const float *blob_host, size_t n_floats)
-{
-    if (!tr) return NC_ERR_ARG;
-    nc_ctx *ctx = tr->ctx;
-    if (!blob_host || n_floats != (size_t)NPAR) return nc_fail(ctx, NC_ERR_ARG, "nc_hap_train_set_weights: expects %d floats", NPAR);
-    NC_HIP(ctx, hipSetDevice(ctx->device));
-    NC_HIP(ctx, hipMemcpyAsync(tr->w, blob_host, (size_t)NPAR * 4, hipMemcpyHostToDevice, ctx->stream));
-    NC_HIP(ctx, hipMemsetAsync(tr->m, 0, (size_t)NPAR * 4 * 3, ctx->stream));
-    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    tr->t = 0;
-    tr->have_grad = false;
-    return NC_OK;
-}
-
-int nc_hap_train_get_weights(nc_hap_train *tr, float *blob_host, size_t n_floats)
-{
-    if (!tr) return NC_ERR_ARG;
-    nc_ctx *ctx = tr->ctx;
-    if (!blob_host || n_floats != (size_t)NPAR) return nc_fail(ctx, NC_ERR_ARG, "nc_hap_train_get_weights: expects %d floats", NPAR);
-    NC_HIP(ctx, hipSetDevice(ctx->device));
-    NC_HIP(ctx, hipMemcpyAsync(blob_host, tr->w, (size_t)NPAR * 4, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NC_OK;
-}
+int nc_hap_train_create(nc_ctx *ctx, int32_t kind, int64_t max_batch, nc_hap_train **out) { return T::create(ctx, kind, max_batch, out); }
+int nc_hap_train_free(nc_hap_train *tr) { return train_free(tr); }
+int nc_hap_train_set_weights(nc_hap_train *tr, const float *blob_host, size_t n_floats) { return train_set_weights(tr, unit::NAME, NPAR, blob_host, n_floats); }
+int nc_hap_train_get_weights(nc_hap_train *tr, float *blob_host, size_t n_floats) { return train_get_weights(tr, unit::NAME, NPAR, blob_host, n_floats); }
 
 int nc_hap_train_forward(nc_hap_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
                          float keep, float *probs_dev)
 {
-    NC_TRY(check_call(tr, "nc_hap_train_forward", n, x_dev, ref_code_dev, keep));
-    nc_ctx *ctx = tr->ctx;
-    if (!probs_dev) return nc_fail(ctx, NC_ERR_ARG, "nc_hap_train_forward: null argument");
-    NC_HIP(ctx, hipSetDevice(ctx->device));
-    if (keep == 1.0f) keep_mask_dev = nullptr;
-    for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
-        const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
-        snp_trunk_forward(trunk_of(tr), ctx->stream, nb, x_dev + s0 * NC_SNP_TENSOR, scale_dev ? scale_dev + s0 : nullptr);
-        hipLaunchKernelGGL(k_heads, dim3(blocks_for(nb, 64)), dim3(64), 0, ctx->stream, tr->f1, tr->f1d, tr->w, ref_code_dev + s0,
-                           keep_mask_dev ? keep_mask_dev + s0 * 48 : nullptr, 1.0f / keep, (const uint8_t *)nullptr, 0.0f, nb, probs_dev + s0 * 4, tr->tact,
-                           tr->tdel, tr->df1, tr->loss, tr->loss2 + 2);
-    }
-    NC_HIP(ctx, hipGetLastError());
-    return NC_OK;
+    return T::forward(tr, n, x_dev, ref_code_dev, scale_dev, keep_mask_dev, keep, probs_dev, nullptr);
 }
 
 int nc_hap_train_loss_grad(nc_hap_train *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
                            float keep, const uint8_t *label_dev, float gamma, float *loss2_host, float *grad_dev)
 {
-    NC_TRY(check_call(tr, "nc_hap_train_loss_grad", n, x_dev, ref_code_dev, keep));
-    nc_ctx *ctx = tr->ctx;
-    if (!label_dev) return nc_fail(ctx, NC_ERR_ARG, "nc_hap_train_loss_grad: null argument");
-    NC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (keep == 1.0f) keep_mask_dev = nullptr;
-    tr->have_grad = tr->partial = false;
-    NC_HIP(ctx, hipMemsetAsync(tr->loss2, 0, 8 * 4, st));
-    for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
-        const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
-        const unsigned ns = (unsigned)((nb + SLAB - 1) / SLAB);
-        const float *x = x_dev + s0 * NC_SNP_TENSOR;
-        mark(tr, TS_FWD);
-        snp_trunk_forward(trunk_of(tr), st, nb, x, scale_dev ? scale_dev + s0 : nullptr);
-        mark(tr, TS_HEADS);
-        hipLaunchKernelGGL(k_heads, dim3(blocks_for(nb, 64)), dim3(64), 0, st, tr->f1, tr->f1d, tr->w, ref_code_dev + s0,
-                           keep_mask_dev ? keep_mask_dev + s0 * 48 : nullptr, 1.0f / keep, label_dev + s0, 1.0f / (float)n, nb, (float *)nullptr, tr->tact,
-                           tr->tdel, tr->df1, tr->loss + s0, tr->loss2 + 2);
-        hipLaunchKernelGGL(k_small_wgrad, dim3(ns, blocks_for(NSMALL)), dim3(256), 0, st, tr->tact, tr->tdel, tr->df1, ref_code_dev + s0, nb, tr->slabs);
-        snp_trunk_backward<NPAR>(trunk_of(tr), st, nb, scale_dev ? tr->xs : x, scale_dev ? XS : 1025, [&](int i) { mark(tr, TS_FC1 + i); });
-        mark(tr, TS_PARAMS);
-        if (s0 + nb < n) {                                              // not the last slice: fold its slabs into g, the workspace is reused
-            hipLaunchKernelGGL(k_params, dim3(blocks_for(NPAR)), dim3(256), 0, st, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, (int)ns, 0, 0.0f,
-                               tr->g, 0, tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
-            tr->partial = true;
-        } else {
-            tr->pending_ns = (int)ns;
-            tr->pending_gamma = gamma;
-        }
-    }
-    if (grad_dev)
-        hipLaunchKernelGGL(k_params, dim3(blocks_for(NPAR)), dim3(256), 0, st, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, tr->pending_ns, 1, gamma,
-                           grad_dev, 0, tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
-    hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, st, tr->loss, n, tr->w, gamma, tr->loss2);
-    mark(tr, TS_N);
-    NC_HIP(ctx, hipGetLastError());
-    // the labels are on the device: the flag k_heads sets comes back with the losses, so this call always waits
-    float l3[3] = {0.0f, 0.0f, 0.0f};
-    NC_HIP(ctx, hipMemcpyAsync(l3, tr->loss2, 3 * 4, hipMemcpyDeviceToHost, st));
-    NC_HIP(ctx, hipStreamSynchronize(st));
-    if (l3[2] != 0.0f) return nc_fail(ctx, NC_ERR_ARG, "nc_hap_train_loss_grad: a label outside 0 .. 3 (A0 G1 T2 C3)");
-    tr->have_grad = true;
-    if (loss2_host) {
-        loss2_host[0] = l3[0];
-        loss2_host[1] = l3[1];
-    }
-    return NC_OK;
+    return T::loss_grad(tr, n, x_dev, ref_code_dev, scale_dev, keep_mask_dev, keep, label_dev, gamma, loss2_host, grad_dev);
 }
 
-int nc_hap_train_adam(nc_hap_train *tr, float lr, float beta1, float beta2, float eps)
-{
-    if (!tr) return NC_ERR_ARG;
-    nc_ctx *ctx = tr->ctx;
-    if (!tr->have_grad) return nc_fail(ctx, NC_ERR_STATE, "nc_hap_train_adam: no gradient (nc_hap_train_loss_grad comes first, once per step)");
-    NC_HIP(ctx, hipSetDevice(ctx->device));
-    tr->t++;
-    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)tr->t)) / (1.0 - std::pow((double)beta1, (double)tr->t)));
-    hipLaunchKernelGGL(k_params, dim3(blocks_for(NPAR)), dim3(256), 0, ctx->stream, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, tr->pending_ns, 1,
-                       tr->pending_gamma, (float *)nullptr, 1, tr->w, tr->m, tr->v, lr_t, beta1, beta2, eps);
-    NC_HIP(ctx, hipGetLastError());
-    tr->have_grad = false;
-    return NC_OK;
-}
+int nc_hap_train_adam(nc_hap_train *tr, float lr, float beta1, float beta2, float eps) { return T::adam(tr, lr, beta1, beta2, eps); }
 
 int nc_hap_train_info(nc_hap_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps)
 {
-    if (!tr) return NC_ERR_ARG;
-    if (slice_sites) *slice_sites = tr->slice;
-    if (workspace_bytes) *workspace_bytes = (int64_t)tr->ws_bytes;
-    if (steps) *steps = tr->t;
-    return NC_OK;
+    return train_info(tr, slice_sites, workspace_bytes, steps);
 }
 
-int nc_hap_train_stage_ms(nc_hap_train *tr, int32_t on, float *ms7)
-{
-    if (!tr) return NC_ERR_ARG;
-    nc_ctx *ctx = tr->ctx;
-    if (ms7 && tr->timing) {
-        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < TS_N; i++) {
-            ms7[i] = 0.0f;
-            NC_HIP(ctx, hipEventElapsedTime(&ms7[i], tr->ev[i], tr->ev[i + 1]));
-        }
-    }
-    tr->timing = on;
-    return NC_OK;
-}
+int nc_hap_train_stage_ms(nc_hap_train *tr, int32_t on, float *ms7) { return train_stage_ms(tr, on, ms7); }
 
 }   // extern "C"

@@ -448,23 +448,8 @@ __global__ __launch_bounds__(256) void k_params(const float *__restrict__ gacc, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the host side of a handle
-enum { TS_FWD = 0, TS_HEADS, TS_FC1, TS_CONV3, TS_CONV2, TS_CONV1, TS_PARAMS, TS_N };
-
-struct indel_train_state {
-    nc_ctx *ctx = nullptr;
-    int64_t max_batch = 0, slice = 0;
-    size_t ws_bytes = 0;
-    float *w = nullptr, *m = nullptr, *v = nullptr, *g = nullptr;      // fp32 state in blob order
-    float *ws = nullptr;                                               // one allocation: the buffers below
+struct indel_train_state : train_state {
     float *a1, *a2, *a3, *f1, *f1d, *tact, *tdel, *df1, *d1, *d2, *d3, *slabs, *loss, *loss2, *wsq;   // loss2: cost, CE, the bad-label flag
-    int64_t t = 0;                                                     // Adam steps taken
-    // the gradient of the last loss_grad = g (fc1's kernel; with `partial` also the other parameters of the earlier slices) + the pending
-    // slabs + gamma w: summed by the adam call's own kernel
-    bool have_grad = false, partial = false;
-    int pending_ns = 0;
-    float pending_gamma = 0.0f;
-    int timing = 0;
-    hipEvent_t ev[TS_N + 1] = {nullptr};
 };
 
 inline dim3 tile_grid(int64_t npos)
@@ -473,29 +458,14 @@ inline dim3 tile_grid(int64_t npos)
     return dim3((unsigned)(t < 2048 ? t : 2048));
 }
 
-// A unit U names its blob (U::B), its entry points' prefix (U::NAME), whether a label outside the classes is looked for on the device
-// (U::CHECK_LABELS: the flag in loss2[2] that U::heads sets; the call then always waits), how many 16-row tiles of fc1's weight gradient a
-// workgroup owns (U::FCW_J) and launches its k_heads:
+// A unit U names its blob (U::B), its entry points' prefix (U::NAME), the model it accepts (U::KIND, U::MODEL), what a label outside the classes
+// is called where one is looked for on the device (U::BAD_LABELS, else null: the flag in loss2[2] that U::heads sets; the call then always
+// waits), how many 16-row tiles of fc1's weight gradient a workgroup owns (U::FCW_J) and launches its k_heads:
 //   static void heads(indel_train_state *, hipStream_t, int64_t nb, const uint8_t *mask, float inv_keep, const uint8_t *label, float inv_n,
 //                     float *probs, float *loss)
 template <class U>
 struct indel_train {
     using B = typename U::B;
-
-    static void mark(indel_train_state *tr, int i)
-    {
-        if (tr->timing) (void)hipEventRecord(tr->ev[i], tr->ctx->stream);
-    }
-
-    static int check_call(indel_train_state *tr, const char *fn, int64_t n, const void *x, float keep)
-    {
-        if (!tr) return NC_ERR_ARG;
-        if (n < 1 || n > tr->max_batch)
-            return nc_fail(tr->ctx, NC_ERR_ARG, "%s_%s: n = %lld outside 1 .. max_batch = %lld", U::NAME, fn, (long long)n, (long long)tr->max_batch);
-        if (!x) return nc_fail(tr->ctx, NC_ERR_ARG, "%s_%s: null argument", U::NAME, fn);
-        if (!(keep > 0.0f && keep <= 1.0f)) return nc_fail(tr->ctx, NC_ERR_ARG, "%s_%s: keep = %g outside (0, 1]", U::NAME, fn, (double)keep);
-        return NC_OK;
-    }
 
     // conv1 - fc1 of `nb` sites (a slice) into the workspace
     static void forward_trunk(indel_train_state *tr, int64_t nb, const float *x)
@@ -507,78 +477,30 @@ struct indel_train {
         hipLaunchKernelGGL(k_fc1_fwd<B::NF>, dim3(blocks_for(nb, 16)), dim3(64 * FW), 0, st, tr->a3, tr->w + O_KF, tr->w + B::O_BF, tr->f1, tr->f1d, nb);
     }
 
-    // the state of a handle that create() has checked the kind of: allocations, events
-    static int init(indel_train_state *tr, nc_ctx *ctx, int64_t max_batch, int64_t slice_sites)
+    template <class H>
+    static int create(nc_ctx *ctx, int32_t kind, int64_t max_batch, int64_t slice_sites, H **out)
     {
-        NC_HIP(ctx, hipSetDevice(ctx->device));
-        tr->ctx = ctx;
-        tr->max_batch = max_batch;
-        tr->slice = slice_sites > 0 ? slice_sites : DEFAULT_SLICE;
-        if (tr->slice > max_batch) tr->slice = max_batch;
-        const size_t sl = (size_t)tr->slice, ns = (sl + SLAB - 1) / SLAB;
-        size_t sizes[] = {sl * B::N1, sl * B::N2, sl * B::NF, sl * F1, sl * F1, sl * B::TA, sl * B::TD, sl * F1, sl * B::N1, sl * B::N2, sl * B::NF, ns * B::NSM,
-                          (size_t)max_batch, 8, 2 * WSQ_BLOCKS};
-        float **ptrs[] = {&tr->a1, &tr->a2, &tr->a3, &tr->f1, &tr->f1d, &tr->tact, &tr->tdel, &tr->df1, &tr->d1, &tr->d2, &tr->d3, &tr->slabs, &tr->loss, &tr->loss2, &tr->wsq};
-        size_t total = 0;
-        for (size_t s : sizes) total += (s + 63) & ~size_t(63);
-        tr->ws_bytes = total * 4;
-        hipError_t e = hipMalloc((void **)&tr->ws, tr->ws_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&tr->w, (size_t)B::NPAR * 4 * 4);
-        if (e != hipSuccess) return nc_fail(ctx, NC_ERR_NOMEM, "%s_create: hipMalloc of %zu bytes: %s", U::NAME, total * 4, hipGetErrorString(e));
-        tr->m = tr->w + B::NPAR;
-        tr->v = tr->m + B::NPAR;
-        tr->g = tr->v + B::NPAR;
-        size_t off = 0;
-        for (size_t i = 0; i < sizeof sizes / sizeof sizes[0]; i++) {
-            *ptrs[i] = tr->ws + off;
-            off += (sizes[i] + 63) & ~size_t(63);
-        }
-        NC_HIP(ctx, hipMemsetAsync(tr->w, 0, (size_t)B::NPAR * 4 * 4, ctx->stream));
-        for (int i = 0; i <= TS_N; i++) NC_HIP(ctx, hipEventCreate(&tr->ev[i]));
-        return NC_OK;
-    }
-
-    // (also what create() calls when init() has failed half way: every member is null or owned)
-    static void release(indel_train_state *tr)
-    {
-        (void)hipSetDevice(tr->ctx->device);
-        (void)hipStreamSynchronize(tr->ctx->stream);
-        for (int i = 0; i <= TS_N; i++)
-            if (tr->ev[i]) (void)hipEventDestroy(tr->ev[i]);
-        if (tr->ws) (void)hipFree(tr->ws);
-        if (tr->w) (void)hipFree(tr->w);
-    }
-
-    static int set_weights(indel_train_state *tr, const float *blob_host, size_t n_floats)
-    {
-        if (!tr) return NC_ERR_ARG;
-        nc_ctx *ctx = tr->ctx;
-        if (!blob_host || n_floats != (size_t)B::NPAR) return nc_fail(ctx, NC_ERR_ARG, "%s_set_weights: expects %d floats", U::NAME, B::NPAR);
-        NC_HIP(ctx, hipSetDevice(ctx->device));
-        NC_HIP(ctx, hipMemcpyAsync(tr->w, blob_host, (size_t)B::NPAR * 4, hipMemcpyHostToDevice, ctx->stream));
-        NC_HIP(ctx, hipMemsetAsync(tr->m, 0, (size_t)B::NPAR * 4 * 3, ctx->stream));
-        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        tr->t = 0;
-        tr->have_grad = false;
-        return NC_OK;
-    }
-
-    static int get_weights(indel_train_state *tr, float *blob_host, size_t n_floats)
-    {
-        if (!tr) return NC_ERR_ARG;
-        nc_ctx *ctx = tr->ctx;
-        if (!blob_host || n_floats != (size_t)B::NPAR) return nc_fail(ctx, NC_ERR_ARG, "%s_get_weights: expects %d floats", U::NAME, B::NPAR);
-        NC_HIP(ctx, hipSetDevice(ctx->device));
-        NC_HIP(ctx, hipMemcpyAsync(blob_host, tr->w, (size_t)B::NPAR * 4, hipMemcpyDeviceToHost, ctx->stream));
-        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return NC_OK;
+        if (!ctx || !out) return NC_ERR_ARG;
+        *out = nullptr;
+        if (kind != U::KIND)
+            return nc_fail(ctx, NC_ERR_UNSUPPORTED, "%s_create: only the %s model (kind %d) is trained here, not kind %d", U::NAME, U::MODEL, U::KIND, kind);
+        if (max_batch < 1 || slice_sites < 0) return nc_fail(ctx, NC_ERR_ARG, "%s_create: max_batch / slice_sites", U::NAME);
+        return train_create(ctx, max_batch, out, [slice_sites](indel_train_state *tr) {
+            tr->slice = slice_sites > 0 ? slice_sites : DEFAULT_SLICE;
+            if (tr->slice > tr->max_batch) tr->slice = tr->max_batch;
+            const size_t sl = (size_t)tr->slice, ns = (sl + SLAB - 1) / SLAB;
+            const size_t sizes[] = {sl * B::N1, sl * B::N2, sl * B::NF, sl * F1, sl * F1, sl * B::TA, sl * B::TD, sl * F1, sl * B::N1, sl * B::N2, sl * B::NF,
+                                    ns * B::NSM, (size_t)tr->max_batch, 8, 2 * WSQ_BLOCKS};
+            float **const ptrs[] = {&tr->a1, &tr->a2, &tr->a3, &tr->f1, &tr->f1d, &tr->tact, &tr->tdel, &tr->df1, &tr->d1, &tr->d2, &tr->d3, &tr->slabs, &tr->loss,
+                                    &tr->loss2, &tr->wsq};
+            return train_alloc(tr, U::NAME, B::NPAR, sizes, ptrs);
+        });
     }
 
     static int forward(indel_train_state *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, float *probs_dev)
     {
-        NC_TRY(check_call(tr, "forward", n, x_dev, keep));
+        NC_TRY(train_check_call(tr, U::NAME, "forward", n, x_dev && probs_dev, keep));
         nc_ctx *ctx = tr->ctx;
-        if (!probs_dev) return nc_fail(ctx, NC_ERR_ARG, "%s_forward: null argument", U::NAME);
         NC_HIP(ctx, hipSetDevice(ctx->device));
         if (keep == 1.0f) keep_mask_dev = nullptr;
         for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
@@ -593,37 +515,36 @@ struct indel_train {
     static int loss_grad(indel_train_state *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, const uint8_t *label_dev, float gamma,
                          float *loss2_host, float *grad_dev)
     {
-        NC_TRY(check_call(tr, "loss_grad", n, x_dev, keep));
+        NC_TRY(train_check_call(tr, U::NAME, "loss_grad", n, x_dev && label_dev, keep));
         nc_ctx *ctx = tr->ctx;
-        if (!label_dev) return nc_fail(ctx, NC_ERR_ARG, "%s_loss_grad: null argument", U::NAME);
         NC_HIP(ctx, hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         if (keep == 1.0f) keep_mask_dev = nullptr;
         tr->have_grad = tr->partial = false;
-        if (U::CHECK_LABELS) NC_HIP(ctx, hipMemsetAsync(tr->loss2, 0, 8 * 4, st));
+        if (U::BAD_LABELS) NC_HIP(ctx, hipMemsetAsync(tr->loss2, 0, 8 * 4, st));
         for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
             const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
             const unsigned ns = (unsigned)((nb + SLAB - 1) / SLAB);
             const float *x = x_dev + s0 * B::XT;
-            mark(tr, TS_FWD);
+            train_mark(tr, TS_FWD);
             forward_trunk(tr, nb, x);
-            mark(tr, TS_HEADS);
+            train_mark(tr, TS_HEADS);
             U::heads(tr, st, nb, keep_mask_dev ? keep_mask_dev + s0 * F1 : nullptr, 1.0f / keep, label_dev + s0, 1.0f / (float)n, nullptr, tr->loss + s0);
             hipLaunchKernelGGL(k_small_wgrad<B>, dim3(ns, blocks_for(B::NSMALL)), dim3(256), 0, st, tr->tact, tr->tdel, tr->df1, nb, tr->slabs);
-            mark(tr, TS_FC1);
+            train_mark(tr, TS_FC1);
             hipLaunchKernelGGL((k_fc1_wgrad<B::NF, U::FCW_J>), dim3((B::NF + 16 * U::FCW_J - 1) / (16 * U::FCW_J)), dim3(256), 0, st, tr->a3, tr->df1, nb, s0 > 0 ? 1 : 0, tr->g);
             hipLaunchKernelGGL(k_fc1_dgrad<B::NF>, dim3(blocks_for(nb, 16), DG_Y), dim3(256), 0, st, tr->w + O_KF, tr->df1, tr->a3, nb, tr->d3);
-            mark(tr, TS_CONV3);
+            train_mark(tr, TS_CONV3);
             hipLaunchKernelGGL((k_conv_wgrad<B::H - 1, 63, 32, 48, 2, SLAB, B::NSM>), dim3(ns, 6), dim3(256), 0, st, tr->a2, tr->d3, nb, (int)O_K3, tr->slabs);
             hipLaunchKernelGGL((k_bias_grad<48, B::P3, SLAB, B::NSM>), dim3(ns), dim3(256), 0, st, tr->d3, nb, (int)O_B3, tr->slabs);
             hipLaunchKernelGGL((k_conv_dgrad<B::H - 1, 63, 32, 48>), tile_grid(nb * B::P2), dim3(256), 0, st, tr->d3, tr->w + O_K3, tr->a2, tr->d2, nb * B::P2);
-            mark(tr, TS_CONV2);
+            train_mark(tr, TS_CONV2);
             hipLaunchKernelGGL((k_conv_wgrad<B::H, W, 24, 32, 3, SLAB, B::NSM>), dim3(ns, 3), dim3(256), 0, st, tr->a1, tr->d2, nb, (int)O_K2, tr->slabs);
             hipLaunchKernelGGL((k_bias_grad<32, B::P2, SLAB, B::NSM>), dim3(ns), dim3(256), 0, st, tr->d2, nb, (int)O_B2, tr->slabs);
             hipLaunchKernelGGL((k_conv_dgrad<B::H, W, 24, 32>), tile_grid(nb * (B::H * W)), dim3(256), 0, st, tr->d2, tr->w + O_K2, tr->a1, tr->d1, nb * (B::H * W));
-            mark(tr, TS_CONV1);
+            train_mark(tr, TS_CONV1);
             hipLaunchKernelGGL((k_conv1_wgrad<B::H, B::NSM>), dim3(ns, 4), dim3(64 * C1W), 0, st, x, tr->d1, nb, tr->slabs);
-            mark(tr, TS_PARAMS);
+            train_mark(tr, TS_PARAMS);
             if (s0 + nb < n) {                                          // not the last slice: fold its slabs into g, the workspace is reused
                 hipLaunchKernelGGL(k_params<B>, dim3(blocks_for(B::NPAR)), dim3(256), 0, st, tr->g, tr->partial ? 1 : 0, tr->slabs, (int)ns, 0, 0.0f, tr->g, 0,
                                    tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
@@ -638,27 +559,9 @@ struct indel_train {
                                tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
         hipLaunchKernelGGL(k_wsq<B>, dim3(WSQ_BLOCKS), dim3(256), 0, st, tr->w, reinterpret_cast<double *>(tr->wsq));
         hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(1024), 0, st, tr->loss, n, reinterpret_cast<const double *>(tr->wsq), gamma, tr->loss2);
-        mark(tr, TS_N);
+        train_mark(tr, TS_N);
         NC_HIP(ctx, hipGetLastError());
-        if (U::CHECK_LABELS) {
-            // the labels are on the device: the flag U::heads sets comes back with the losses, so this call always waits
-            float l3[3] = {0.0f, 0.0f, 0.0f};
-            NC_HIP(ctx, hipMemcpyAsync(l3, tr->loss2, 3 * 4, hipMemcpyDeviceToHost, st));
-            NC_HIP(ctx, hipStreamSynchronize(st));
-            if (l3[2] != 0.0f) return nc_fail(ctx, NC_ERR_ARG, "%s_loss_grad: a label outside 0 .. %d", U::NAME, U::MAX_LABEL);
-            tr->have_grad = true;
-            if (loss2_host) {
-                loss2_host[0] = l3[0];
-                loss2_host[1] = l3[1];
-            }
-            return NC_OK;
-        }
-        tr->have_grad = true;
-        if (loss2_host) {
-            NC_HIP(ctx, hipMemcpyAsync(loss2_host, tr->loss2, 2 * 4, hipMemcpyDeviceToHost, st));
-            NC_HIP(ctx, hipStreamSynchronize(st));
-        }
-        return NC_OK;
+        return train_finish_loss_grad(tr, U::NAME, tr->loss2, 2, U::BAD_LABELS, loss2_host);
     }
 
     static int adam(indel_train_state *tr, float lr, float beta1, float beta2, float eps)
@@ -668,35 +571,10 @@ struct indel_train {
         if (!tr->have_grad) return nc_fail(ctx, NC_ERR_STATE, "%s_adam: no gradient (%s_loss_grad comes first, once per step)", U::NAME, U::NAME);
         NC_HIP(ctx, hipSetDevice(ctx->device));
         tr->t++;
-        const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)tr->t)) / (1.0 - std::pow((double)beta1, (double)tr->t)));
         hipLaunchKernelGGL(k_params<B>, dim3(blocks_for(B::NPAR)), dim3(256), 0, ctx->stream, tr->g, tr->partial ? 1 : 0, tr->slabs, tr->pending_ns, 1, tr->pending_gamma,
-                           (float *)nullptr, 1, tr->w, tr->m, tr->v, lr_t, beta1, beta2, eps);
+                           (float *)nullptr, 1, tr->w, tr->m, tr->v, train_lr_t(lr, beta1, beta2, tr->t), beta1, beta2, eps);
         NC_HIP(ctx, hipGetLastError());
         tr->have_grad = false;
-        return NC_OK;
-    }
-
-    static int info(indel_train_state *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps)
-    {
-        if (!tr) return NC_ERR_ARG;
-        if (slice_sites) *slice_sites = tr->slice;
-        if (workspace_bytes) *workspace_bytes = (int64_t)tr->ws_bytes;
-        if (steps) *steps = tr->t;
-        return NC_OK;
-    }
-
-    static int stage_ms(indel_train_state *tr, int32_t on, float *ms7)
-    {
-        if (!tr) return NC_ERR_ARG;
-        nc_ctx *ctx = tr->ctx;
-        if (ms7 && tr->timing) {
-            NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (int i = 0; i < TS_N; i++) {
-                ms7[i] = 0.0f;
-                NC_HIP(ctx, hipEventElapsedTime(&ms7[i], tr->ev[i], tr->ev[i + 1]));
-            }
-        }
-        tr->timing = on;
         return NC_OK;
     }
 };

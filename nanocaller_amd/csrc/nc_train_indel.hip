@@ -81,10 +81,9 @@ __global__ __launch_bounds__(64) void k_heads(const float *__restrict__ f1, cons
 
 struct unit {
     using B = ::B;
-    static constexpr const char *NAME = "nc_indel_train";
-    static constexpr bool CHECK_LABELS = false;                        // (IndelTrainer looks at the labels on the host)
+    static constexpr const char *NAME = "nc_indel_train", *MODEL = "diploid indel", *BAD_LABELS = nullptr;   // (IndelTrainer looks at the labels on the host)
+    static constexpr int KIND = NC_MODEL_INDEL;
     static constexpr int FCW_J = 4;                                    // 64 rows of fc1's weight gradient per workgroup: 303 workgroups
-    static constexpr int MAX_LABEL = 3;
     static void heads(indel_train_state *tr, hipStream_t st, int64_t nb, const uint8_t *mask, float inv_keep, const uint8_t *label, float inv_n, float *probs,
                       float *loss)
     {
@@ -102,33 +101,12 @@ extern "C" {
 
 int nc_indel_train_create(nc_ctx *ctx, int32_t kind, int64_t max_batch, int64_t slice_sites, nc_indel_train **out)
 {
-    if (!ctx || !out) return NC_ERR_ARG;
-    *out = nullptr;
-    if (kind != NC_MODEL_INDEL)
-        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_indel_train_create: only the diploid indel model (kind %d) is trained, not kind %d", NC_MODEL_INDEL, kind);
-    if (max_batch < 1 || slice_sites < 0) return nc_fail(ctx, NC_ERR_ARG, "nc_indel_train_create: max_batch / slice_sites");
-    nc_indel_train *tr = new nc_indel_train;
-    tr->ctx = ctx;
-    const int rc = T::init(tr, ctx, max_batch, slice_sites);
-    if (rc != NC_OK) {
-        T::release(tr);
-        delete tr;
-        return rc;
-    }
-    *out = tr;
-    return NC_OK;
+    return T::create(ctx, kind, max_batch, slice_sites, out);
 }
 
-int nc_indel_train_free(nc_indel_train *tr)
-{
-    if (!tr) return NC_OK;
-    T::release(tr);
-    delete tr;
-    return NC_OK;
-}
-
-int nc_indel_train_set_weights(nc_indel_train *tr, const float *blob_host, size_t n_floats) { return T::set_weights(tr, blob_host, n_floats); }
-int nc_indel_train_get_weights(nc_indel_train *tr, float *blob_host, size_t n_floats) { return T::get_weights(tr, blob_host, n_floats); }
+int nc_indel_train_free(nc_indel_train *tr) { return train_free(tr); }
+int nc_indel_train_set_weights(nc_indel_train *tr, const float *blob_host, size_t n_floats) { return train_set_weights(tr, unit::NAME, B::NPAR, blob_host, n_floats); }
+int nc_indel_train_get_weights(nc_indel_train *tr, float *blob_host, size_t n_floats) { return train_get_weights(tr, unit::NAME, B::NPAR, blob_host, n_floats); }
 
 int nc_indel_train_forward(nc_indel_train *tr, int64_t n, const float *x_dev, const uint8_t *keep_mask_dev, float keep, float *probs_dev)
 {
@@ -145,9 +123,9 @@ int nc_indel_train_adam(nc_indel_train *tr, float lr, float beta1, float beta2, 
 
 int nc_indel_train_info(nc_indel_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps)
 {
-    return T::info(tr, slice_sites, workspace_bytes, steps);
+    return train_info(tr, slice_sites, workspace_bytes, steps);
 }
 
-int nc_indel_train_stage_ms(nc_indel_train *tr, int32_t on, float *ms7) { return T::stage_ms(tr, on, ms7); }
+int nc_indel_train_stage_ms(nc_indel_train *tr, int32_t on, float *ms7) { return train_stage_ms(tr, on, ms7); }
 
 }   // extern "C"

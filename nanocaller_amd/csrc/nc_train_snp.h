@@ -2,6 +2,8 @@
 // to 48 channels, conv2 to [4][20][32], conv3 to [3][9][64], fc1 1,728 -> 48.  Both blobs (weights.LAYER_SPECS[KIND_SNP], [KIND_SNP_HAP]) begin
 // with these layers, kernel then bias of each, so the trunk's offsets are the same numbers in both and stand here once; what differs is what
 // follows fc1 and with it NPAR, the floats per gradient slab, a template parameter of the two kernels that write slabs.
+// Behind the kernels: k_params and the host side of a handle, snp_train<U>, over the unit U that each .hip file supplies with its kernels
+// behind fc1 (as indel_train<U> of nc_train_indel.h; what no family owns is in nc_train.h).
 // lane l of an MFMA: A[row l&15][k l>>4], B[k l>>4][col l&15], C/D col l&15, row 4*(l>>4)+r (the lane maps of nc_cnn_fp32.hip).
 #pragma once
 #include "nc_train.h"
@@ -266,9 +268,31 @@ __global__ __launch_bounds__(256) void k_conv1_wgrad(const float *__restrict__ x
     }
 }
 
-// What a unit's loss_grad launches around its own heads kernels, on the unit's stream.  The buffers of one workspace slice:
-struct snp_trunk_ws {
-    float *w, *xs, *a1, *a2, *a3, *f1, *f1d, *df1, *d1, *d2, *d3, *slabs;
+// One parameter per lane: gradient = g_in (earlier slices, may be NULL) + the slabs in slab order (+ gamma w on kernel entries with `reg`);
+// written to g_out (may be NULL); with `step` the Adam update in TensorFlow's form, w -= lr_t m / (sqrt(v) + eps).
+template <class U>
+__global__ __launch_bounds__(256) void k_params(const float *__restrict__ g_in, const float *__restrict__ slabs, int ns, int reg, float gamma,
+                                                float *__restrict__ g_out, int step, float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                float lr_t, float b1, float b2, float eps)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= U::NPAR) return;
+    float g = g_in ? g_in[i] : 0.0f;
+    for (int k = 0; k < ns; k++) g += slabs[(int64_t)k * U::NPAR + i];
+    const float wi = w[i];
+    if (reg && !U::is_bias(i)) g = fmaf(gamma, wi, g);
+    if (g_out) g_out[i] = g;
+    if (step) {
+        const float mi = fmaf(b1, m[i], (1.0f - b1) * g), vi = fmaf(b2, v[i], (1.0f - b2) * g * g);
+        m[i] = mi;
+        v[i] = vi;
+        w[i] = wi - lr_t * mi / (sqrtf(vi) + eps);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the host side of a handle
+struct snp_train_state : train_state {
+    float *xs, *a1, *a2, *a3, *f1, *f1d, *tact, *tdel, *df1, *d1, *d2, *d3, *slabs, *loss, *lossv;   // lossv: the loss terms, then the bad-label flag
 };
 
 inline dim3 snp_tile_grid(int64_t npos)
@@ -277,40 +301,138 @@ inline dim3 snp_tile_grid(int64_t npos)
     return dim3((unsigned)(t < 2048 ? t : 2048));
 }
 
-// conv1 - fc1 of `nb` sites (a slice) into the workspace
-inline void snp_trunk_forward(const snp_trunk_ws &t, hipStream_t st, int64_t nb, const float *x, const double *scale)
-{
-    int pitch = 1025;
-    if (scale) {
-        hipLaunchKernelGGL(k_scale_x, dim3(blocks_for(nb * 1025)), dim3(256), 0, st, x, scale, t.xs, nb);
-        x = t.xs;
-        pitch = XS;
-    }
-    hipLaunchKernelGGL(k_conv1_fwd, dim3(blocks_for(nb * 205)), dim3(256), 0, st, x, pitch, t.w, t.a1, nb * 205);
-    hipLaunchKernelGGL((k_conv23_fwd<5, 41, 48, 32>), snp_tile_grid(nb * 80), dim3(256), 0, st, t.a1, t.w + O_K2, t.w + O_B2, t.a2, nb * 80);
-    hipLaunchKernelGGL((k_conv23_fwd<4, 20, 32, 64>), snp_tile_grid(nb * 27), dim3(256), 0, st, t.a2, t.w + O_K3, t.w + O_B3, t.a3, nb * 27);
-    hipLaunchKernelGGL(k_fc1_fwd, dim3(blocks_for(nb, 16)), dim3(256), 0, st, t.a3, t.w + O_KF, t.w + O_BF, t.f1, t.f1d, nb);
-}
+// A unit U names its blob (U::NPAR, U::is_bias, the per-site records U::TA and U::TD, U::NSMALL = the parameters of its k_small_wgrad), its
+// labels (U::NLAB per site, as many per-site losses) and loss terms (U::NLOSS), its entry points' prefix (U::NAME), the model it accepts
+// (U::KIND, U::MODEL) and what a label outside the classes is called (U::BAD_LABELS; null where labels are not looked at on the device: then
+// loss_grad waits only when the losses are asked for).  It launches its own kernels behind fc1:
+//   static void heads(snp_train_state *, hipStream_t, int64_t nb, const int32_t *ref_code, const uint8_t *mask, float inv_keep,
+//                     const uint8_t *label, float inv_n, float *probs, float *gt, float *loss)     (sets lossv[NLOSS] on a bad label)
+//   static void small_wgrad(snp_train_state *, hipStream_t, unsigned ns, const int32_t *ref_code, int64_t nb)
+//   static void loss_reduce(snp_train_state *, hipStream_t, int64_t n, float gamma)                (loss -> lossv[0 .. NLOSS))
+template <class U>
+struct snp_train {
+    static constexpr int NPAR = U::NPAR;
 
-// The trunk's gradients of a slice from d fc1 (t.df1) down to conv1's kernels, into the slice's slabs.  x / pitch: the input conv1 read;
-// stage(i) is called before stage i = 0 fc1, 1 conv3, 2 conv2, 3 conv1 (the units record their timing events there).
-template <int NPAR, typename Stage>
-inline void snp_trunk_backward(const snp_trunk_ws &t, hipStream_t st, int64_t nb, const float *x, int pitch, Stage stage)
-{
-    const unsigned ns = (unsigned)((nb + SLAB - 1) / SLAB);
-    stage(0);
-    hipLaunchKernelGGL(k_fc1_wgrad<NPAR>, dim3(ns, 9), dim3(256), 0, st, t.a3, t.df1, nb, t.slabs);
-    hipLaunchKernelGGL(k_fc1_dgrad, dim3(blocks_for(nb, 16)), dim3(256), 0, st, t.w + O_KF, t.df1, t.a3, nb, t.d3);
-    stage(1);
-    hipLaunchKernelGGL((k_conv_wgrad<4, 20, 32, 64, 2, SLAB, NPAR>), dim3(ns, 6), dim3(256), 0, st, t.a2, t.d3, nb, (int)O_K3, t.slabs);
-    hipLaunchKernelGGL((k_bias_grad<64, 27, SLAB, NPAR>), dim3(ns), dim3(256), 0, st, t.d3, nb, (int)O_B3, t.slabs);
-    hipLaunchKernelGGL((k_conv_dgrad<4, 20, 32, 64>), snp_tile_grid(nb * 80), dim3(256), 0, st, t.d3, t.w + O_K3, t.a2, t.d2, nb * 80);
-    stage(2);
-    hipLaunchKernelGGL((k_conv_wgrad<5, 41, 48, 32, 3, SLAB, NPAR>), dim3(ns, 6), dim3(256), 0, st, t.a1, t.d2, nb, (int)O_K2, t.slabs);
-    hipLaunchKernelGGL((k_bias_grad<32, 80, SLAB, NPAR>), dim3(ns), dim3(256), 0, st, t.d2, nb, (int)O_B2, t.slabs);
-    hipLaunchKernelGGL((k_conv_dgrad<5, 41, 48, 32>), snp_tile_grid(nb * 205), dim3(256), 0, st, t.d2, t.w + O_K2, t.a1, t.d1, nb * 205);
-    stage(3);
-    hipLaunchKernelGGL(k_conv1_wgrad<NPAR>, dim3(ns, 6), dim3(256), 0, st, x, pitch, t.d1, nb, t.slabs);
-}
+    // conv1 - fc1 of `nb` sites (a slice) into the workspace; returns the input conv1 read and sets its pitch
+    static const float *forward_trunk(snp_train_state *t, int64_t nb, const float *x, const double *scale, int &pitch)
+    {
+        hipStream_t st = t->ctx->stream;
+        pitch = 1025;
+        if (scale) {
+            hipLaunchKernelGGL(k_scale_x, dim3(blocks_for(nb * 1025)), dim3(256), 0, st, x, scale, t->xs, nb);
+            x = t->xs;
+            pitch = XS;
+        }
+        hipLaunchKernelGGL(k_conv1_fwd, dim3(blocks_for(nb * 205)), dim3(256), 0, st, x, pitch, t->w, t->a1, nb * 205);
+        hipLaunchKernelGGL((k_conv23_fwd<5, 41, 48, 32>), snp_tile_grid(nb * 80), dim3(256), 0, st, t->a1, t->w + O_K2, t->w + O_B2, t->a2, nb * 80);
+        hipLaunchKernelGGL((k_conv23_fwd<4, 20, 32, 64>), snp_tile_grid(nb * 27), dim3(256), 0, st, t->a2, t->w + O_K3, t->w + O_B3, t->a3, nb * 27);
+        hipLaunchKernelGGL(k_fc1_fwd, dim3(blocks_for(nb, 16)), dim3(256), 0, st, t->a3, t->w + O_KF, t->w + O_BF, t->f1, t->f1d, nb);
+        return x;
+    }
+
+    template <class H>
+    static int create(nc_ctx *ctx, int32_t kind, int64_t max_batch, H **out)
+    {
+        if (!ctx || !out) return NC_ERR_ARG;
+        *out = nullptr;
+        if (kind != U::KIND)
+            return nc_fail(ctx, NC_ERR_UNSUPPORTED, "%s_create: only the %s model (kind %d) is trained here, not kind %d", U::NAME, U::MODEL, U::KIND, kind);
+        if (max_batch < 1) return nc_fail(ctx, NC_ERR_ARG, "%s_create: max_batch", U::NAME);
+        return train_create(ctx, max_batch, out, [](snp_train_state *tr) {
+            tr->slice = tr->max_batch < MAX_SLICE ? tr->max_batch : MAX_SLICE;
+            const size_t sl = (size_t)tr->slice, ns = (sl + SLAB - 1) / SLAB;
+            const size_t sizes[] = {sl * XS, sl * N1, sl * N2, sl * N3, sl * 48, sl * 48, sl * U::TA, sl * U::TD, sl * 48, sl * N1, sl * N2, sl * N3, ns * NPAR,
+                                    (size_t)tr->max_batch * U::NLAB, 8};
+            float **const ptrs[] = {&tr->xs, &tr->a1, &tr->a2, &tr->a3, &tr->f1, &tr->f1d, &tr->tact, &tr->tdel, &tr->df1, &tr->d1, &tr->d2, &tr->d3, &tr->slabs,
+                                    &tr->loss, &tr->lossv};
+            return train_alloc(tr, U::NAME, NPAR, sizes, ptrs);
+        });
+    }
+
+    // gt_dev: the diploid model's genotype output, null for the haploid one
+    static int forward(snp_train_state *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                       float keep, float *probs_dev, float *gt_dev)
+    {
+        NC_TRY(train_check_call(tr, U::NAME, "forward", n, x_dev && ref_code_dev && probs_dev, keep));
+        nc_ctx *ctx = tr->ctx;
+        NC_HIP(ctx, hipSetDevice(ctx->device));
+        if (keep == 1.0f) keep_mask_dev = nullptr;
+        for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
+            const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
+            int pitch;
+            forward_trunk(tr, nb, x_dev + s0 * NC_SNP_TENSOR, scale_dev ? scale_dev + s0 : nullptr, pitch);
+            U::heads(tr, ctx->stream, nb, ref_code_dev + s0, keep_mask_dev ? keep_mask_dev + s0 * 48 : nullptr, 1.0f / keep, nullptr, 0.0f, probs_dev + s0 * 4,
+                     gt_dev ? gt_dev + s0 * 2 : nullptr, tr->loss);
+        }
+        NC_HIP(ctx, hipGetLastError());
+        return NC_OK;
+    }
+
+    static int loss_grad(snp_train_state *tr, int64_t n, const float *x_dev, const int32_t *ref_code_dev, const double *scale_dev, const uint8_t *keep_mask_dev,
+                         float keep, const uint8_t *label_dev, float gamma, float *loss_host, float *grad_dev)
+    {
+        NC_TRY(train_check_call(tr, U::NAME, "loss_grad", n, x_dev && ref_code_dev && label_dev, keep));
+        nc_ctx *ctx = tr->ctx;
+        NC_HIP(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        if (keep == 1.0f) keep_mask_dev = nullptr;
+        tr->have_grad = tr->partial = false;
+        if (U::BAD_LABELS) NC_HIP(ctx, hipMemsetAsync(tr->lossv, 0, 8 * 4, st));
+        for (int64_t s0 = 0; s0 < n; s0 += tr->slice) {
+            const int64_t nb = n - s0 < tr->slice ? n - s0 : tr->slice;
+            const unsigned ns = (unsigned)((nb + SLAB - 1) / SLAB);
+            train_mark(tr, TS_FWD);
+            int pitch;
+            const float *x = forward_trunk(tr, nb, x_dev + s0 * NC_SNP_TENSOR, scale_dev ? scale_dev + s0 : nullptr, pitch);
+            train_mark(tr, TS_HEADS);
+            U::heads(tr, st, nb, ref_code_dev + s0, keep_mask_dev ? keep_mask_dev + s0 * 48 : nullptr, 1.0f / keep, label_dev + s0 * U::NLAB, 1.0f / (float)n,
+                     nullptr, nullptr, tr->loss + s0 * U::NLAB);
+            U::small_wgrad(tr, st, ns, ref_code_dev + s0, nb);
+            train_mark(tr, TS_FC1);
+            hipLaunchKernelGGL(k_fc1_wgrad<NPAR>, dim3(ns, 9), dim3(256), 0, st, tr->a3, tr->df1, nb, tr->slabs);
+            hipLaunchKernelGGL(k_fc1_dgrad, dim3(blocks_for(nb, 16)), dim3(256), 0, st, tr->w + O_KF, tr->df1, tr->a3, nb, tr->d3);
+            train_mark(tr, TS_CONV3);
+            hipLaunchKernelGGL((k_conv_wgrad<4, 20, 32, 64, 2, SLAB, NPAR>), dim3(ns, 6), dim3(256), 0, st, tr->a2, tr->d3, nb, (int)O_K3, tr->slabs);
+            hipLaunchKernelGGL((k_bias_grad<64, 27, SLAB, NPAR>), dim3(ns), dim3(256), 0, st, tr->d3, nb, (int)O_B3, tr->slabs);
+            hipLaunchKernelGGL((k_conv_dgrad<4, 20, 32, 64>), snp_tile_grid(nb * 80), dim3(256), 0, st, tr->d3, tr->w + O_K3, tr->a2, tr->d2, nb * 80);
+            train_mark(tr, TS_CONV2);
+            hipLaunchKernelGGL((k_conv_wgrad<5, 41, 48, 32, 3, SLAB, NPAR>), dim3(ns, 6), dim3(256), 0, st, tr->a1, tr->d2, nb, (int)O_K2, tr->slabs);
+            hipLaunchKernelGGL((k_bias_grad<32, 80, SLAB, NPAR>), dim3(ns), dim3(256), 0, st, tr->d2, nb, (int)O_B2, tr->slabs);
+            hipLaunchKernelGGL((k_conv_dgrad<5, 41, 48, 32>), snp_tile_grid(nb * 205), dim3(256), 0, st, tr->d2, tr->w + O_K2, tr->a1, tr->d1, nb * 205);
+            train_mark(tr, TS_CONV1);
+            hipLaunchKernelGGL(k_conv1_wgrad<NPAR>, dim3(ns, 6), dim3(256), 0, st, x, pitch, tr->d1, nb, tr->slabs);
+            train_mark(tr, TS_PARAMS);
+            if (s0 + nb < n) {                                          // not the last slice: fold its slabs into g, the workspace is reused
+                hipLaunchKernelGGL(k_params<U>, dim3(blocks_for(NPAR)), dim3(256), 0, st, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, (int)ns, 0, 0.0f,
+                                   tr->g, 0, tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
+                tr->partial = true;
+            } else {
+                tr->pending_ns = (int)ns;
+                tr->pending_gamma = gamma;
+            }
+        }
+        if (grad_dev)
+            hipLaunchKernelGGL(k_params<U>, dim3(blocks_for(NPAR)), dim3(256), 0, st, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, tr->pending_ns, 1, gamma,
+                               grad_dev, 0, tr->w, tr->m, tr->v, 0.0f, 0.0f, 0.0f, 0.0f);
+        U::loss_reduce(tr, st, n, gamma);
+        train_mark(tr, TS_N);
+        NC_HIP(ctx, hipGetLastError());
+        return train_finish_loss_grad(tr, U::NAME, tr->lossv, U::NLOSS, U::BAD_LABELS, loss_host);
+    }
+
+    static int adam(snp_train_state *tr, float lr, float beta1, float beta2, float eps)
+    {
+        if (!tr) return NC_ERR_ARG;
+        nc_ctx *ctx = tr->ctx;
+        if (!tr->have_grad) return nc_fail(ctx, NC_ERR_STATE, "%s_adam: no gradient (%s_loss_grad comes first, once per step)", U::NAME, U::NAME);
+        NC_HIP(ctx, hipSetDevice(ctx->device));
+        tr->t++;
+        hipLaunchKernelGGL(k_params<U>, dim3(blocks_for(NPAR)), dim3(256), 0, ctx->stream, tr->partial ? tr->g : (const float *)nullptr, tr->slabs, tr->pending_ns, 1,
+                           tr->pending_gamma, (float *)nullptr, 1, tr->w, tr->m, tr->v, train_lr_t(lr, beta1, beta2, tr->t), beta1, beta2, eps);
+        NC_HIP(ctx, hipGetLastError());
+        tr->have_grad = false;
+        return NC_OK;
+    }
+};
 
 }   // namespace

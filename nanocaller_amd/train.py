@@ -15,14 +15,13 @@ truth_neighbors (-truth_neighbors) adds every site a second time with the truth'
 """
 from __future__ import annotations
 
-import ctypes as C
 import gzip
-import os
 
 import numpy as np
 
-from . import _lib
-from .weights import KIND_SNP, LAYER_SPECS, Weights, get_SNP_model, write_ncw
+from . import train_common
+from .train_common import SnpFamilyTrainer, add_train_args, initial_blob, run_epochs, snp_params, subsample_negatives, weighted_coverage
+from .weights import KIND_SNP, get_SNP_model, write_ncw  # noqa: F401  (write_ncw: imported from here by its users)
 
 LOSS_KEYS = ("cost", "GT", "A", "G", "T", "C")
 BASE_CODE = {"A": 0, "G": 1, "T": 2, "C": 3}
@@ -31,26 +30,13 @@ GT_MAP = {(0, 0): 0, (1, 1): 0, (2, 2): 0, (1, 2): 1, (2, 1): 1, (0, 1): 1, (1, 
 
 
 def xavier_init(seed=0):
-    """canonical float32 blob: Xavier-uniform kernels (limit sqrt(6 / (fan_in + fan_out)), TensorFlow's initializer), zero biases"""
-    rng = np.random.default_rng(seed)
-    parts = []
-    for _, shp in LAYER_SPECS[KIND_SNP]:
-        rf = int(np.prod(shp[:-2]))
-        lim = np.sqrt(6.0 / (rf * shp[-2] + rf * shp[-1]))
-        parts.append(rng.uniform(-lim, lim, int(np.prod(shp))).astype(np.float32))
-        parts.append(np.zeros(shp[-1], np.float32))
-    return np.concatenate(parts)
+    """train_common.xavier_init for the diploid SNP model"""
+    return train_common.xavier_init(KIND_SNP, seed)
 
 
 def blob_tensors(flat):
-    """canonical blob -> [(name, array)] as weights.write_ncw takes them"""
-    out, off = [], 0
-    for name, shp in LAYER_SPECS[KIND_SNP]:
-        nk = int(np.prod(shp))
-        out.append((name + ".k", np.asarray(flat[off:off + nk], np.float32).reshape(shp)))
-        out.append((name + ".b", np.asarray(flat[off + nk:off + nk + shp[-1]], np.float32)))
-        off += nk + shp[-1]
-    return out
+    """train_common.blob_tensors for the diploid SNP model"""
+    return train_common.blob_tensors(flat, KIND_SNP)
 
 
 # ------------------------------------------------------------------ labels (pure host code)
@@ -111,10 +97,7 @@ def label_sites(pos, ref_code, truth, intervals, neg_ratio=2.0, seed=0):
     ref_code = np.asarray(ref_code, np.int64)
     keep = in_bed(intervals, pos) if intervals is not None else np.ones(pos.shape, bool)
     is_truth = np.fromiter((int(p) in truth for p in pos), bool, pos.size) & keep
-    neg = np.nonzero(keep & ~is_truth)[0]
-    n_truth = int(is_truth.sum())
-    if neg_ratio is not None and n_truth > 0 and neg.size > int(neg_ratio * n_truth):
-        neg = np.sort(np.random.default_rng(seed).permutation(neg)[:int(neg_ratio * n_truth)])
+    neg, _ = subsample_negatives(np.nonzero(keep & ~is_truth)[0], int(is_truth.sum()), neg_ratio, seed)
     idx = np.sort(np.concatenate([np.nonzero(is_truth)[0], neg]))
     labels = np.zeros((idx.size, 5), np.uint8)
     for j, i in enumerate(idx):
@@ -295,122 +278,18 @@ def snp_training_examples(params, truth_vcf=None, confident_bed=None, neg_ratio=
 
 
 # ------------------------------------------------------------------ the trainer
-class SnpTrainer:
+class SnpTrainer(SnpFamilyTrainer):
     """One trainer per engine context.  init: a model name, an .ncw path, a canonical blob (numpy), or None = Xavier-uniform from `seed`."""
+
+    PREFIX, KIND, LOSS_KEYS, OUT_WIDTHS = "nc_train", KIND_SNP, LOSS_KEYS, (4, 2)
+    LABEL_WIDTH, LABEL_TEXT = 5, "labels are [n][5]: A, G, T, C in the site's alleles, GT class"
 
     def __init__(self, device=0, init=None, lr=1e-3, gamma=1e-3, keep=0.5, seed=0, max_batch=4096, kind=KIND_SNP,
                  beta1=0.9, beta2=0.999, eps=1e-8):
         if kind != KIND_SNP:
             raise ValueError("SnpTrainer: only the diploid SNP model (kind %d) is trained, not kind %d" % (KIND_SNP, kind))
-        if isinstance(init, str):
-            path, _ = get_SNP_model(init)
-            if path is None:
-                raise ValueError("SnpTrainer: %r is neither a model name nor an .ncw file" % init)
-            w = Weights(path)
-            if w.kind != KIND_SNP:
-                raise ValueError("SnpTrainer: %s holds a model of kind %d, only the diploid SNP model is trained" % (path, w.kind))
-            flat = w.flat
-        elif init is None:
-            flat = xavier_init(seed)
-        else:
-            flat = np.ascontiguousarray(init, np.float32)
-        import torch
-
-        from .engine import get_engine
-        self.eng = get_engine(device)
-        self.eng.use_torch_stream()
-        self.L, self.device = self.eng.L, self.eng.device
-        self.lr, self.gamma, self.keep, self.max_batch = float(lr), float(gamma), float(keep), int(max_batch)
-        self.adam = (float(beta1), float(beta2), float(eps))
-        self.gen = torch.Generator(device=self.device)
-        self.gen.manual_seed(int(seed))
-        h = C.c_void_p()
-        self.eng._check(self.L.nc_train_create(self.eng.ctx, int(kind), self.max_batch, C.byref(h)), "nc_train_create")
-        self.h = h
-        self.set_weights(flat)
-
-    def close(self):
-        if getattr(self, "h", None) and getattr(self.eng, "ctx", None):
-            self.L.nc_train_free(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _c(self, rc, what):
-        self.eng._check(rc, what)
-
-    def set_weights(self, flat):
-        flat = np.ascontiguousarray(flat, np.float32)
-        self._c(self.L.nc_train_set_weights(self.h, _lib.npp(flat), flat.size), "nc_train_set_weights")
-
-    def get_weights(self):
-        flat = np.zeros(sum(int(np.prod(s)) + s[-1] for _, s in LAYER_SPECS[KIND_SNP]), np.float32)
-        self._c(self.L.nc_train_get_weights(self.h, _lib.npp(flat), flat.size), "nc_train_get_weights")
-        return flat
-
-    def _inputs(self, x, ref_code, labels=None, scale=None):
-        import torch
-        dev = self.device
-        x = torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous()          # (an int16 tensor is cast here)
-        ref_code = torch.as_tensor(ref_code).to(device=dev, dtype=torch.int32).contiguous()
-        if labels is not None:
-            labels = torch.as_tensor(labels).to(device=dev, dtype=torch.uint8).contiguous()
-        if scale is not None:
-            scale = torch.as_tensor(scale).to(device=dev, dtype=torch.float64).contiguous()
-        n = int(x.shape[0])
-        if not 1 <= n <= self.max_batch:
-            raise ValueError("SnpTrainer: %d sites, max_batch is %d" % (n, self.max_batch))
-        return n, x, ref_code, labels, scale
-
-    def draw_mask(self, n):
-        """uint8 [n][48], 1 = kept with probability `keep`, from the trainer's seeded device generator"""
-        import torch
-        return (torch.rand((n, 48), generator=self.gen, device=self.device) < self.keep).to(torch.uint8)
-
-    def forward(self, x, ref_code, scale=None, mask=None, keep=1.0):
-        """-> (probs [n][4], gt [n][2]) device tensors of the training forward"""
-        import torch
-        n, x, ref_code, _, scale = self._inputs(x, ref_code, None, scale)
-        probs = torch.empty((n, 4), dtype=torch.float32, device=self.device)
-        gt = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
-        self._c(self.L.nc_train_forward(self.h, n, p(x), p(ref_code), p(scale), p(mask), float(keep), p(probs), p(gt)), "nc_train_forward")
-        return probs, gt
-
-    def loss_grad(self, x, ref_code, labels, mask=None, keep=1.0, scale=None, want_grad=True):
-        """-> (dict of the six losses, gradient blob device tensor or None); nc_train_adam steps with this gradient"""
-        import torch
-        n, x, ref_code, labels, scale = self._inputs(x, ref_code, labels, scale)
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
-        grad = torch.empty(self.get_n_params(), dtype=torch.float32, device=self.device) if want_grad else None
-        l6 = np.zeros(6, np.float32)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
-        self._c(self.L.nc_train_loss_grad(self.h, n, p(x), p(ref_code), p(scale), p(mask), float(keep), p(labels), self.gamma, _lib.npp(l6), p(grad)),
-                "nc_train_loss_grad")
-        return dict(zip(LOSS_KEYS, (float(v) for v in l6))), grad
-
-    @staticmethod
-    def get_n_params():
-        return sum(int(np.prod(s)) + s[-1] for _, s in LAYER_SPECS[KIND_SNP])
-
-    def adam_step(self, lr=None):
-        b1, b2, eps = self.adam
-        self._c(self.L.nc_train_adam(self.h, self.lr if lr is None else float(lr), b1, b2, eps), "nc_train_adam")
-
-    def step(self, x, ref_code, labels, mask=None, scale=None):
-        """one Adam step on the batch -> dict(cost, GT, A, G, T, C) before the step; mask: the dropout mask to use instead of a drawn one"""
-        if mask is None and self.keep < 1.0:
-            mask = self.draw_mask(int(x.shape[0]))
-        losses, _ = self.loss_grad(x, ref_code, labels, mask, self.keep, scale, want_grad=False)
-        self.adam_step()
-        return losses
+        flat = initial_blob("SnpTrainer", init, KIND_SNP, seed, lambda name: get_SNP_model(name)[0])
+        self._open(device, flat, lr, gamma, keep, seed, max_batch, (beta1, beta2, eps))
 
     def evaluate(self, x, ref_code, labels, scale=None):
         """keep = 1: the losses and the six accuracies of model_run.py:164-175 (GT, the four allele heads, all five right at once);
@@ -425,21 +304,6 @@ class SnpTrainer:
         out.update(acc_A=float(acc[0]), acc_G=float(acc[1]), acc_T=float(acc[2]), acc_C=float(acc[3]), acc_GT=float(acc[4]),
                    acc_all=float(hit.all(1).float().mean().item()), probs=probs, gt=gt)
         return out
-
-    def info(self):
-        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
-        self._c(self.L.nc_train_info(self.h, C.byref(a), C.byref(b), C.byref(c)), "nc_train_info")
-        return dict(slice_sites=int(a.value), workspace_bytes=int(b.value), steps=int(c.value))
-
-    def stage_ms(self, on=True):
-        """per-stage HIP-event times of the last loss_grad (ms) when timing was on; switches timing on / off for the next ones"""
-        ms = np.zeros(7, np.float32)
-        self._c(self.L.nc_train_stage_ms(self.h, 1 if on else 0, _lib.npp(ms)), "nc_train_stage_ms")
-        return dict(zip(("forward_trunk", "heads", "fc1_grad", "conv3_grad", "conv2_grad", "conv1_grad", "params"), (float(v) for v in ms)))
-
-    def save(self, path, train_coverage):
-        write_ncw(path, KIND_SNP, float(train_coverage), blob_tensors(self.get_weights()))
-        return path
 
 
 def train_snp_model(params):
@@ -457,67 +321,20 @@ def train_snp_model(params):
     x = torch.cat([v[0] for v in ex.values()])
     ref = torch.cat([v[1] for v in ex.values()])
     lab = torch.from_numpy(np.concatenate([v[2] for v in ex.values()])).to(x.device)
-    n_each = np.array([v[0].shape[0] for v in ex.values()], np.float64)
-    coverage = float((np.array([v[4] for v in ex.values()]) * n_each).sum() / n_each.sum())    # mean depth of the training sites
-    n = int(x.shape[0])
-    perm = np.random.default_rng(seed).permutation(n)
-    n_val = min(max(1, int(n * float(params.get("val_frac", 0.1)))), n - 1) if n > 1 else 0
-    val, trn = torch.from_numpy(perm[:n_val]).to(x.device), perm[n_val:]
     tr = SnpTrainer(params.get("device", 0), params.get("init"), params.get("lr", 1e-3), params.get("gamma", 1e-3), params.get("keep", 0.5), seed,
                     max_batch=max(batch, 1))
-    os.makedirs(params["out_dir"], exist_ok=True)
-    rng, hist = np.random.default_rng(seed + 1), []
-    for epoch in range(1, int(params.get("epochs", 10)) + 1):
-        order, costs = rng.permutation(trn), []
-        for o in range(0, order.size, batch):
-            sel = torch.from_numpy(order[o:o + batch]).to(x.device)
-            costs.append(tr.step(x[sel], ref[sel], lab[sel])["cost"])
-        rec = dict(epoch=epoch, train_cost=float(np.mean(costs)))
-        if n_val:
-            ev = [tr.evaluate(x[val[o:o + batch]], ref[val[o:o + batch]], lab[val[o:o + batch]]) for o in range(0, n_val, batch)]
-            wts = [min(batch, n_val - o) for o in range(0, n_val, batch)]
-            rec.update({"val_" + k: float(np.average([e[k] for e in ev], weights=wts)) for k in ev[0] if k not in ("probs", "gt")})
-        rec["path"] = tr.save(os.path.join(params["out_dir"], "model-%d.ncw" % epoch), coverage)
-        print("epoch %d: %s" % (epoch, ", ".join("%s %.4g" % (k, v) for k, v in rec.items() if k not in ("epoch", "path"))), flush=True)
-        hist.append(rec)
-    tr.close()
-    return hist
+    return run_epochs(tr, (x, ref), lab, params, batch, weighted_coverage([v[0].shape[0] for v in ex.values()], [v[4] for v in ex.values()]),
+                      LOSS_KEYS + ("acc_A", "acc_G", "acc_T", "acc_C", "acc_GT", "acc_all"))
 
 
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m nanocaller_amd.train", description="train or fine-tune the diploid SNP model on the GPU")
-    ap.add_argument("-bam", required=True)
-    ap.add_argument("-ref", required=True)
-    ap.add_argument("-vcf", required=True, help="truth VCF (plain or gzipped)")
-    ap.add_argument("-bed", required=True, help="confident regions")
-    ap.add_argument("-o", "--out_dir", required=True)
-    ap.add_argument("-chrom", nargs="+", required=True, help="contigs as NAME:START-END")
-    ap.add_argument("-seq", default="ont")
-    ap.add_argument("-init", default=None, help="model name or .ncw file to fine-tune (default: Xavier-uniform)")
-    ap.add_argument("-epochs", type=int, default=10)
-    ap.add_argument("-batch", type=int, default=1024)
-    ap.add_argument("-lr", type=float, default=1e-3)
-    ap.add_argument("-gamma", type=float, default=1e-3)
-    ap.add_argument("-keep", type=float, default=0.5)
-    ap.add_argument("-seed", type=int, default=0)
-    ap.add_argument("-mincov", type=int, default=4)
-    ap.add_argument("-maxcov", type=int, default=160)
-    ap.add_argument("-min_allele_freq", type=float, default=0.15)
+    add_train_args(ap, True, "model name or .ncw file to fine-tune (default: Xavier-uniform)")
     ap.add_argument("-truth_neighbors", action="store_true", help="every site a second time with the truth's heterozygous sites as its neighbours")
     ap.add_argument("-background", action="store_true", help="sample columns under the candidate threshold as further reference-call examples")
     a = ap.parse_args(argv)
-    regions = []
-    for c in a.chrom:
-        name, span = c.rsplit(":", 1)
-        s, e = span.split("-")
-        regions.append((name, int(s), int(e)))
-    thr = {"ont": [0.4, 0.6], "ul_ont": [0.4, 0.6], "ul_ont_extreme": [0.4, 0.6], "pacbio": [0.3, 0.7]}.get(a.seq, [0.4, 0.6])
-    params = dict(sam_path=a.bam, fasta_path=a.ref, truth_vcf=a.vcf, confident_bed=a.bed, out_dir=a.out_dir, chrom_list=regions, seq=a.seq,
-                  mincov=a.mincov, maxcov=a.maxcov, min_allele_freq=a.min_allele_freq, min_nbr_sites=1, threshold=thr, supplementary=False,
-                  exclude_bed=None, init=a.init, epochs=a.epochs, batch=a.batch, lr=a.lr, gamma=a.gamma, keep=a.keep, seed=a.seed,
-                  truth_neighbors=a.truth_neighbors, background=a.background)
-    train_snp_model(params)
+    train_snp_model(dict(snp_params(a), truth_neighbors=a.truth_neighbors, background=a.background))
 
 
 if __name__ == "__main__":

@@ -239,6 +239,24 @@ def test_rejected_kinds():
     tr.close()
 
 
+@pytest.mark.parametrize("wrong", ["x", "mask", "labels", "ref_code"])
+def test_misshapen_inputs_refused(wrong):
+    """a tensor, mask, label array or reference-code array of the wrong shape raises ValueError before the device call, which would read
+    n sites of each; the trainer then still takes a correct step on 3 sites"""
+    x, ref, lab, mask = R.make_inputs(3)
+    bad = dict(x=np.asarray(x), ref_code=np.asarray(ref), labels=np.asarray(lab), mask=np.asarray(mask))
+    assert bad["x"].shape == (3, 5, 41, 5) and bad["mask"].shape == (3, 48) and bad["labels"].shape == (3, 5) and bad["ref_code"].shape == (3,)
+    bad[wrong] = {"x": bad["x"][..., :4], "mask": bad["mask"][:, :32], "labels": bad["labels"][:, 0], "ref_code": bad["ref_code"][:2]}[wrong]
+    tr = train.SnpTrainer(0, weights("xavier3"), max_batch=8)
+    with pytest.raises(ValueError):
+        tr.step(bad["x"], bad["ref_code"], bad["labels"], mask=bad["mask"])
+    assert tr.info()["steps"] == 0
+    losses = tr.step(x, ref, lab, mask=mask)
+    assert tr.info()["steps"] == 1 and np.isfinite([losses[k] for k in R.LOSS_KEYS]).all()
+    assert not np.array_equal(tr.get_weights(), weights("xavier3"))
+    tr.close()
+
+
 def test_train_snp_model_from_files():
     """the file route (truth VCF + confident BED) gives the planted-truth route's examples inside the intervals, and train_snp_model writes
     one loadable model per epoch"""
