@@ -922,7 +922,8 @@ int nc_synth_indel_reads(nc_ctx *ctx, int64_t L, uint64_t seed, double p_sub, do
                          const int32_t *ev_off_dev, const int32_t *ins_off_read_dev, uint8_t *codes_dev, int32_t *ev_pos_dev,
                          int32_t *ev_len_dev, int32_t *ins_off_dev, uint8_t *ins_bases_dev);
 
-/* ------------------------------------------------------------------ read-based SNP phasing and haplotagging (csrc/nc_happhase.hip)
+/* ------------------------------------------------------------------ read-based SNP phasing and haplotagging (csrc/nc_happhase.hip;
+ * nc_snp_phase_realign in nc_hprealign.hip, the three weight exports in nc_hpquals.hip)
  * Replaces the `whatshap phase` + `whatshap haplotag` steps of phase_run (nanocaller_src/indelCaller.py:192-262) with an exact
  * minimum-error-correction phaser over the contig's resident pack (DESIGN.md "Read-based phasing": every step and tie-break).
  * Sites: the het SNP calls of one contig, positions ascending strictly; site_alleles [n_sites][2] = base codes of the first and second

@@ -1,5 +1,6 @@
-// What the phaser (nc_happhase.hip) and its allele detector by realignment (nc_hprealign.hip) share: the phasing handle, the prefix kernel
-// that turns per-read counts into offsets, per-call device scratch.
+// What the phaser (nc_happhase.hip), its allele detector by realignment (nc_hprealign.hip) and its quality reader (nc_hpquals.hip) share: the
+// phasing handle and its set-up, the prefix kernel that turns per-read counts into offsets and the tail that turns them into the entry arrays,
+// the uploads of the CSR and its weights, per-call device scratch.
 #pragma once
 #include "nc_common.h"
 
@@ -98,5 +99,91 @@ static inline int hp_check_sites(nc_ctx *ctx, int32_t n_sites, const int32_t *po
 {
     for (int32_t s = 1; s < n_sites; s++)
         if (pos[s] <= pos[s - 1]) return nc_fail(ctx, NC_ERR_ARG, "phasing sites must ascend strictly (site %d)", s);
+    return NC_OK;
+}
+
+// a handle over the checked sites: ctx, n_reads, n_sites and site_pos filled in, off = n_reads + 1 zeros
+static inline int hp_new_handle(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32_t *site_pos, nc_phase **out)
+{
+    NC_TRY(hp_check_sites(ctx, n_sites, site_pos));
+    nc_phase *ph = new nc_phase();
+    ph->ctx = ctx;
+    ph->n_reads = n_reads;
+    ph->n_sites = n_sites;
+    ph->site_pos.assign(site_pos, site_pos + n_sites);
+    ph->off.assign(n_reads + 1, 0);
+    *out = ph;
+    return NC_OK;
+}
+
+// keeps the first HIP error of a sequence of calls whose later steps ask `rc == NC_OK` before they run
+struct HpErr {
+    nc_ctx *ctx;
+    int rc = NC_OK;
+    void operator()(hipError_t e, const char *what)
+    {
+        if (e != hipSuccess && rc == NC_OK) rc = nc_fail(ctx, NC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    }
+};
+
+// The tail the allele detectors share: the per-read entry counts d_cnt on the device -> ph->d_off and ph->off (k_hp_scan), d_site / d_al
+// allocated for the total, filled by the caller's launch fill() (asked for only where there are reads), esite / eal downloaded.
+// sync_what: the caller's label of the two synchronisations in an error message.  d_flag (or null): a word the caller's kernels raise on malformed input; it comes down with the offsets, and nonzero fails with flag_msg.
+template <class Fill>
+static inline int hp_entries_from_counts(nc_phase *ph, HpErr &hip, const int32_t *d_cnt, const char *sync_what, const int32_t *d_flag, const char *flag_msg,
+                                         Fill fill)
+{
+    nc_ctx *ctx = ph->ctx;
+    const int32_t n_reads = ph->n_reads;
+    int32_t flag = 0;
+    if (hip.rc == NC_OK) {
+        k_hp_scan<<<1, HP_THREADS, 0, ctx->stream>>>(d_cnt, n_reads, ph->d_off);
+        hip(hipGetLastError(), "k_hp_scan");
+        hip(hipMemcpyAsync(ph->off.data(), ph->d_off, (n_reads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream), "offset download");
+        if (d_flag) hip(hipMemcpyAsync(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream), "status download");
+        hip(hipStreamSynchronize(ctx->stream), sync_what);
+    }
+    if (hip.rc == NC_OK && flag) hip.rc = nc_fail(ctx, NC_ERR_ARG, "%s", flag_msg);
+    const int64_t ne = hip.rc == NC_OK ? ph->off[n_reads] : 0;
+    if (hip.rc == NC_OK) {
+        hip(hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16), "hipMalloc(entries)");
+        hip(hipMalloc(&ph->d_al, ne + 16), "hipMalloc(alleles)");
+    }
+    if (hip.rc == NC_OK && n_reads) fill();
+    if (hip.rc == NC_OK) {
+        ph->esite.resize(ne);
+        ph->eal.resize(ne);
+        if (ne) {
+            hip(hipMemcpyAsync(ph->esite.data(), ph->d_site, ne * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream), "entry download");
+            hip(hipMemcpyAsync(ph->eal.data(), ph->d_al, ne, hipMemcpyDeviceToHost, ctx->stream), "allele download");
+        }
+        hip(hipStreamSynchronize(ctx->stream), sync_what);
+    }
+    return hip.rc;
+}
+
+static inline int hp_upload_csr(nc_phase *ph)
+{
+    nc_ctx *ctx = ph->ctx;
+    const int64_t ne = ph->off[ph->n_reads];
+    NC_HIP(ctx, hipMalloc(&ph->d_off, (ph->n_reads + 1) * sizeof(int64_t)));
+    NC_HIP(ctx, hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16));
+    NC_HIP(ctx, hipMalloc(&ph->d_al, ne + 16));
+    NC_HIP(ctx, hipMemcpyAsync(ph->d_off, ph->off.data(), (ph->n_reads + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (ne) {
+        NC_HIP(ctx, hipMemcpyAsync(ph->d_site, ph->esite.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(ph->d_al, ph->eal.data(), ne, hipMemcpyHostToDevice, ctx->stream));
+    }
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NC_OK;
+}
+
+// the weighted model's entry weights beside the CSR in HBM (k_hp_tag<true> reads them)
+static inline int hp_upload_weights(nc_phase *ph)
+{
+    nc_ctx *ctx = ph->ctx;
+    if (!ph->d_w) NC_HIP(ctx, hipMalloc(&ph->d_w, ph->ew.size() + 16));
+    if (!ph->ew.empty()) NC_HIP(ctx, hipMemcpyAsync(ph->d_w, ph->ew.data(), ph->ew.size(), hipMemcpyHostToDevice, ctx->stream));
+    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NC_OK;
 }

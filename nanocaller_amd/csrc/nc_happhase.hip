@@ -7,21 +7,17 @@
 //   k_hp_gather<true>   per read: the (site, allele) CSR entries
 //   (nc_hprealign.hip)  instead of k_hp_gather, opt-in: the alleles by local realignment of the read against both haplotypes
 //   host                read selection (max_cov), blocks, slot assignment, per-column masks, backtrace offsets
-//   k_hp_dp<false>      one workgroup per block: the 2^15 partition costs in LDS (uint16, relative to the column minimum),
-//                       leaving slots minimised out, backtrace in HBM, traceback by the same workgroup
-//   k_hp_dp<true>       opt-in (nc_snp_phase_solve_gt): the same walk with a column cost that may also call the site homozygous
-//                       for either allele, at a price for leaving the called genotype; the traceback records each column's outcome
-//   k_hp_tag            one thread per read-name group: per-block scores -> HP / PS
-//   k_hp_quals          opt-in (nc_snp_phase_weights_from_bam): one wave per kept read walks its BAM record's CIGAR in the inflated record stream
-//                       -> the read's MAPQ and, per CSR entry, the quality of the query base aligned to the site
-//   k_hp_dp<*, true>    the weighted model (DESIGN.md "Read-based phasing", step 6c): an entry's flip costs its weight instead of 1; the
-//   k_hp_tag<true>      column's signed weight sums come from two tables in LDS, the haplotag score adds +-weight
+//   k_hp_dp<GT, W>      one workgroup per block: the 2^15 partition costs in LDS (uint16, relative to the column minimum),
+//                       leaving slots minimised out, backtrace in HBM, traceback by the same workgroup; HpColCost is the column cost of all four forms
+//     GT                opt-in (nc_snp_phase_solve_gt): the column cost may also call the site homozygous for either allele, at a price for
+//                       leaving the called genotype; the traceback records each column's outcome
+//     W                 the weighted model (DESIGN.md "Read-based phasing", step 6c; nc_hpquals.hip sets the weights): an entry's flip costs its
+//                       weight instead of 1; the column's signed weight sums come from two tables in LDS
+//   k_hp_tag<W>         one thread per read-name group: per-block scores (W: +-weight) -> HP / PS
 #include "nc_happhase.h"
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
-#include <type_traits>
 #include <vector>
 
 namespace {
@@ -29,24 +25,10 @@ namespace {
 constexpr int HP_SLOTS = 15;
 constexpr int HP_STATES = 1 << HP_SLOTS;
 constexpr int HP_GT_COST_MAX = 1024;       // (a column's cost stays far inside the DP's 16-bit relative range)
-constexpr int HP_W_MAX = 93;               // the largest entry weight (a BAM quality is a Phred value 0..93)
 constexpr int HP_WTAB = 256 + 128;         // the weighted column's two tables: subsets of slots 0..7, of slots 8..14
 
 struct HpCol {            // one column of a block: the active slots, those continuing from the previous column, the allele masks
     uint16_t act, keep, m0, m1;
-};
-
-struct HpColGt {          // the genotype-aware form's column: the same, and the site's called class (0 het, 1 / 2 homozygous first / second allele)
-    uint16_t act, keep, m0, m1, gt, pad;
-};
-
-// the genotype-aware column cost: het(B) = min(e0, e1) + hadd, against the two constants homA / homB of the column
-struct HpGtCost {
-    uint32_t hadd, homA, homB;
-    __device__ __forceinline__ HpGtCost(uint32_t m0, uint32_t m1, uint32_t gt, uint32_t G)
-        : hadd(gt == 0 ? 0u : G), homA(__popc(m1) + (gt == 1 ? 0u : G)), homB(__popc(m0) + (gt == 2 ? 0u : G))
-    {
-    }
 };
 
 // the weighted form's LDS tables (only its instantiations allocate them): T[x] = sum of d over the slots of x, d[s] = +w on the m1 slots,
@@ -62,16 +44,104 @@ __device__ __forceinline__ int16_t *hp_wtab()
     }
 }
 
-// the weighted e0 = W(m1 & ~B) + W(m0 & B) and e1 = W(m0 & ~B) + W(m1 & B) from the column's slot weights (the traceback's one thread)
-__device__ __forceinline__ void hp_w_costs(const uint8_t *w, uint32_t m0, uint32_t m1, uint32_t B, uint32_t &e0, uint32_t &e1)
-{
-    e0 = e1 = 0;
-    for (int s = 0; s < HP_SLOTS; s++) {
-        const uint32_t b = 1u << s, v = w[s];
-        if (m0 & b) (B & b ? e0 : e1) += v;
-        if (m1 & b) (B & b ? e1 : e0) += v;
+// The cost of column j, stated once for the four forms.  A subset B of the slots puts its reads on the second haplotype: e0 / e1 = what the
+// column's alleles cost when the site's first / second allele lies on the first haplotype, e0 = C(m1 & ~B) + C(m0 & B) and
+// e1 = C(m0 & ~B) + C(m1 & B), C = the number of slots or (W) the sum of their weights w[slot].
+// GT: the site may also come out homozygous: het(B) = min(e0, e1) + hadd against the column's constants homA = C(m1) and homB = C(m0), each
+// with the price G added where it leaves the called class gt (0 het, 1 / 2 homozygous first / second allele).
+template <bool GT, bool W>
+struct HpColCost {
+    uint32_t m0, m1;
+    uint32_t c0 = 0, c1 = 0;                                            // C(m0), C(m1)
+    uint32_t gt = 0, hadd = 0, homA = 0, homB = 0;
+    const uint8_t *w = nullptr;
+    int16_t *T;
+
+    __device__ __forceinline__ HpColCost(const HpCol &c, int32_t j, const uint8_t *site_gt, uint32_t G, const uint8_t *colw, int16_t *T_)
+        : m0(c.m0), m1(c.m1), T(T_)
+    {
+        if constexpr (W) {
+            w = colw + 16 * (int64_t)j;
+            for (int s = 0; s < HP_SLOTS; s++) {
+                c0 += (m0 >> s) & 1 ? w[s] : 0;
+                c1 += (m1 >> s) & 1 ? w[s] : 0;
+            }
+        } else {
+            c0 = __popc(m0);
+            c1 = __popc(m1);
+        }
+        if constexpr (GT) {
+            gt = site_gt[j];
+            hadd = gt == 0 ? 0u : G;
+            homA = c1 + (gt == 1 ? 0u : G);
+            homB = c0 + (gt == 2 ? 0u : G);
+        }
     }
-}
+
+    // (W) threads 0 .. HP_WTAB - 1 write the column's tables; a barrier lies between this and the first pair()
+    __device__ __forceinline__ void fill_table(int tid) const
+    {
+        if constexpr (W) {
+            if (tid < HP_WTAB) {
+                const uint32_t x = tid < 256 ? (uint32_t)tid : (uint32_t)(tid - 256) << 8;
+                int32_t t = 0;
+                for (int s = 0; s < HP_SLOTS; s++)
+                    if ((x >> s) & 1) t += (m1 >> s) & 1 ? (int32_t)w[s] : ((m0 >> s) & 1 ? -(int32_t)w[s] : 0);
+                T[tid] = (int16_t)t;
+            }
+        }
+    }
+
+    // (e0, e1) of B on the parallel path: (W) e1 = C(m0) + T(B), e0 = C(m1) - T(B) from the tables of this column
+    __device__ __forceinline__ void pair(uint32_t B, uint32_t &e0, uint32_t &e1) const
+    {
+        if constexpr (W) {
+            const int32_t tb = T[B & 255] + T[256 + (B >> 8)];
+            e1 = (uint32_t)((int32_t)c0 + tb);
+            e0 = (uint32_t)((int32_t)c1 - tb);
+        } else {
+            e0 = __popc(m1 & ~B) + __popc(m0 & B);
+            e1 = __popc(m0 & ~B) + __popc(m1 & B);
+        }
+    }
+
+    // the same on the traceback's one thread, where the tables hold another column: (W) slot by slot
+    __device__ __forceinline__ void pair_by_slots(uint32_t B, uint32_t &e0, uint32_t &e1) const
+    {
+        if constexpr (W) {
+            e0 = e1 = 0;
+            for (int s = 0; s < HP_SLOTS; s++) {
+                const uint32_t b = 1u << s, v = w[s];
+                if (m0 & b) (B & b ? e0 : e1) += v;
+                if (m1 & b) (B & b ? e1 : e0) += v;
+            }
+        } else {
+            pair(B, e0, e1);
+        }
+    }
+
+    __device__ __forceinline__ uint32_t cost(uint32_t B) const
+    {
+        uint32_t e0, e1;
+        pair(B, e0, e1);
+        return GT ? min(min(e0, e1) + hadd, min(homA, homB)) : min(e0, e1);
+    }
+
+    // the traceback's outcome at B: the site's bit, and (GT) the class of the smallest (cost, pref): pref 0 for the called class, else 1 het,
+    // 2 homozygous first, 3 homozygous second
+    __device__ __forceinline__ void outcome(uint32_t B, int32_t j, uint8_t *colh, uint8_t *colg) const
+    {
+        uint32_t e0, e1;
+        pair_by_slots(B, e0, e1);
+        colh[j] = e0 <= e1 ? 0 : 1;
+        if constexpr (GT) {
+            const uint32_t cost[3] = {min(e0, e1) + hadd, homA, homB};
+            uint32_t best = ~0u;
+            for (uint32_t o = 0; o < 3; o++) best = min(best, (cost[o] << 4) | ((o == gt ? 0u : o + 1) << 2) | o);
+            colg[j] = (uint8_t)(best & 3);
+        }
+    }
+};
 
 __device__ __forceinline__ uint32_t hp_pdep(uint32_t t, uint32_t mask)
 {
@@ -129,14 +199,14 @@ __global__ __launch_bounds__(256) void k_hp_gather(const uint8_t *__restrict__ c
 // One workgroup per block [bfirst, blast] of columns (= sites).  D(j, B) for the subsets B of the active slots lives in LDS as
 // uint16 relative to the column minimum (the minima are summed into the block's cost); P(b) for the subsets of the continuing
 // slots, the backtrace (smallest minimising bits of the leaving slots) per (column, continuing subset) in HBM at bt_off[column].
-// GT: the genotype-aware form (its column carries the called class; gt_cost = the price G of leaving it; colg[column] = the outcome, classed
+// GT: the genotype-aware form (site_gt[column] = the called class; gt_cost = the price G of leaving it; colg[column] = the outcome, classed
 // as the called class is).  The plain form reads neither argument.
 // W: the weighted form (colw[16 * column + slot] = the weight of the slot's allele at the column; unit costs read no weight).
 template <bool GT, bool W>
-__global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<GT, HpColGt, HpCol> *__restrict__ cols, const int32_t *__restrict__ bfirst,
-                                                       const int32_t *__restrict__ blast, const int64_t *__restrict__ bt_off, uint16_t *__restrict__ bt,
-                                                       uint16_t *__restrict__ colB, uint8_t *__restrict__ colh, int64_t *__restrict__ bcost,
-                                                       int32_t *__restrict__ overflow, uint8_t *__restrict__ colg, uint32_t gt_cost,
+__global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const HpCol *__restrict__ cols, const int32_t *__restrict__ bfirst, const int32_t *__restrict__ blast,
+                                                       const int64_t *__restrict__ bt_off, uint16_t *__restrict__ bt, uint16_t *__restrict__ colB,
+                                                       uint8_t *__restrict__ colh, int64_t *__restrict__ bcost, int32_t *__restrict__ overflow,
+                                                       const uint8_t *__restrict__ site_gt, uint8_t *__restrict__ colg, uint32_t gt_cost,
                                                        const uint8_t *__restrict__ colw)
 {
     int16_t *const T = hp_wtab<W>();
@@ -149,33 +219,10 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
     int64_t total = 0;
     uint32_t prevA = 0;
     for (int32_t j = c0; j <= c1; j++) {
-        const auto c = cols[j];
-        const uint32_t A = c.act, K = c.keep, m0 = c.m0, m1 = c.m1;
-        uint32_t hadd = 0, hom = 0;                                      // (GT) het's surcharge, the cheaper homozygous outcome
-        uint32_t Wm0 = 0, Wm1 = 0;                                       // (W) the weights of the m0 / m1 slots
-        if constexpr (W) {
-            const uint8_t *w = colw + 16 * (int64_t)j;
-            for (int s = 0; s < HP_SLOTS; s++) {
-                Wm0 += (m0 >> s) & 1 ? w[s] : 0;
-                Wm1 += (m1 >> s) & 1 ? w[s] : 0;
-            }
-            if (tid < HP_WTAB) {                                         // (the previous column's readers are behind the loop's last barrier)
-                const uint32_t x = tid < 256 ? (uint32_t)tid : (uint32_t)(tid - 256) << 8;
-                int32_t t = 0;
-                for (int s = 0; s < HP_SLOTS; s++)
-                    if ((x >> s) & 1) t += (m1 >> s) & 1 ? (int32_t)w[s] : ((m0 >> s) & 1 ? -(int32_t)w[s] : 0);
-                T[tid] = (int16_t)t;
-            }
-        }
-        if constexpr (GT && !W) {
-            const HpGtCost g(m0, m1, c.gt, gt_cost);
-            hadd = g.hadd;
-            hom = min(g.homA, g.homB);
-        }
-        if constexpr (GT && W) {
-            hadd = c.gt == 0 ? 0u : gt_cost;
-            hom = min(Wm1 + (c.gt == 1 ? 0u : gt_cost), Wm0 + (c.gt == 2 ? 0u : gt_cost));
-        }
+        const HpCol c = cols[j];
+        const uint32_t A = c.act, K = c.keep;
+        const HpColCost<GT, W> col(c, j, site_gt, gt_cost, colw, T);
+        col.fill_table(tid);                                             // (the previous column's readers are behind the loop's last barrier)
         if (j > c0) {
             const uint32_t Lm = prevA & ~K;
             const int nk = __popc(K), nl = __popc(Lm);
@@ -218,16 +265,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
         uint32_t mn = ~0u;
         for (int32_t t = tid; t < NA; t += HP_THREADS) {
             const uint32_t B = hp_pdep(t, A);
-            uint32_t e0, e1;
-            if constexpr (W) {                                           // e1 = W(m0) + T(B), e0 = W(m1) - T(B)
-                const int32_t tb = T[B & 255] + T[256 + (B >> 8)];
-                e1 = (uint32_t)((int32_t)Wm0 + tb);
-                e0 = (uint32_t)((int32_t)Wm1 - tb);
-            } else {
-                e0 = __popc(m1 & ~B) + __popc(m0 & B);
-                e1 = __popc(m0 & ~B) + __popc(m1 & B);
-            }
-            mn = min(mn, (first ? 0u : (uint32_t)P[B & K]) + (GT ? min(min(e0, e1) + hadd, hom) : min(e0, e1)));
+            mn = min(mn, (first ? 0u : (uint32_t)P[B & K]) + col.cost(B));
         }
         mn = hp_wave_min(mn);
         if (lane == 0 && mn != ~0u) atomicMin(&smin, mn);
@@ -235,16 +273,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
         const uint32_t cmin = smin;
         for (int32_t t = tid; t < NA; t += HP_THREADS) {
             const uint32_t B = hp_pdep(t, A);
-            uint32_t e0, e1;
-            if constexpr (W) {                                           // e1 = W(m0) + T(B), e0 = W(m1) - T(B)
-                const int32_t tb = T[B & 255] + T[256 + (B >> 8)];
-                e1 = (uint32_t)((int32_t)Wm0 + tb);
-                e0 = (uint32_t)((int32_t)Wm1 - tb);
-            } else {
-                e0 = __popc(m1 & ~B) + __popc(m0 & B);
-                e1 = __popc(m0 & ~B) + __popc(m1 & B);
-            }
-            const uint32_t v = (first ? 0u : (uint32_t)P[B & K]) + (GT ? min(min(e0, e1) + hadd, hom) : min(e0, e1)) - cmin;
+            const uint32_t v = (first ? 0u : (uint32_t)P[B & K]) + col.cost(B) - cmin;
             if (v > 0xFFFFu) atomicOr(overflow, 1);
             D[B] = (uint16_t)min(v, 0xFFFFu);
         }
@@ -270,29 +299,9 @@ __global__ __launch_bounds__(HP_THREADS) void k_hp_dp(const std::conditional_t<G
     if (tid == 0) {
         uint32_t B = smin & 0xFFFF;
         for (int32_t j = c1; j >= c0; j--) {
-            const auto c = cols[j];
-            uint32_t e0, e1;
-            if constexpr (W) hp_w_costs(colw + 16 * (int64_t)j, c.m0, c.m1, B, e0, e1);
-            else {
-                e0 = __popc(c.m1 & ~B) + __popc(c.m0 & B);
-                e1 = __popc(c.m0 & ~B) + __popc(c.m1 & B);
-            }
+            const HpCol c = cols[j];
             colB[j] = (uint16_t)B;
-            colh[j] = e0 <= e1 ? 0 : 1;
-            if constexpr (GT) {
-                // the smallest (cost, pref): pref 0 for the called class, else 1 het, 2 homozygous first, 3 homozygous second
-                HpGtCost g(c.m0, c.m1, c.gt, gt_cost);
-                if constexpr (W) {                                       // homA = W(m1) (+G), homB = W(m0) (+G)
-                    uint32_t w1, w0;
-                    hp_w_costs(colw + 16 * (int64_t)j, c.m0, c.m1, 0, w1, w0);
-                    g.homA = w1 + (c.gt == 1 ? 0u : gt_cost);
-                    g.homB = w0 + (c.gt == 2 ? 0u : gt_cost);
-                }
-                const uint32_t cost[3] = {min(e0, e1) + g.hadd, g.homA, g.homB};
-                uint32_t best = ~0u;
-                for (uint32_t o = 0; o < 3; o++) best = min(best, (cost[o] << 4) | ((o == c.gt ? 0u : o + 1) << 2) | o);
-                colg[j] = (uint8_t)(best & 3);
-            }
+            HpColCost<GT, W>(c, j, site_gt, gt_cost, colw, T).outcome(B, j, colh, colg);
             if (j > c0) {
                 const uint32_t bk = B & c.keep;
                 B = bk | bt[bt_off[j] + hp_pext(bk, c.keep)];
@@ -364,137 +373,6 @@ __global__ __launch_bounds__(256) void k_hp_tag(int32_t n_groups, const int32_t 
     gps[g] = hp ? best_ps : 0;
 }
 
-// ---- MAPQ and base qualities from the device ingest's inflated record stream (nc_ingest.hip made the pack from the same records)
-__device__ __forceinline__ uint32_t hq_ldu32(const uint8_t *p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-constexpr int HQ_WPB = 4;                                               // waves (reads) per workgroup
-enum { HQ_BAD_RECORD = 1, HQ_BAD_FIELDS = 4 };                          // status bits: the record leaves the stream / its fields leave block_size (k_meta's bit)
-
-// One wave per kept read r (record at raw + rec[r]; entries off[r] .. off[r + 1] in site order).  The CIGAR -- the record's own, or the CG tag's
-// behind the placeholder <l_seq>S<n>N, k_meta's rule -- goes by in chunks of 64 operations, one per lane; prefix sums give every operation its
-// reference and query start, and the lane looks up the read's entries whose site lies in its reference run: under M / = / X the aligned query
-// base's quality, under D / N the last query base's before the operation.  ew = min(quality, w_max); default_weight where there is no base or no
-// quality (0xff), and for an entry outside the alignment.  Everything read is checked against block_size, the stream's length and l_seq.
-__global__ __launch_bounds__(64 * HQ_WPB) void k_hp_quals(const uint8_t *__restrict__ raw, int64_t raw_len, int32_t n_reads, const int64_t *__restrict__ rec,
-                                                          const int64_t *__restrict__ off, const int32_t *__restrict__ esite, const int32_t *__restrict__ spos,
-                                                          int32_t mapq_min, int32_t default_weight, int32_t w_max, uint8_t *__restrict__ ew,
-                                                          uint8_t *__restrict__ mapq, uint8_t *__restrict__ rok, int32_t *__restrict__ status)
-{
-    const int lane = threadIdx.x & 63;
-    const int32_t r = blockIdx.x * HQ_WPB + (threadIdx.x >> 6);
-    if (r >= n_reads) return;
-    const int64_t e0 = off[r], e1 = off[r + 1], o = rec[r];
-    int bad = (o < 0 || o + 36 > raw_len) ? HQ_BAD_RECORD : 0;
-    int64_t bs = 0;
-    if (!bad) {
-        bs = (int32_t)hq_ldu32(raw + o);
-        if (bs < 32 || o + 4 + bs > raw_len) bad = HQ_BAD_RECORD;
-    }
-    const uint8_t *p = raw + (bad ? 0 : o + 4);                          // the record body: p[0, bs)
-    int64_t l_name = 0, n_cig = 0, l_seq = 0, pos = 0;
-    int mq = 0;
-    if (!bad) {
-        pos = (int32_t)hq_ldu32(p + 4);
-        l_name = p[8];
-        mq = p[9];
-        n_cig = p[12] | (p[13] << 8);
-        l_seq = (int32_t)hq_ldu32(p + 16);
-        if (l_seq < 0 || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs) bad = HQ_BAD_FIELDS;
-    }
-    if (bad) {
-        if (lane == 0) {
-            atomicOr(status, bad);
-            mapq[r] = 0;
-            rok[r] = 0;
-        }
-        for (int64_t e = e0 + lane; e < e1; e += 64) ew[e] = (uint8_t)default_weight;
-        return;
-    }
-    int64_t cigo = 32 + l_name, nc = n_cig;                              // the CIGAR: p[cigo, cigo + 4 nc)
-    const int64_t qualo = cigo + 4 * n_cig + (l_seq + 1) / 2, auxo = qualo + l_seq;
-    if (n_cig == 2) {
-        const uint32_t c0 = hq_ldu32(p + cigo), c1 = hq_ldu32(p + cigo + 4);
-        if ((c0 & 15) == 4 && (int64_t)(c0 >> 4) == l_seq && (c1 & 15) == 3) {
-            // the placeholder: the real CIGAR is the CG:B,I tag's (every lane walks the tags alike)
-            for (int64_t a = auxo; a + 3 <= bs;) {
-                const char t0 = (char)p[a], t1 = (char)p[a + 1], ty = (char)p[a + 2];
-                a += 3;
-                switch (ty) {
-                case 'c': case 'C': case 'A': a += 1; break;
-                case 's': case 'S': a += 2; break;
-                case 'i': case 'I': case 'f': a += 4; break;
-                case 'Z': case 'H':
-                    while (a < bs && p[a]) a++;
-                    a++;
-                    break;
-                case 'B': {
-                    if (a + 5 > bs) {
-                        a = bs;
-                        break;
-                    }
-                    const char st = (char)p[a];
-                    const int64_t cnt = hq_ldu32(p + a + 1);
-                    const int es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-                    if (t0 == 'C' && t1 == 'G' && st == 'I' && a + 5 + cnt * 4 <= bs) {
-                        cigo = a + 5;
-                        nc = cnt;
-                    }
-                    a += 5 + cnt * es;
-                    break;
-                }
-                default: a = bs; break;
-                }
-            }
-        }
-    }
-    const int64_t s1 = pos + 1;                                          // the 1-based position of the alignment's first reference base
-    int64_t rp = 0, qp = 0;
-#pragma unroll 1
-    for (int64_t k0 = 0; k0 < nc; k0 += 64) {
-        const int64_t k = k0 + lane;
-        const uint32_t c = k < nc ? hq_ldu32(p + cigo + 4 * k) : 15u;
-        const int op = c & 15;
-        const int32_t len = (int32_t)(c >> 4);
-        const bool m = op == 0 || op == 7 || op == 8, gap = op == 2 || op == 3;
-        const int32_t radv = (m || gap) ? len : 0, qadv = (m || op == 1 || op == 4) ? len : 0;     // (hard clips and pads consume nothing)
-        const int64_t ri = (int64_t)nc_wave_incl_scan(radv & 0xFFFF) + ((int64_t)nc_wave_incl_scan(radv >> 16) << 16);
-        const int64_t qi = (int64_t)nc_wave_incl_scan(qadv & 0xFFFF) + ((int64_t)nc_wave_incl_scan(qadv >> 16) << 16);
-        if (radv > 0) {
-            const int64_t a = s1 + rp + ri - radv, b = a + radv, q0 = qp + qi - qadv;
-            int64_t lo = e0, hi = e1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (spos[esite[mid]] < a) lo = mid + 1;
-                else hi = mid;
-            }
-            for (int64_t e = lo; e < e1; e++) {
-                const int64_t sp = spos[esite[e]];
-                if (sp >= b) break;
-                const int64_t q = m ? q0 + (sp - a) : q0 - 1;
-                int32_t w = default_weight;
-                if (q >= 0 && q < l_seq) {
-                    const int32_t v = p[qualo + q];
-                    if (v != 0xff) w = min(v, w_max);
-                }
-                ew[e] = (uint8_t)w;
-            }
-        }
-        rp += __shfl(ri, 63);
-        qp += __shfl(qi, 63);
-    }
-    for (int64_t e = e0 + lane; e < e1; e += 64) {                       // entries the alignment does not reach
-        const int64_t sp = spos[esite[e]];
-        if (sp < s1 || sp >= s1 + rp) ew[e] = (uint8_t)default_weight;
-    }
-    if (lane == 0) {
-        mapq[r] = (uint8_t)mq;
-        rok[r] = mq >= mapq_min ? 1 : 0;
-    }
-}
-
 }  // namespace
 
 static void hp_free_dev(nc_phase *ph)
@@ -509,32 +387,6 @@ static void hp_free_dev(nc_phase *ph)
     ph->d_al = nullptr;
 }
 
-static int hp_upload_csr(nc_phase *ph)
-{
-    nc_ctx *ctx = ph->ctx;
-    const int64_t ne = ph->off[ph->n_reads];
-    NC_HIP(ctx, hipMalloc(&ph->d_off, (ph->n_reads + 1) * sizeof(int64_t)));
-    NC_HIP(ctx, hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16));
-    NC_HIP(ctx, hipMalloc(&ph->d_al, ne + 16));
-    NC_HIP(ctx, hipMemcpyAsync(ph->d_off, ph->off.data(), (ph->n_reads + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ne) {
-        NC_HIP(ctx, hipMemcpyAsync(ph->d_site, ph->esite.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        NC_HIP(ctx, hipMemcpyAsync(ph->d_al, ph->eal.data(), ne, hipMemcpyHostToDevice, ctx->stream));
-    }
-    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NC_OK;
-}
-
-// the weighted model's entry weights beside the CSR in HBM (k_hp_tag<true> reads them)
-static int hp_upload_weights(nc_phase *ph)
-{
-    nc_ctx *ctx = ph->ctx;
-    if (!ph->d_w) NC_HIP(ctx, hipMalloc(&ph->d_w, ph->ew.size() + 16));
-    if (!ph->ew.empty()) NC_HIP(ctx, hipMemcpyAsync(ph->d_w, ph->ew.data(), ph->ew.size(), hipMemcpyHostToDevice, ctx->stream));
-    NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NC_OK;
-}
-
 extern "C" {
 
 int nc_snp_phase_gather(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, int32_t n_reads, const int32_t *rd_start, const int32_t *rd_end,
@@ -544,64 +396,36 @@ int nc_snp_phase_gather(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, in
         return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_gather: bad argument");
     (void)codes_len;
     *out = nullptr;
-    NC_TRY(hp_check_sites(ctx, n_sites, site_pos));
     const double t0 = hp_now_ms();
-    nc_phase *ph = new nc_phase();
-    ph->ctx = ctx;
-    ph->n_reads = n_reads;
-    ph->n_sites = n_sites;
-    ph->site_pos.assign(site_pos, site_pos + n_sites);
-    ph->off.assign(n_reads + 1, 0);
-    int rc = NC_OK;
+    nc_phase *ph = nullptr;
+    NC_TRY(hp_new_handle(ctx, n_reads, n_sites, site_pos, &ph));
+    HpErr hip{ctx};
     {
         HpScratch sc;
         int32_t *d_spos = nullptr, *d_cnt = nullptr;
         uint8_t *d_sal = nullptr;
-        auto hip = [&](hipError_t e, const char *what) {
-            if (e != hipSuccess && rc == NC_OK) rc = nc_fail(ctx, NC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-        };
-        if ((rc = sc.get(ctx, &d_spos, n_sites + 1)) || (rc = sc.get(ctx, &d_sal, 2 * (size_t)n_sites + 2)) || (rc = sc.get(ctx, &d_cnt, n_reads + 1))) {
+        if ((hip.rc = sc.get(ctx, &d_spos, n_sites + 1)) || (hip.rc = sc.get(ctx, &d_sal, 2 * (size_t)n_sites + 2)) || (hip.rc = sc.get(ctx, &d_cnt, n_reads + 1))) {
             nc_snp_phase_free(ph);
-            return rc;
+            return hip.rc;
         }
         hip(hipMalloc(&ph->d_off, (n_reads + 1) * sizeof(int64_t)), "hipMalloc(offsets)");
-        if (n_sites && rc == NC_OK) {
+        if (n_sites && hip.rc == NC_OK) {
             hip(hipMemcpyAsync(d_spos, site_pos, n_sites * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "site upload");
             hip(hipMemcpyAsync(d_sal, site_alleles, 2 * (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream), "allele upload");
         }
         const int nb = (n_reads + 255) / 256;
-        if (n_reads && rc == NC_OK) {
+        if (n_reads && hip.rc == NC_OK) {
             k_hp_gather<false><<<nb, 256, 0, ctx->stream>>>(codes, n_reads, rd_start, rd_end, slot_off, n_sites, d_spos, d_sal, d_cnt, nullptr, nullptr, nullptr);
             hip(hipGetLastError(), "k_hp_gather (count)");
         }
-        if (rc == NC_OK) {
-            k_hp_scan<<<1, HP_THREADS, 0, ctx->stream>>>(d_cnt, n_reads, ph->d_off);
-            hip(hipGetLastError(), "k_hp_scan");
-            hip(hipMemcpyAsync(ph->off.data(), ph->d_off, (n_reads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream), "offset download");
-            hip(hipStreamSynchronize(ctx->stream), "gather sync");
-        }
-        const int64_t ne = rc == NC_OK ? ph->off[n_reads] : 0;
-        if (rc == NC_OK) {
-            hip(hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16), "hipMalloc(entries)");
-            hip(hipMalloc(&ph->d_al, ne + 16), "hipMalloc(alleles)");
-        }
-        if (rc == NC_OK && n_reads) {
+        hp_entries_from_counts(ph, hip, d_cnt, "gather sync", nullptr, nullptr, [&] {
             k_hp_gather<true><<<nb, 256, 0, ctx->stream>>>(codes, n_reads, rd_start, rd_end, slot_off, n_sites, d_spos, d_sal, nullptr, ph->d_off, ph->d_site, ph->d_al);
             hip(hipGetLastError(), "k_hp_gather (fill)");
-        }
-        if (rc == NC_OK) {
-            ph->esite.resize(ne);
-            ph->eal.resize(ne);
-            if (ne) {
-                hip(hipMemcpyAsync(ph->esite.data(), ph->d_site, ne * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream), "entry download");
-                hip(hipMemcpyAsync(ph->eal.data(), ph->d_al, ne, hipMemcpyDeviceToHost, ctx->stream), "allele download");
-            }
-            hip(hipStreamSynchronize(ctx->stream), "gather sync");
-        }
+        });
     }
-    if (rc != NC_OK) {
+    if (hip.rc != NC_OK) {
         nc_snp_phase_free(ph);
-        return rc;
+        return hip.rc;
     }
     ph->ms[0] = (float)(hp_now_ms() - t0);
     *out = ph;
@@ -613,23 +437,21 @@ int nc_snp_phase_load(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32
 {
     if (!ctx || !out || n_reads < 0 || n_sites < 0 || !entry_off || (n_sites && !site_pos)) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: bad argument");
     *out = nullptr;
-    NC_TRY(hp_check_sites(ctx, n_sites, site_pos));
-    if (entry_off[0] != 0) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: entry_off[0] != 0");
-    for (int32_t r = 0; r < n_reads; r++) {
-        if (entry_off[r + 1] < entry_off[r]) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: offsets descend at read %d", r);
-        for (int64_t e = entry_off[r]; e < entry_off[r + 1]; e++)
+    nc_phase *ph = nullptr;
+    NC_TRY(hp_new_handle(ctx, n_reads, n_sites, site_pos, &ph));
+    int rc = entry_off[0] != 0 ? nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: entry_off[0] != 0") : NC_OK;
+    for (int32_t r = 0; r < n_reads && rc == NC_OK; r++) {
+        if (entry_off[r + 1] < entry_off[r]) rc = nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: offsets descend at read %d", r);
+        for (int64_t e = entry_off[r]; e < entry_off[r + 1] && rc == NC_OK; e++)
             if (entry_site[e] < 0 || entry_site[e] >= n_sites || entry_allele[e] > 1 || (e > entry_off[r] && entry_site[e] <= entry_site[e - 1]))
-                return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: read %d: sites must ascend inside [0, n_sites), alleles 0 / 1", r);
+                rc = nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_load: read %d: sites must ascend inside [0, n_sites), alleles 0 / 1", r);
     }
-    nc_phase *ph = new nc_phase();
-    ph->ctx = ctx;
-    ph->n_reads = n_reads;
-    ph->n_sites = n_sites;
-    ph->site_pos.assign(site_pos, site_pos + n_sites);
-    ph->off.assign(entry_off, entry_off + n_reads + 1);
-    ph->esite.assign(entry_site, entry_site + entry_off[n_reads]);
-    ph->eal.assign(entry_allele, entry_allele + entry_off[n_reads]);
-    const int rc = hp_upload_csr(ph);
+    if (rc == NC_OK) {
+        ph->off.assign(entry_off, entry_off + n_reads + 1);
+        ph->esite.assign(entry_site, entry_site + entry_off[n_reads]);
+        ph->eal.assign(entry_allele, entry_allele + entry_off[n_reads]);
+        rc = hp_upload_csr(ph);
+    }
     if (rc != NC_OK) {
         nc_snp_phase_free(ph);
         return rc;
@@ -638,141 +460,185 @@ int nc_snp_phase_load(nc_ctx *ctx, int32_t n_reads, int32_t n_sites, const int32
     return NC_OK;
 }
 
-// site_gt: null for the plain solve; else the called class of every site, and gt_cost the price of leaving it (the genotype-aware form)
-static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost)
-{
-    const double t0 = hp_now_ms();
-    const int32_t R = ph->n_reads, S = ph->n_sites;
-    const std::vector<int64_t> &off = ph->off;
-    const std::vector<int32_t> &es = ph->esite;
+}  // extern "C"
+
+// ---- the solve (DESIGN.md "Read-based phasing", steps 2 to 6), one step per function; every order and tie-break below is part of the algorithm
+namespace {
+
+using HpDpKernel = decltype(&k_hp_dp<false, false>);
+const HpDpKernel hp_dp_kernel[2][2] = {{k_hp_dp<false, false>, k_hp_dp<false, true>}, {k_hp_dp<true, false>, k_hp_dp<true, true>}};      // [gt][weighted]
+
+struct HpSolve {
+    nc_ctx *ctx;
+    nc_phase *ph;
+    const int32_t R, S;
+    const std::vector<int64_t> &off;
+    const std::vector<int32_t> &es;
+    // what the steps hand on
+    std::vector<uint8_t> acc;          // per read: accepted by read selection
+    std::vector<std::vector<int32_t>> enter, ending;     // per site: the accepted reads whose span starts / ends there, in read-index order
+    std::vector<int8_t> slot;          // per accepted read: its slot 0 .. 14
+    std::vector<HpCol> cols;           // per site (one spare)
+    std::vector<uint8_t> colw;         // weighted: 16 per site, the weight of every slot's allele
+    std::vector<int64_t> bt_off;       // per site: where the column's backtrace starts; bt_total entries in all
+    int64_t bt_total = 0;
+    std::vector<uint16_t> colB;        // the device run's traceback per site: the partition, the site's bit, (genotype-aware) the outcome
+    std::vector<uint8_t> colh, colg;
+
+    HpSolve(nc_ctx *c, nc_phase *p) : ctx(c), ph(p), R(p->n_reads), S(p->n_sites), off(p->off), es(p->esite) {}
+
     // read selection: most informative sites first, then the first site, then the read index
-    std::vector<int32_t> order;
-    const bool weighted = ph->weighted;                                 // (a read the MAPQ floor refuses is never accepted)
-    for (int32_t r = 0; r < R; r++)
-        if (off[r + 1] - off[r] >= 2 && (!weighted || ph->rok[r])) order.push_back(r);
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        const int64_t na = off[a + 1] - off[a], nb = off[b + 1] - off[b];
-        if (na != nb) return na > nb;
-        if (es[off[a]] != es[off[b]]) return es[off[a]] < es[off[b]];
-        return a < b;
-    });
-    std::vector<int32_t> cov(S, 0);
-    std::vector<uint8_t> acc(R, 0);
-    for (int32_t r : order) {
-        const int32_t a = es[off[r]], b = es[off[r + 1] - 1];
-        bool ok = true;
-        for (int32_t s = a; s <= b && ok; s++) ok = cov[s] < max_cov;
-        if (!ok) continue;
-        for (int32_t s = a; s <= b; s++) cov[s]++;
-        acc[r] = 1;
+    void select_reads(int32_t max_cov)
+    {
+        std::vector<int32_t> order;
+        for (int32_t r = 0; r < R; r++)                                  // (a read the MAPQ floor refuses is never accepted)
+            if (off[r + 1] - off[r] >= 2 && (!ph->weighted || ph->rok[r])) order.push_back(r);
+        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+            const int64_t na = off[a + 1] - off[a], nb = off[b + 1] - off[b];
+            if (na != nb) return na > nb;
+            if (es[off[a]] != es[off[b]]) return es[off[a]] < es[off[b]];
+            return a < b;
+        });
+        std::vector<int32_t> cov(S, 0);
+        acc.assign(R, 0);
+        for (int32_t r : order) {
+            const int32_t a = es[off[r]], b = es[off[r + 1] - 1];
+            bool ok = true;
+            for (int32_t s = a; s <= b && ok; s++) ok = cov[s] < max_cov;
+            if (!ok) continue;
+            for (int32_t s = a; s <= b; s++) cov[s]++;
+            acc[r] = 1;
+        }
     }
+
+    // the handle's result as that of a contig without blocks: nothing phased, no read placed; (genotype-aware) every outcome the call
+    void reset_result(const uint8_t *site_gt)
+    {
+        ph->site_block.assign(S, -1);
+        ph->site_h.assign(S, 0);
+        ph->site_phased.assign(S, 0);
+        ph->site_ps.assign(S, 0);
+        ph->site_gt.clear();
+        if (site_gt) ph->site_gt.assign(site_gt, site_gt + S);
+        ph->side.assign(R, -1);
+        ph->block_first.clear();
+        ph->block_last.clear();
+        ph->block_ps.clear();
+    }
+
     // blocks: consecutive sites share a block when an accepted span covers both
-    std::vector<int32_t> link(S + 1, 0);
-    std::vector<int32_t> starts_at(S + 1, 0), ends_at(S + 1, 0);
-    std::vector<std::vector<int32_t>> enter(S);
-    for (int32_t r = 0; r < R; r++) {
-        if (!acc[r]) continue;
-        const int32_t a = es[off[r]], b = es[off[r + 1] - 1];
-        link[a]++;
-        link[b]--;                                   // link[i] > 0 after the prefix: sites i and i + 1 joined
-        enter[a].push_back(r);                       // read-index order (r ascends)
-    }
-    ph->site_block.assign(S, -1);
-    ph->site_h.assign(S, 0);
-    ph->site_phased.assign(S, 0);
-    ph->site_ps.assign(S, 0);
-    ph->site_gt.clear();
-    if (site_gt) ph->site_gt.assign(site_gt, site_gt + S);              // outside the blocks the outcome is the call
-    ph->side.assign(R, -1);
-    ph->block_first.clear();
-    ph->block_last.clear();
-    ph->block_ps.clear();
-    for (int32_t s = 1; s <= S; s++) link[s] += link[s - 1];
-    for (int32_t s = 0; s < S;) {
-        if (link[s] <= 0) {
-            s++;
-            continue;
+    void cut_blocks()
+    {
+        std::vector<int32_t> link(S + 1, 0);
+        enter.assign(S, {});
+        for (int32_t r = 0; r < R; r++) {
+            if (!acc[r]) continue;
+            const int32_t a = es[off[r]], b = es[off[r + 1] - 1];
+            link[a]++;
+            link[b]--;                               // link[i] > 0 after the prefix: sites i and i + 1 joined
+            enter[a].push_back(r);
         }
-        int32_t e = s;
-        while (e < S && link[e] > 0) e++;            // sites s .. e form a block
-        ph->block_first.push_back(s);
-        ph->block_last.push_back(e);
-        s = e + 1;
-    }
-    const int32_t nblk = (int32_t)ph->block_first.size();
-    // slots and the per-column masks
-    std::vector<HpCol> cols(S + 1, HpCol{0, 0, 0, 0});
-    std::vector<int8_t> slot(R, -1);
-    std::vector<std::vector<int32_t>> ending(S);
-    for (int32_t bi = 0; bi < nblk; bi++) {
-        uint32_t freem = (1u << HP_SLOTS) - 1, act = 0;
-        for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi]; c++) {
-            ph->site_block[c] = bi;
-            if (c > ph->block_first[bi])
-                for (int32_t r : ending[c - 1]) {
-                    freem |= 1u << slot[r];
-                    act &= ~(1u << slot[r]);
-                }
-            uint32_t entering = 0;
-            for (int32_t r : enter[c]) {
-                if (!freem) return nc_fail(ctx, NC_ERR_STATE, "nc_snp_phase_solve: more than %d reads active", HP_SLOTS);
-                const int sl = __builtin_ctz(freem);
-                freem &= freem - 1;
-                slot[r] = (int8_t)sl;
-                entering |= 1u << sl;
-                ending[es[off[r + 1] - 1]].push_back(r);
+        for (int32_t s = 1; s <= S; s++) link[s] += link[s - 1];
+        for (int32_t s = 0; s < S;) {
+            if (link[s] <= 0) {
+                s++;
+                continue;
             }
-            act |= entering;
-            cols[c].act = (uint16_t)act;
-            cols[c].keep = (uint16_t)(act & ~entering);
+            int32_t e = s;
+            while (e < S && link[e] > 0) e++;        // sites s .. e form a block
+            ph->block_first.push_back(s);
+            ph->block_last.push_back(e);
+            s = e + 1;
         }
     }
-    for (int32_t r = 0; r < R; r++) {
-        if (!acc[r]) continue;
-        for (int64_t e = off[r]; e < off[r + 1]; e++) {
-            const int32_t c = es[e];
-            (ph->eal[e] ? cols[c].m1 : cols[c].m0) |= (uint16_t)(1u << slot[r]);
-            ph->site_phased[c] = 1;
+
+    // slots: a read entering at a column takes the lowest free slot, in read-index order; the column's act / keep
+    int assign_slots()
+    {
+        ending.assign(S, {});
+        cols.assign(S + 1, HpCol{0, 0, 0, 0});
+        slot.assign(R, -1);
+        for (size_t bi = 0; bi < ph->block_first.size(); bi++) {
+            uint32_t freem = (1u << HP_SLOTS) - 1, act = 0;
+            for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi]; c++) {
+                ph->site_block[c] = (int32_t)bi;
+                if (c > ph->block_first[bi])
+                    for (int32_t r : ending[c - 1]) {
+                        freem |= 1u << slot[r];
+                        act &= ~(1u << slot[r]);
+                    }
+                uint32_t entering = 0;
+                for (int32_t r : enter[c]) {
+                    if (!freem) return nc_fail(ctx, NC_ERR_STATE, "nc_snp_phase_solve: more than %d reads active", HP_SLOTS);
+                    const int sl = __builtin_ctz(freem);
+                    freem &= freem - 1;
+                    slot[r] = (int8_t)sl;
+                    entering |= 1u << sl;
+                    ending[es[off[r + 1] - 1]].push_back(r);
+                }
+                act |= entering;
+                cols[c].act = (uint16_t)act;
+                cols[c].keep = (uint16_t)(act & ~entering);
+            }
         }
+        return NC_OK;
     }
-    std::vector<uint8_t> colw;                                          // weighted: the weight of every column's slots
-    if (weighted) {
+
+    // a column's allele masks and (weighted) slot weights from the accepted reads' entries; a site with an accepted allele counts as phased
+    void fill_masks()
+    {
+        // plain pointers: through the members, with byte stores in the loop, this step measured 1 ms slower on the 1.8 M entries of a chr20-sized contig
+        HpCol *col = cols.data();
+        uint8_t *phased = ph->site_phased.data();
+        const uint8_t *al = ph->eal.data();
+        const int32_t *site = es.data();
+        for (int32_t r = 0; r < R; r++) {
+            if (!acc[r]) continue;
+            const int sl = slot[r];
+            for (int64_t e = off[r], e1 = off[r + 1]; e < e1; e++) {
+                const int32_t c = site[e];
+                (al[e] ? col[c].m1 : col[c].m0) |= (uint16_t)(1u << sl);
+                phased[c] = 1;
+            }
+        }
+        if (!ph->weighted) return;
         colw.assign(16 * (size_t)(S + 1), 0);
+        uint8_t *cw = colw.data();
+        const uint8_t *ew = ph->ew.data();
         for (int32_t r = 0; r < R; r++)
             if (acc[r])
-                for (int64_t e = off[r]; e < off[r + 1]; e++) colw[16 * (size_t)es[e] + slot[r]] = ph->ew[e];
+                for (int64_t e = off[r], e1 = off[r + 1]; e < e1; e++) cw[16 * (size_t)site[e] + slot[r]] = ew[e];
     }
-    std::vector<int64_t> bt_off(S + 1, 0);
-    int64_t bt_total = 0;
-    for (int32_t bi = 0; bi < nblk; bi++)
-        for (int32_t c = ph->block_first[bi] + 1; c <= ph->block_last[bi]; c++) {
-            bt_off[c] = bt_total;
-            bt_total += 1ll << __builtin_popcount(cols[c].keep);
-        }
-    ph->ms[1] = (float)(hp_now_ms() - t0);
-    const double t1 = hp_now_ms();
-    std::vector<uint16_t> colB(S + 1, 0);
-    std::vector<uint8_t> colh(S + 1, 0), colg(S + 1, 0);
-    ph->block_cost.assign(nblk, 0);
-    int32_t overflow = 0;
-    if (nblk) {
+
+    // the backtrace of a block's columns behind its first: one entry per subset of the continuing slots
+    void layout_backtrace()
+    {
+        bt_off.assign(S + 1, 0);
+        for (size_t bi = 0; bi < ph->block_first.size(); bi++)
+            for (int32_t c = ph->block_first[bi] + 1; c <= ph->block_last[bi]; c++) {
+                bt_off[c] = bt_total;
+                bt_total += 1ll << __builtin_popcount(cols[c].keep);
+            }
+    }
+
+    // the device run, one workgroup per block (not launched where no block formed) -> block_cost and the traceback per site
+    // site_gt: null for the plain form; else the called class of every site, and gt_cost the price of leaving it
+    int run_dp(const uint8_t *site_gt, int32_t gt_cost)
+    {
+        const int32_t nblk = (int32_t)ph->block_first.size();
+        colB.assign(S + 1, 0);
+        colh.assign(S + 1, 0);
+        colg.assign(S + 1, 0);
+        ph->block_cost.assign(nblk, 0);
+        if (!nblk) return NC_OK;
+        int32_t overflow = 0;
         HpScratch sc;
         HpCol *d_cols = nullptr;
-        HpColGt *d_gcols = nullptr;
-        uint8_t *d_colg = nullptr;
         int32_t *d_bf = nullptr, *d_bl = nullptr, *d_ovf = nullptr;
         int64_t *d_bto = nullptr, *d_cost = nullptr;
         uint16_t *d_bt = nullptr, *d_colB = nullptr;
-        uint8_t *d_colh = nullptr, *d_colw = nullptr;
-        std::vector<HpColGt> gcols;
-        if (site_gt) {
-            gcols.assign(S + 1, HpColGt{0, 0, 0, 0, 0, 0});
-            for (int32_t s = 0; s < S; s++) gcols[s] = HpColGt{cols[s].act, cols[s].keep, cols[s].m0, cols[s].m1, site_gt[s], 0};
-            NC_TRY(sc.get(ctx, &d_gcols, S + 1));
-            NC_TRY(sc.get(ctx, &d_colg, S + 1));
-        } else {
-            NC_TRY(sc.get(ctx, &d_cols, S + 1));
-        }
+        uint8_t *d_colh = nullptr, *d_colw = nullptr, *d_gt = nullptr, *d_colg = nullptr;
+        NC_TRY(sc.get(ctx, &d_cols, S + 1));
         NC_TRY(sc.get(ctx, &d_bf, nblk));
         NC_TRY(sc.get(ctx, &d_bl, nblk));
         NC_TRY(sc.get(ctx, &d_ovf, 1));
@@ -781,24 +647,22 @@ static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *s
         NC_TRY(sc.get(ctx, &d_bt, bt_total + 1));
         NC_TRY(sc.get(ctx, &d_colB, S + 1));
         NC_TRY(sc.get(ctx, &d_colh, S + 1));
-        if (site_gt) NC_HIP(ctx, hipMemcpyAsync(d_gcols, gcols.data(), (S + 1) * sizeof(HpColGt), hipMemcpyHostToDevice, ctx->stream));
-        else NC_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (S + 1) * sizeof(HpCol), hipMemcpyHostToDevice, ctx->stream));
+        NC_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (S + 1) * sizeof(HpCol), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bf, ph->block_first.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bl, ph->block_last.data(), nblk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(d_bto, bt_off.data(), (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         NC_HIP(ctx, hipMemsetAsync(d_ovf, 0, sizeof(int32_t), ctx->stream));
-        if (weighted) {
+        if (site_gt) {
+            NC_TRY(sc.get(ctx, &d_gt, S + 1));
+            NC_TRY(sc.get(ctx, &d_colg, S + 1));
+            NC_HIP(ctx, hipMemcpyAsync(d_gt, site_gt, S, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (ph->weighted) {
             NC_TRY(sc.get(ctx, &d_colw, colw.size()));
             NC_HIP(ctx, hipMemcpyAsync(d_colw, colw.data(), colw.size(), hipMemcpyHostToDevice, ctx->stream));
         }
-        if (site_gt && weighted)
-            k_hp_dp<true, true><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_gcols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_colg, (uint32_t)gt_cost, d_colw);
-        else if (weighted)
-            k_hp_dp<false, true><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, nullptr, 0, d_colw);
-        else if (site_gt)
-            k_hp_dp<true, false><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_gcols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_colg, (uint32_t)gt_cost, nullptr);
-        else
-            k_hp_dp<false, false><<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, nullptr, 0, nullptr);
+        hp_dp_kernel[site_gt != nullptr][ph->weighted]<<<nblk, HP_THREADS, 0, ctx->stream>>>(d_cols, d_bf, d_bl, d_bto, d_bt, d_colB, d_colh, d_cost, d_ovf, d_gt,
+                                                                                             d_colg, (uint32_t)gt_cost, d_colw);
         NC_HIP(ctx, hipGetLastError());
         NC_HIP(ctx, hipMemcpyAsync(colB.data(), d_colB, (S + 1) * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(colh.data(), d_colh, S + 1, hipMemcpyDeviceToHost, ctx->stream));
@@ -806,28 +670,54 @@ static int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *s
         NC_HIP(ctx, hipMemcpyAsync(ph->block_cost.data(), d_cost, nblk * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipMemcpyAsync(&overflow, d_ovf, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (overflow) return nc_fail(ctx, NC_ERR_CAPACITY, "nc_snp_phase_solve: a partition cost exceeds 65535 above its column's minimum");
+        return NC_OK;
     }
-    if (overflow) return nc_fail(ctx, NC_ERR_CAPACITY, "nc_snp_phase_solve: a partition cost exceeds 65535 above its column's minimum");
-    for (int32_t s = 0; s < S; s++) ph->site_h[s] = ph->site_block[s] >= 0 ? colh[s] : 0;
-    if (site_gt)                                                        // a site is phased when it has an accepted allele and comes out het
-        for (int32_t s = 0; s < S; s++) {
-            if (ph->site_block[s] >= 0) ph->site_gt[s] = colg[s];
-            if (ph->site_gt[s] != 0) ph->site_phased[s] = 0;
+
+    // the traceback into the handle: site_h, (genotype-aware) the outcomes, site_phased, the phase sets, the reads' sides
+    void write_back(const uint8_t *site_gt)
+    {
+        for (int32_t s = 0; s < S; s++) ph->site_h[s] = ph->site_block[s] >= 0 ? colh[s] : 0;
+        if (site_gt)                                                     // a site is phased when it has an accepted allele and comes out het
+            for (int32_t s = 0; s < S; s++) {
+                if (ph->site_block[s] >= 0) ph->site_gt[s] = colg[s];
+                if (ph->site_gt[s] != 0) ph->site_phased[s] = 0;
+            }
+        for (size_t bi = 0; bi < ph->block_first.size(); bi++) {
+            int32_t ps = 0;
+            for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi] && !ps; c++)
+                if (ph->site_phased[c]) ps = ph->site_pos[c];
+            ph->block_ps.push_back(ps);
+            for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi]; c++)
+                if (ph->site_phased[c]) ph->site_ps[c] = ps;
         }
-    for (int32_t bi = 0; bi < nblk; bi++) {
-        int32_t ps = 0;
-        for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi] && !ps; c++)
-            if (ph->site_phased[c]) ps = ph->site_pos[c];
-        ph->block_ps.push_back(ps);
-        for (int32_t c = ph->block_first[bi]; c <= ph->block_last[bi]; c++)
-            if (ph->site_phased[c]) ph->site_ps[c] = ps;
+        for (int32_t r = 0; r < R; r++)
+            if (acc[r]) ph->side[r] = (int8_t)((colB[es[off[r]]] >> slot[r]) & 1);
     }
-    for (int32_t r = 0; r < R; r++)
-        if (acc[r]) ph->side[r] = (int8_t)((colB[es[off[r]]] >> slot[r]) & 1);
+};
+
+int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost)
+{
+    const double t0 = hp_now_ms();
+    HpSolve sv(ctx, ph);
+    sv.select_reads(max_cov);
+    sv.reset_result(site_gt);
+    sv.cut_blocks();
+    NC_TRY(sv.assign_slots());
+    sv.fill_masks();
+    sv.layout_backtrace();
+    ph->ms[1] = (float)(hp_now_ms() - t0);
+    const double t1 = hp_now_ms();
+    NC_TRY(sv.run_dp(site_gt, gt_cost));
+    sv.write_back(site_gt);
     ph->ms[2] = (float)(hp_now_ms() - t1);
     ph->solved = true;
     return NC_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int nc_snp_phase_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov)
 {
@@ -934,78 +824,6 @@ int nc_snp_phase_genotypes(const nc_phase *ph, const uint8_t **site_gt)
 {
     if (!ph || !site_gt) return NC_ERR_ARG;
     *site_gt = ph->solved && !ph->site_gt.empty() ? ph->site_gt.data() : nullptr;
-    return NC_OK;
-}
-
-int nc_snp_phase_set_weights(nc_ctx *ctx, nc_phase *ph, const uint8_t *entry_weight, const uint8_t *read_ok)
-{
-    if (!ctx || !ph) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_set_weights: bad argument");
-    const int64_t ne = ph->off[ph->n_reads];
-    for (int64_t e = 0; entry_weight && e < ne; e++)
-        if (entry_weight[e] > HP_W_MAX) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_set_weights: entry %lld: weight %d above %d", (long long)e, entry_weight[e], HP_W_MAX);
-    for (int32_t r = 0; read_ok && r < ph->n_reads; r++)
-        if (read_ok[r] > 1) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_set_weights: read %d: read_ok must be 0 or 1", r);
-    if (entry_weight) ph->ew.assign(entry_weight, entry_weight + ne);
-    else ph->ew.assign(ne, 1);
-    if (read_ok) ph->rok.assign(read_ok, read_ok + ph->n_reads);
-    else ph->rok.assign(ph->n_reads, 1);
-    ph->rmapq.assign(ph->n_reads, 0);
-    ph->weighted = true;
-    ph->solved = false;
-    return hp_upload_weights(ph);
-}
-
-int nc_snp_phase_weights_from_bam(nc_ctx *ctx, nc_phase *ph, const uint8_t *d_raw, int64_t raw_len, const int64_t *d_rec_off, int32_t mapq_min,
-                                  int32_t default_weight, int32_t w_max)
-{
-    if (!ctx || !ph || raw_len < 0 || (ph->n_reads && (!d_raw || !d_rec_off)))
-        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_weights_from_bam: bad argument");
-    if (mapq_min < 0 || mapq_min > 255 || default_weight < 0 || default_weight > HP_W_MAX || w_max < 0 || w_max > HP_W_MAX)
-        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_weights_from_bam: mapq_min outside [0, 255], or default_weight / w_max outside [0, %d]", HP_W_MAX);
-    const int32_t R = ph->n_reads, S = ph->n_sites;
-    const int64_t ne = ph->off[R];
-    std::vector<uint8_t> ew(ne, 0), mq(R, 0), ok(R, 0);
-    int32_t status = 0;
-    if (!ph->d_off) NC_TRY(hp_upload_csr(ph));
-    if (!ph->d_w) NC_HIP(ctx, hipMalloc(&ph->d_w, ne + 16));
-    if (R) {
-        HpScratch sc;
-        int32_t *d_spos = nullptr, *d_status = nullptr;
-        uint8_t *d_mq = nullptr, *d_ok = nullptr;
-        NC_TRY(sc.get(ctx, &d_spos, S + 1));
-        NC_TRY(sc.get(ctx, &d_status, 1));
-        NC_TRY(sc.get(ctx, &d_mq, R));
-        NC_TRY(sc.get(ctx, &d_ok, R));
-        if (S) NC_HIP(ctx, hipMemcpyAsync(d_spos, ph->site_pos.data(), S * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        NC_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream));
-        k_hp_quals<<<(R + HQ_WPB - 1) / HQ_WPB, 64 * HQ_WPB, 0, ctx->stream>>>(d_raw, raw_len, R, d_rec_off, ph->d_off, ph->d_site, d_spos, mapq_min, default_weight,
-                                                                             w_max, ph->d_w, d_mq, d_ok, d_status);
-        NC_HIP(ctx, hipGetLastError());
-        if (ne) NC_HIP(ctx, hipMemcpyAsync(ew.data(), ph->d_w, ne, hipMemcpyDeviceToHost, ctx->stream));
-        NC_HIP(ctx, hipMemcpyAsync(mq.data(), d_mq, R, hipMemcpyDeviceToHost, ctx->stream));
-        NC_HIP(ctx, hipMemcpyAsync(ok.data(), d_ok, R, hipMemcpyDeviceToHost, ctx->stream));
-        NC_HIP(ctx, hipMemcpyAsync(&status, d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        NC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (status) {
-        ph->weighted = false;
-        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_weights_from_bam: records that %s (status %d)",
-                       status & HQ_BAD_RECORD ? "leave the record stream" : "do not hold the fields their header claims", status);
-    }
-    ph->ew.swap(ew);
-    ph->rmapq.swap(mq);
-    ph->rok.swap(ok);
-    ph->weighted = true;
-    ph->solved = false;
-    return NC_OK;
-}
-
-int nc_snp_phase_weights(const nc_phase *ph, const uint8_t **entry_weight, const uint8_t **read_mapq, const uint8_t **read_ok)
-{
-    if (!ph) return NC_ERR_ARG;
-    if (entry_weight) *entry_weight = ph->weighted ? ph->ew.data() : nullptr;
-    if (read_mapq) *read_mapq = ph->weighted ? ph->rmapq.data() : nullptr;
-    if (read_ok) *read_ok = ph->weighted ? ph->rok.data() : nullptr;
     return NC_OK;
 }
 

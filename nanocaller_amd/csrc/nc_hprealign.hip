@@ -209,57 +209,51 @@ int nc_snp_phase_realign(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, c
                     (n_ins_bases && !reads->ins_bases)))
         return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_realign: the read table lacks the events or the inserted bases");
     *out = nullptr;
-    NC_TRY(hp_check_sites(ctx, n_sites, site_pos));
-    if (n_sites && (site_pos[0] < 1 || site_pos[n_sites - 1] > ref_len)) return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_realign: a site lies outside [1, %d]", ref_len);
     const double t0 = hp_now_ms();
-    nc_phase *ph = new nc_phase();
-    ph->ctx = ctx;
-    ph->n_reads = n_reads;
-    ph->n_sites = n_sites;
-    ph->site_pos.assign(site_pos, site_pos + n_sites);
-    ph->off.assign(n_reads + 1, 0);
-    int rc = NC_OK;
-    int32_t status = 0;
+    nc_phase *ph = nullptr;
+    NC_TRY(hp_new_handle(ctx, n_reads, n_sites, site_pos, &ph));
+    if (n_sites && (site_pos[0] < 1 || site_pos[n_sites - 1] > ref_len)) {
+        nc_snp_phase_free(ph);
+        return nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_realign: a site lies outside [1, %d]", ref_len);
+    }
+    HpErr hip{ctx};
     {
         HpScratch sc;
         int32_t *d_spos = nullptr, *d_cnt = nullptr, *d_first = nullptr, *d_status = nullptr;
         uint8_t *d_sal = nullptr, *d_pal = nullptr;
         int64_t *d_poff = nullptr;
         HrSite *d_sites = nullptr;
-        auto hip = [&](hipError_t e, const char *what) {
-            if (e != hipSuccess && rc == NC_OK) rc = nc_fail(ctx, NC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-        };
-        if ((rc = sc.get(ctx, &d_spos, n_sites + 1)) || (rc = sc.get(ctx, &d_sal, 2 * (size_t)n_sites + 2)) || (rc = sc.get(ctx, &d_cnt, n_reads + 1)) ||
-            (rc = sc.get(ctx, &d_first, n_reads + 1)) || (rc = sc.get(ctx, &d_status, 1)) || (rc = sc.get(ctx, &d_poff, n_reads + 1)) ||
-            (rc = sc.get(ctx, &d_sites, n_sites + 1))) {
+        if ((hip.rc = sc.get(ctx, &d_spos, n_sites + 1)) || (hip.rc = sc.get(ctx, &d_sal, 2 * (size_t)n_sites + 2)) || (hip.rc = sc.get(ctx, &d_cnt, n_reads + 1)) ||
+            (hip.rc = sc.get(ctx, &d_first, n_reads + 1)) || (hip.rc = sc.get(ctx, &d_status, 1)) || (hip.rc = sc.get(ctx, &d_poff, n_reads + 1)) ||
+            (hip.rc = sc.get(ctx, &d_sites, n_sites + 1))) {
             nc_snp_phase_free(ph);
-            return rc;
+            return hip.rc;
         }
         hip(hipMalloc(&ph->d_off, (n_reads + 1) * sizeof(int64_t)), "hipMalloc(offsets)");
         hip(hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream), "status reset");
-        if (n_sites && rc == NC_OK) {
+        if (n_sites && hip.rc == NC_OK) {
             hip(hipMemcpyAsync(d_spos, site_pos, n_sites * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "site upload");
             hip(hipMemcpyAsync(d_sal, site_alleles, 2 * (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream), "allele upload");
-            if (rc == NC_OK) {
+            if (hip.rc == NC_OK) {
                 k_hr_sites<<<(n_sites + 255) / 256, 256, 0, ctx->stream>>>(n_sites, d_spos, d_sal, ref_code, ref_len, d_sites);
                 hip(hipGetLastError(), "k_hr_sites");
             }
         }
         const int nb = (n_reads + 255) / 256;
         std::vector<int64_t> poff(n_reads + 1, 0);
-        if (n_reads && rc == NC_OK) {
+        if (n_reads && hip.rc == NC_OK) {
             k_hr_span<<<nb, 256, 0, ctx->stream>>>(n_reads, reads->rd_start, reads->rd_end, n_sites, d_spos, d_first, d_cnt);
             hip(hipGetLastError(), "k_hr_span");
         }
-        if (rc == NC_OK) {
+        if (hip.rc == NC_OK) {
             k_hp_scan<<<1, HP_THREADS, 0, ctx->stream>>>(d_cnt, n_reads, d_poff);
             hip(hipGetLastError(), "k_hp_scan (pairs)");
             hip(hipMemcpyAsync(&poff[n_reads], d_poff + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream), "pair count download");
             hip(hipStreamSynchronize(ctx->stream), "span sync");
         }
-        const int64_t np = rc == NC_OK ? poff[n_reads] : 0;
-        if (rc == NC_OK) rc = sc.get(ctx, &d_pal, (size_t)np + 1);
-        if (rc == NC_OK && np) {
+        const int64_t np = hip.rc == NC_OK ? poff[n_reads] : 0;
+        if (hip.rc == NC_OK) hip.rc = sc.get(ctx, &d_pal, (size_t)np + 1);
+        if (hip.rc == NC_OK && np) {
             HrReads R;
             R.codes = codes;
             R.codes_len = codes_len;
@@ -278,41 +272,18 @@ int nc_snp_phase_realign(nc_ctx *ctx, const uint8_t *codes, int64_t codes_len, c
             k_hr_align<<<(unsigned)((np + 255) / 256), 256, 0, ctx->stream>>>(R, np, d_poff, d_first, d_sites, d_pal, d_status);
             hip(hipGetLastError(), "k_hr_align");
         }
-        if (rc == NC_OK && n_reads) {
+        if (hip.rc == NC_OK && n_reads) {
             k_hr_compact<false><<<nb, 256, 0, ctx->stream>>>(n_reads, d_poff, d_first, d_pal, d_cnt, nullptr, nullptr, nullptr);
             hip(hipGetLastError(), "k_hr_compact (count)");
         }
-        if (rc == NC_OK) {
-            k_hp_scan<<<1, HP_THREADS, 0, ctx->stream>>>(d_cnt, n_reads, ph->d_off);
-            hip(hipGetLastError(), "k_hp_scan");
-            hip(hipMemcpyAsync(ph->off.data(), ph->d_off, (n_reads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream), "offset download");
-            hip(hipMemcpyAsync(&status, d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream), "status download");
-            hip(hipStreamSynchronize(ctx->stream), "realign sync");
-        }
-        if (rc == NC_OK && status)
-            rc = nc_fail(ctx, NC_ERR_ARG, "nc_snp_phase_realign: a read's events, inserted bases or codes lie outside their arrays (malformed pack)");
-        const int64_t ne = rc == NC_OK ? ph->off[n_reads] : 0;
-        if (rc == NC_OK) {
-            hip(hipMalloc(&ph->d_site, ne * sizeof(int32_t) + 16), "hipMalloc(entries)");
-            hip(hipMalloc(&ph->d_al, ne + 16), "hipMalloc(alleles)");
-        }
-        if (rc == NC_OK && n_reads) {
+        hp_entries_from_counts(ph, hip, d_cnt, "realign sync", d_status, "nc_snp_phase_realign: a read's events, inserted bases or codes lie outside their arrays (malformed pack)", [&] {
             k_hr_compact<true><<<nb, 256, 0, ctx->stream>>>(n_reads, d_poff, d_first, d_pal, nullptr, ph->d_off, ph->d_site, ph->d_al);
             hip(hipGetLastError(), "k_hr_compact (fill)");
-        }
-        if (rc == NC_OK) {
-            ph->esite.resize(ne);
-            ph->eal.resize(ne);
-            if (ne) {
-                hip(hipMemcpyAsync(ph->esite.data(), ph->d_site, ne * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream), "entry download");
-                hip(hipMemcpyAsync(ph->eal.data(), ph->d_al, ne, hipMemcpyDeviceToHost, ctx->stream), "allele download");
-            }
-            hip(hipStreamSynchronize(ctx->stream), "realign sync");
-        }
+        });
     }
-    if (rc != NC_OK) {
+    if (hip.rc != NC_OK) {
         nc_snp_phase_free(ph);
-        return rc;
+        return hip.rc;
     }
     ph->ms[0] = (float)(hp_now_ms() - t0);
     *out = ph;

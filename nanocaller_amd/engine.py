@@ -536,20 +536,36 @@ class Engine:
         reads' record offsets in the reads' order (int64 device tensor): base qualities capped at w_max as weights, read_ok = MAPQ >= mapq_min
         (nc_snp_phase_weights_from_bam).
         The result then gains `entry_weight`, `read_mapq` and `read_ok`."""
-        L = self.L
         pos = np.ascontiguousarray(site_pos, np.int32)
-        h = C.c_void_p()
+        h = self._phase_open(pos, site_alleles, reads, csr, realign)
+        try:
+            self._phase_weigh(h, weights, bam_quals)
+            if site_gt is None:
+                self._check(self.L.nc_snp_phase_solve(self.ctx, h, int(max_cov)), "nc_snp_phase_solve")
+            else:
+                gt = np.ascontiguousarray(site_gt, np.uint8)
+                if gt.shape != pos.shape:
+                    raise ValueError("snp_phase: site_gt holds %d classes for %d sites" % (gt.size, pos.size))
+                self._check(self.L.nc_snp_phase_solve_gt(self.ctx, h, int(max_cov), _lib.npp(gt), int(distrust_cost)), "nc_snp_phase_solve_gt")
+            grp = np.ascontiguousarray(read_group, np.int32)
+            self._check(self.L.nc_haplotag_run(self.ctx, h, int(n_groups), _lib.npp(grp)), "nc_haplotag_run")
+            return self._phase_result(h, with_gt=site_gt is not None, with_weights=weights is not None or bam_quals is not None)
+        finally:
+            self.L.nc_snp_phase_free(h)
+
+    def _phase_open(self, pos, site_alleles, reads, csr, realign):
+        """the phasing handle of snp_phase's `realign=`, `reads=` or `csr=` (the caller frees it)"""
+        L, h = self.L, C.c_void_p()
+        if realign is not None or reads is not None:
+            al = np.ascontiguousarray(site_alleles, np.uint8).reshape(-1, 2)
+            torch.cuda.current_stream(self.device).synchronize()            # (the pack's upload may still be in flight on torch's stream)
         if realign is not None:
             codes, reads_c, n_events, n_ins, ref_code = realign
-            al = np.ascontiguousarray(site_alleles, np.uint8).reshape(-1, 2)
-            torch.cuda.current_stream(self.device).synchronize()
             rc = L.nc_snp_phase_realign(self.ctx, _ptr(codes), codes.numel(), C.byref(reads_c), int(n_events), int(n_ins), _ptr(ref_code),
                                         int(ref_code.numel()), pos.size, _lib.npp(pos), _lib.npp(al), C.byref(h))
             self._check(rc, "nc_snp_phase_realign")
         elif reads is not None:
             codes, rs, re_, so = reads
-            al = np.ascontiguousarray(site_alleles, np.uint8).reshape(-1, 2)
-            torch.cuda.current_stream(self.device).synchronize()            # (the pack's upload may still be in flight on torch's stream)
             rc = L.nc_snp_phase_gather(self.ctx, _ptr(codes), codes.numel(), int(rs.numel()), _ptr(rs), _ptr(re_), _ptr(so), pos.size, _lib.npp(pos),
                                        _lib.npp(al), C.byref(h))
             self._check(rc, "nc_snp_phase_gather")
@@ -557,59 +573,57 @@ class Engine:
             off, site, allele = (np.ascontiguousarray(a, t) for a, t in zip(csr, (np.int64, np.int32, np.uint8)))
             self._check(L.nc_snp_phase_load(self.ctx, off.size - 1, pos.size, _lib.npp(pos), _lib.npp(off), _lib.npp(site), _lib.npp(allele),
                                             C.byref(h)), "nc_snp_phase_load")
-        try:
-            if weights is not None and bam_quals is not None:
-                raise ValueError("snp_phase: weights= and bam_quals= are two sources of the same weights")
-            if weights is not None:
-                ew, ok = (None if a is None else np.ascontiguousarray(a, np.uint8) for a in weights)
-                v = _lib.PhaseArraysC()
-                L.nc_snp_phase_view(h, C.byref(v))
-                if (ew is not None and ew.size != v.n_entries) or (ok is not None and ok.size != v.n_reads):
-                    raise ValueError("snp_phase: weights= holds %s weights / %s flags for %d entries / %d reads"
-                                     % (None if ew is None else ew.size, None if ok is None else ok.size, v.n_entries, v.n_reads))
-                self._check(L.nc_snp_phase_set_weights(self.ctx, h, None if ew is None else _lib.npp(ew), None if ok is None else _lib.npp(ok)),
-                            "nc_snp_phase_set_weights")
-            if bam_quals is not None:
-                raw, rec_off, mapq_min, default_weight, w_max = bam_quals
-                v = _lib.PhaseArraysC()
-                L.nc_snp_phase_view(h, C.byref(v))
-                if rec_off.dtype != torch.int64 or rec_off.numel() != v.n_reads or raw.dtype != torch.uint8:
-                    raise ValueError("snp_phase: bam_quals= needs a uint8 record stream and %d int64 record offsets, one per read" % v.n_reads)
-                torch.cuda.current_stream(self.device).synchronize()
-                self._check(L.nc_snp_phase_weights_from_bam(self.ctx, h, _ptr(raw), int(raw.numel()), _ptr(rec_off), int(mapq_min), int(default_weight),
-                                                            int(w_max)), "nc_snp_phase_weights_from_bam")
-            if site_gt is None:
-                self._check(L.nc_snp_phase_solve(self.ctx, h, int(max_cov)), "nc_snp_phase_solve")
-            else:
-                gt = np.ascontiguousarray(site_gt, np.uint8)
-                if gt.shape != pos.shape:
-                    raise ValueError("snp_phase: site_gt holds %d classes for %d sites" % (gt.size, pos.size))
-                self._check(L.nc_snp_phase_solve_gt(self.ctx, h, int(max_cov), _lib.npp(gt), int(distrust_cost)), "nc_snp_phase_solve_gt")
-            grp = np.ascontiguousarray(read_group, np.int32)
-            self._check(L.nc_haplotag_run(self.ctx, h, int(n_groups), _lib.npp(grp)), "nc_haplotag_run")
-            v = _lib.PhaseArraysC()
-            L.nc_snp_phase_view(h, C.byref(v))
+        return h
 
-            def a(ptr, n, dt):
-                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), (n,)).copy() if n and ptr else np.zeros(0, dt)
-            R, S, nb, ng = v.n_reads, v.n_sites, v.n_blocks, v.n_groups
-            extra = {}
-            if site_gt is not None:
-                g = C.c_void_p()
-                L.nc_snp_phase_genotypes(h, C.byref(g))
-                extra = dict(site_gt=a(g, S, np.uint8))
-            if weights is not None or bam_quals is not None:
-                pw, pm, po = C.c_void_p(), C.c_void_p(), C.c_void_p()
-                L.nc_snp_phase_weights(h, C.byref(pw), C.byref(pm), C.byref(po))
-                extra.update(entry_weight=a(pw, v.n_entries, np.uint8), read_mapq=a(pm, R, np.uint8), read_ok=a(po, R, np.uint8))
-            return dict(entry_off=a(v.entry_off, R + 1, np.int64), entry_site=a(v.entry_site, v.n_entries, np.int32),
-                        entry_allele=a(v.entry_allele, v.n_entries, np.uint8), side=a(v.read_side, R, np.int8),
-                        site_block=a(v.site_block, S, np.int32), site_h=a(v.site_h, S, np.uint8), site_phased=a(v.site_phased, S, np.uint8).astype(bool),
-                        site_ps=a(v.site_ps, S, np.int32), block_first=a(v.block_first, nb, np.int32), block_last=a(v.block_last, nb, np.int32),
-                        block_ps=a(v.block_ps, nb, np.int32), block_cost=a(v.block_cost, nb, np.int64), group_hp=a(v.group_hp, ng, np.uint8),
-                        group_ps=a(v.group_ps, ng, np.int32), ms=dict(zip(("gather", "select", "dp", "haplotag"), list(v.ms))), **extra)
-        finally:
-            L.nc_snp_phase_free(h)
+    def _phase_view(self, h):
+        v = _lib.PhaseArraysC()
+        self.L.nc_snp_phase_view(h, C.byref(v))
+        return v
+
+    def _phase_weigh(self, h, weights, bam_quals):
+        """the weighted model on the handle, from snp_phase's `weights=` or `bam_quals=`"""
+        if weights is not None and bam_quals is not None:
+            raise ValueError("snp_phase: weights= and bam_quals= are two sources of the same weights")
+        if weights is None and bam_quals is None:
+            return
+        v = self._phase_view(h)
+        if weights is not None:
+            ew, ok = (None if a is None else np.ascontiguousarray(a, np.uint8) for a in weights)
+            if (ew is not None and ew.size != v.n_entries) or (ok is not None and ok.size != v.n_reads):
+                raise ValueError("snp_phase: weights= holds %s weights / %s flags for %d entries / %d reads"
+                                 % (None if ew is None else ew.size, None if ok is None else ok.size, v.n_entries, v.n_reads))
+            self._check(self.L.nc_snp_phase_set_weights(self.ctx, h, None if ew is None else _lib.npp(ew), None if ok is None else _lib.npp(ok)),
+                        "nc_snp_phase_set_weights")
+        else:
+            raw, rec_off, mapq_min, default_weight, w_max = bam_quals
+            if rec_off.dtype != torch.int64 or rec_off.numel() != v.n_reads or raw.dtype != torch.uint8:
+                raise ValueError("snp_phase: bam_quals= needs a uint8 record stream and %d int64 record offsets, one per read" % v.n_reads)
+            torch.cuda.current_stream(self.device).synchronize()
+            self._check(self.L.nc_snp_phase_weights_from_bam(self.ctx, h, _ptr(raw), int(raw.numel()), _ptr(rec_off), int(mapq_min), int(default_weight),
+                                                             int(w_max)), "nc_snp_phase_weights_from_bam")
+
+    def _phase_result(self, h, with_gt, with_weights) -> dict:
+        """snp_phase's result: copies of the handle's arrays"""
+        L, v = self.L, self._phase_view(h)
+
+        def a(ptr, n, dt):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), (n,)).copy() if n and ptr else np.zeros(0, dt)
+        R, S, nb, ng = v.n_reads, v.n_sites, v.n_blocks, v.n_groups
+        extra = {}
+        if with_gt:
+            g = C.c_void_p()
+            L.nc_snp_phase_genotypes(h, C.byref(g))
+            extra = dict(site_gt=a(g, S, np.uint8))
+        if with_weights:
+            pw, pm, po = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            L.nc_snp_phase_weights(h, C.byref(pw), C.byref(pm), C.byref(po))
+            extra.update(entry_weight=a(pw, v.n_entries, np.uint8), read_mapq=a(pm, R, np.uint8), read_ok=a(po, R, np.uint8))
+        return dict(entry_off=a(v.entry_off, R + 1, np.int64), entry_site=a(v.entry_site, v.n_entries, np.int32),
+                    entry_allele=a(v.entry_allele, v.n_entries, np.uint8), side=a(v.read_side, R, np.int8),
+                    site_block=a(v.site_block, S, np.int32), site_h=a(v.site_h, S, np.uint8), site_phased=a(v.site_phased, S, np.uint8).astype(bool),
+                    site_ps=a(v.site_ps, S, np.int32), block_first=a(v.block_first, nb, np.int32), block_last=a(v.block_last, nb, np.int32),
+                    block_ps=a(v.block_ps, nb, np.int32), block_cost=a(v.block_cost, nb, np.int64), group_hp=a(v.group_hp, ng, np.uint8),
+                    group_ps=a(v.group_ps, ng, np.int32), ms=dict(zip(("gather", "select", "dp", "haplotag"), list(v.ms))), **extra)
 
     # ---- writing BAM (csrc/nc_bamwrite.hip; bam_write.py).  Device tensors in and out, on the context's stream.
     def bam_retag_sizes(self, raw, rec_off, thash, tps, new_size, tag_idx, out_off, status, raw_byte_off=0):

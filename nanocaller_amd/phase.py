@@ -27,43 +27,40 @@ _FNV_OFFSET = np.uint64(1469598103934665603)
 _FNV_PRIME = np.uint64(1099511628211)
 
 
+def _selected(params, key, env, on=None) -> bool:
+    """params[key] (== `on`, or truthy where `on` is None); without that key, the environment's `env` == `on` (or '1')"""
+    if key in params:
+        return bool(params[key]) if on is None else params[key] == on
+    return os.environ.get(env) == ("1" if on is None else on)
+
+
 def device_phaser_selected(params) -> bool:
     """params['phaser'] == 'device'; without that key, the environment's NC_PHASER == 'device'"""
-    if "phaser" in params:
-        return params["phaser"] == "device"
-    return os.environ.get("NC_PHASER") == "device"
+    return _selected(params, "phaser", "NC_PHASER", "device")
 
 
 def phased_bam_selected(params) -> bool:
     """params['phased_bam'] truthy; without that key, the environment's NC_PHASED_BAM == '1' (phase_run writes <contig>.phased.bam behind
     the device phaser: bam_write.py)"""
-    if "phased_bam" in params:
-        return bool(params["phased_bam"])
-    return os.environ.get("NC_PHASED_BAM") == "1"
+    return _selected(params, "phased_bam", "NC_PHASED_BAM")
 
 
 def phase_realign_selected(params) -> bool:
     """params['phase_realign'] truthy; without that key, the environment's NC_PHASE_REALIGN == '1' (the device phaser takes a read's allele
     at a site from a local realignment against both haplotypes instead of the code in the site's column: `phase_contig(realign=True)`)"""
-    if "phase_realign" in params:
-        return bool(params["phase_realign"])
-    return os.environ.get("NC_PHASE_REALIGN") == "1"
+    return _selected(params, "phase_realign", "NC_PHASE_REALIGN")
 
 
 def phase_distrust_selected(params) -> bool:
     """params['phase_distrust'] truthy; without that key, the environment's NC_PHASE_DISTRUST == '1' (the device phaser may leave a site's called
     genotype at a price and takes the homozygous-ALT calls too: `phase_contig(distrust=True)`)"""
-    if "phase_distrust" in params:
-        return bool(params["phase_distrust"])
-    return os.environ.get("NC_PHASE_DISTRUST") == "1"
+    return _selected(params, "phase_distrust", "NC_PHASE_DISTRUST")
 
 
 def phase_weighted_selected(params) -> bool:
     """params['phase_weighted'] truthy; without that key, the environment's NC_PHASE_WEIGHTED == '1' (the device phaser weighs alleles by base
     quality and keeps reads below the MAPQ floor params['phase_mapq'] (default 20) out of the MEC: `phase_contig(weighted=True)`)"""
-    if "phase_weighted" in params:
-        return bool(params["phase_weighted"])
-    return os.environ.get("NC_PHASE_WEIGHTED") == "1"
+    return _selected(params, "phase_weighted", "NC_PHASE_WEIGHTED")
 
 
 def name_hash(names) -> np.ndarray:

@@ -155,6 +155,42 @@ def test_contig_against_truth(contig):
     assert acc >= 0.97 and frac_tagged >= 0.8
 
 
+def _assert_nothing_phased(got, n_reads, n_sites, n_groups):
+    assert got["entry_off"].size == n_reads + 1 and got["entry_site"].size == got["entry_allele"].size == got["entry_off"][-1]
+    assert got["side"].tolist() == [-1] * n_reads and got["site_block"].tolist() == [-1] * n_sites
+    for k in ("site_h", "site_phased", "site_ps"):
+        assert got[k].size == n_sites and not got[k].any(), k
+    for k in ("group_hp", "group_ps"):
+        assert got[k].size == n_groups and not got[k].any(), k
+    assert all(got[k].size == 0 for k in ("block_first", "block_last", "block_ps", "block_cost"))
+
+
+def test_degenerate_inputs_come_out_empty(eng, contig):
+    """the handle set-up and the counts-to-entries tail that the allele sources share (csrc/nc_happhase.h) at their zero counts: no reads and no
+    sites, reads without sites, reads that all have fewer than two entries (no block forms, the DP is not launched), and a resident pack's reads
+    against an empty site list -> arrays of the documented lengths, nothing phased or tagged, and the restatement's result"""
+    for reads, n_sites in (([], 0), ([[], [], []], 0), ([[(0, 1)], [], [(2, 0)]], 3)):
+        pos = 7 * np.arange(1, n_sites + 1, dtype=np.int32)
+        groups = np.arange(len(reads), dtype=np.int32)
+        got = eng.snp_phase(pos, None, groups, len(reads), csr=_csr(reads))
+        _assert_nothing_phased(got, len(reads), n_sites, len(reads))
+        assert got["entry_off"][-1] == sum(len(r) for r in reads)
+        _assert_equal_to_restatement(got, reads, pos, groups, 15)
+    import torch
+    from nanocaller_amd.generate_SNP_pileups import device_pack
+    from nanocaller_amd.phase import kept_reads
+    w = contig[0]
+    dp = device_pack(w, None, w.chrom, False, None, 0, by_name=True)[0]   # the resident pack, and its kept reads as phase_contig passes them
+    kept, rs, re_, slot = kept_reads(w, False)
+    n_reads = kept.size
+    assert n_reads > 1000 and int(slot[-1]) <= dp.codes.numel()
+    groups = np.arange(n_reads, dtype=np.int32)
+    got = eng.snp_phase(np.zeros(0, np.int32), np.zeros((0, 2), np.uint8), groups, n_reads,
+                        reads=(dp.codes,) + tuple(torch.from_numpy(a).to(eng.device) for a in (rs, re_, slot)))
+    _assert_nothing_phased(got, n_reads, 0, n_reads)
+    _assert_equal_to_restatement(got, [[]] * n_reads, np.zeros(0, np.int32), groups, 15)
+
+
 # ------------------------------------------------------------------------------------------- the indel pass on haplotags
 @pytest.fixture(scope="module")
 def pass2_files(tmp_path_factory):
