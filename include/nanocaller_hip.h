@@ -943,7 +943,11 @@ int nc_synth_indel_reads(nc_ctx *ctx, int64_t L, uint64_t seed, double p_sub, do
  *   arrays (checked on the device, nothing out of bounds is read).
  * nc_snp_phase_load: the same handle from a host CSR (entry_off [n_reads + 1], entry_site ascending per read, entry_allele 0 / 1).
  * nc_snp_phase_solve: read selection (max_cov in [1, 15]), blocks, slots (host) and the DP (one workgroup per block).  NC_ERR_CAPACITY
- *   when a partition cost exceeds the DP's 16-bit relative range.
+ *   when a partition cost exceeds the DP's 16-bit relative range (more than 65535 above its column's minimum; 65535 itself solves).
+ *   A handle may be solved again (another max_cov, the other solve, new weights).  Every solve first marks the handle unsolved, so one
+ *   that fails (NC_ERR_CAPACITY, NC_ERR_STATE, a HIP error) leaves nothing of an earlier result behind: nc_haplotag_run then answers
+ *   NC_ERR_STATE, nc_snp_phase_view gives n_blocks 0 and NULL for the read, site and block arrays, nc_snp_phase_genotypes NULL, until a
+ *   solve succeeds.  A solve also drops the haplotags of the solve before it (n_groups 0 until the next nc_haplotag_run).
  * nc_haplotag_run: read_group [n_reads] (host) = name group 0 .. n_groups-1 of every read; scores of one name are summed -> HP / PS.
  * nc_snp_phase_view: host views of the handle's arrays (valid until the next call on the handle or nc_snp_phase_free).
  *   read_side: -1 not accepted, else the read's part (0 = HP 1); site_block: -1 outside blocks; site_h: allele carried by HP 1;

@@ -699,6 +699,10 @@ struct HpSolve {
 int hp_solve(nc_ctx *ctx, nc_phase *ph, int32_t max_cov, const uint8_t *site_gt, int32_t gt_cost)
 {
     const double t0 = hp_now_ms();
+    ph->solved = false;                                                  // a solve that fails leaves the handle unsolved: its earlier result is reset below
+    ph->n_groups = 0;                                                    // (the haplotags of an earlier solve go with it)
+    ph->group_hp.clear();
+    ph->group_ps.clear();
     HpSolve sv(ctx, ph);
     sv.select_reads(max_cov);
     sv.reset_result(site_gt);
@@ -799,7 +803,7 @@ int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out)
     if (!ph || !out) return NC_ERR_ARG;
     out->n_reads = ph->n_reads;
     out->n_sites = ph->n_sites;
-    out->n_blocks = (int32_t)ph->block_first.size();
+    out->n_blocks = ph->solved ? (int32_t)ph->block_first.size() : 0;
     out->n_groups = ph->n_groups;
     out->n_entries = ph->off.empty() ? 0 : ph->off[ph->n_reads];
     out->entry_off = ph->off.data();
@@ -810,10 +814,10 @@ int nc_snp_phase_view(const nc_phase *ph, nc_phase_arrays *out)
     out->site_h = ph->solved ? ph->site_h.data() : nullptr;
     out->site_phased = ph->solved ? ph->site_phased.data() : nullptr;
     out->site_ps = ph->solved ? ph->site_ps.data() : nullptr;
-    out->block_first = ph->block_first.data();
-    out->block_last = ph->block_last.data();
-    out->block_ps = ph->block_ps.data();
-    out->block_cost = ph->block_cost.data();
+    out->block_first = ph->solved ? ph->block_first.data() : nullptr;
+    out->block_last = ph->solved ? ph->block_last.data() : nullptr;
+    out->block_ps = ph->solved ? ph->block_ps.data() : nullptr;
+    out->block_cost = ph->solved ? ph->block_cost.data() : nullptr;
     out->group_hp = ph->group_hp.data();
     out->group_ps = ph->group_ps.data();
     for (int k = 0; k < 4; k++) out->ms[k] = ph->ms[k];
