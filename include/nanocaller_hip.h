@@ -1176,6 +1176,32 @@ int nc_hap_indel_train_adam(nc_hap_indel_train *tr, float lr, float beta1, float
 int nc_hap_indel_train_info(nc_hap_indel_train *tr, int64_t *slice_sites, int64_t *workspace_bytes, int64_t *steps);
 int nc_hap_indel_train_stage_ms(nc_hap_indel_train *tr, int32_t on, float *ms7);
 
+/* ---- Text lines on the device (csrc/nc_vcfwrite.hip; ABI 11: added exports).  All pointers dev unless named _host; every
+ * call runs on the context's stream.  A list of lines is its text, the byte offset of every line in that text (n + 1 int64, ascending), and per
+ * line an ascending int64 key and the 0-based half-open interval [beg, end) an index files it under.
+ * nc_lines_merge: the stable merge of list A and list B by key; at equal keys B's lines go first, each list keeping its own order.  -> the merged
+ *   text d_out_text (out_bytes = the two texts' bytes, 16-byte aligned), d_out_off [na + nb + 1] (from 0), d_out_beg / d_out_end [na + nb] and
+ *   d_out_src [na + nb] = where every merged line came from (A's line i: i, B's line j: na + j).  d_status: three int32 the caller has zeroed;
+ *   non-zero where [0] the lists' bytes do not add up to out_bytes, [1] a list's offsets descend, [2] a list's keys descend: the text is then not
+ *   written.  No atomics: repeated calls give the same bytes.  na, nb or both may be 0 (the list's pointers are then not read).  Does not wait.
+ * nc_lines_index: the lines are those of one BGZF piece in file order: the piece's text starts at offset u0 of the offsets in d_line_off and is
+ *   cut into n_members members of 65,280 bytes (the last may be shorter), member k at byte d_foff[k] of the piece, d_foff[n_members] the piece's
+ *   length (nc_bgzf_assemble_device).  Virtual offsets are relative to the piece: d_foff[q / 65280] << 16 | q % 65280 for byte q of its text; the
+ *   last line ends at d_foff[n_members] << 16.  Two calls.  With d_run_bin == NULL and d_win_min == NULL the call fills d_work (int32
+ *   [n + (n + 4095) / 4096 + 8], kept unchanged for the second call) and info_host [4]: the number of runs, the first window, the number of
+ *   windows, and a status: bit 0 the ends descend, bit 1 the begins descend, bit 2 an interval is empty or negative or the offsets do not fit
+ *   the members (the counts are then 0 and the second call is refused); it waits.  With the outputs it writes the runs -- maximal runs of
+ *   consecutive lines of one bin reg2bin(beg, end): d_run_bin, d_run_vbeg (first byte of the first line), d_run_vend (behind the last line) --
+ *   and, for the windows first .. first + count - 1 of 2^min_shift positions, d_win_min = the smallest virtual offset of a line that overlaps
+ *   the window, all ones where none does; it does not wait. */
+int nc_lines_merge(nc_ctx *ctx, int64_t na, const uint8_t *d_a_text, const int64_t *d_a_off, const int64_t *d_a_key, const int64_t *d_a_beg,
+                   const int64_t *d_a_end, int64_t nb, const uint8_t *d_b_text, const int64_t *d_b_off, const int64_t *d_b_key,
+                   const int64_t *d_b_beg, const int64_t *d_b_end, int64_t out_bytes, uint8_t *d_out_text, int64_t *d_out_off,
+                   int64_t *d_out_beg, int64_t *d_out_end, int32_t *d_out_src, int32_t *d_status);
+int nc_lines_index(nc_ctx *ctx, int64_t n, const int64_t *d_beg, const int64_t *d_end, const int64_t *d_line_off, int64_t u0,
+                   int32_t n_members, const int64_t *d_foff, int32_t min_shift, int32_t depth, int32_t *d_work, int64_t *info_host,
+                   int32_t *d_run_bin, uint64_t *d_run_vbeg, uint64_t *d_run_vend, uint64_t *d_win_min);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@ EXPORTS = [
     "nc_hap_indel_train_create", "nc_hap_indel_train_free", "nc_hap_indel_train_set_weights", "nc_hap_indel_train_get_weights",
     "nc_hap_indel_train_forward", "nc_hap_indel_train_loss_grad", "nc_hap_indel_train_adam", "nc_hap_indel_train_info", "nc_hap_indel_train_stage_ms",
     "nc_refconf_columns", "nc_refconf_blocks", "nc_refconf_fetch", "nc_refconf_text",
+    "nc_lines_merge", "nc_lines_index",
 ]
 
 
@@ -321,6 +322,8 @@ def lib():
         L.nc_refconf_blocks.argtypes = [vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, C.POINTER(RefconfParamsC), C.POINTER(i64)]
         L.nc_refconf_fetch.argtypes = [vp, vp]
         L.nc_refconf_text.argtypes = [vp, i64, vp, vp, i32, i64, C.c_char_p, C.POINTER(RefconfParamsC), vp, vp, i64, C.POINTER(i64)]
+        L.nc_lines_merge.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+        L.nc_lines_index.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
         L.nc_snp_vcf_format.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, C.POINTER(i64)]
         for name in EXPORTS:
             fn = getattr(L, name)

@@ -389,9 +389,10 @@ class Engine:
         self._check(self.L.nc_refconf_fetch(self.ctx, _lib.npp(out) if n else None), "nc_refconf_fetch")
         return out
 
-    def refconf_text(self, blocks, ref_code, tile_pos0, chrom, *, error, haploid=False):
+    def refconf_text(self, blocks, ref_code, tile_pos0, chrom, *, error, haploid=False, device_out=False):
         """The records of `blocks` (refconf_blocks; host array or device tensor) written on the device -> (text uint8 host array, byte offset of
-        every line int64 [n + 1] host array).  ref_code: the grid's reference codes (device uint8, index 0 = tile_pos0)."""
+        every line int64 [n + 1] host array); device_out: the two device tensors instead.  ref_code: the grid's reference codes (device uint8,
+        index 0 = tile_pos0)."""
         prm = self._refconf_params(error, None, haploid)
         d_blocks = blocks if isinstance(blocks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(blocks, np.int32).reshape(-1, 6))
         d_blocks = d_blocks.to(device=self.device, dtype=torch.int32).contiguous()
@@ -402,7 +403,66 @@ class Engine:
         self._check(self.L.nc_refconf_text(*args, None, 0, C.byref(nbytes)), "nc_refconf_text")
         text = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=self.device)
         self._check(self.L.nc_refconf_text(*args, _ptr(text), int(nbytes.value), None), "nc_refconf_text")
+        if device_out:
+            return text[:int(nbytes.value)], off
         return text[:int(nbytes.value)].cpu().numpy(), off.cpu().numpy()
+
+    # ------------------------------------------------------------------ text lines (csrc/nc_vcfwrite.hip)
+    def lines_merge(self, a, b):
+        """The stable merge by key of two lists of lines, each a tuple of device tensors (text uint8, line_off int64 [n + 1] from 0, key int64 [n]
+        ascending, beg int64 [n], end int64 [n]) or None for an empty list; at equal keys b's lines go first (nc_lines_merge)
+        -> (text, line_off [na + nb + 1], beg, end, src int32: a's line i is i, b's line j is na + j), device tensors."""
+        dev = self.device
+
+        def norm(lst):
+            if lst is None or int(lst[2].numel()) == 0:
+                return 0, 0, (None,) * 5
+            text, off, key, beg, end = lst
+            n = int(key.numel())
+            if int(off.numel()) != n + 1 or int(beg.numel()) != n or int(end.numel()) != n:
+                raise ValueError("lines_merge: %d keys need %d offsets and %d begins and ends" % (n, n + 1, n))
+            t = (text.contiguous(),) + tuple(x.to(device=dev, dtype=torch.int64).contiguous() for x in (off, key, beg, end))
+            return n, int(text.numel()), t
+        na, ba, A = norm(a)
+        nb, bb, B = norm(b)
+        n, nbytes = na + nb, ba + bb
+        out = torch.empty(max(16, nbytes), dtype=torch.uint8, device=dev)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        beg, end = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+        src = torch.empty(n, dtype=torch.int32, device=dev)
+        st = torch.zeros(3, dtype=torch.int32, device=dev)
+        self._check(self.L.nc_lines_merge(self.ctx, na, *(_ptr(x) for x in A), nb, *(_ptr(x) for x in B), nbytes, _ptr(out), _ptr(off),
+                                          _ptr(beg) if n else None, _ptr(end) if n else None, _ptr(src) if n else None, _ptr(st)), "nc_lines_merge")
+        bad = st.cpu().numpy()
+        if bad.any():
+            raise ValueError("lines_merge: %s" % "; ".join(w for w, x in zip(("the texts do not hold the bytes their offsets say", "a list's line offsets descend",
+                                                                             "a list's keys descend"), bad) if x))
+        return out[:nbytes], off, beg, end, src
+
+    def lines_index(self, beg, end, line_off, u0, foff, *, min_shift=14, depth=5):
+        """A BGZF piece's share of a CSI index (nc_lines_index): its n lines in file order (device int64 tensors: 0-based beg / end [n], line_off
+        [n + 1] with the piece's text starting at offset u0), foff = device int64 [members + 1], where every member starts in the piece and the
+        piece's length.  -> dict(run_bin int32, run_vbeg, run_vend uint64: the chunk runs; w0, win_min uint64: the window minima from window w0
+        on), host arrays; virtual offsets are relative to the piece.  Raises ValueError where the ends or begins do not ascend."""
+        n = int(beg.numel())
+        if n == 0:
+            return dict(run_bin=np.zeros(0, np.int32), run_vbeg=np.zeros(0, np.uint64), run_vend=np.zeros(0, np.uint64), w0=0, win_min=np.zeros(0, np.uint64))
+        work = torch.empty(n + (n + 4095) // 4096 + 8, dtype=torch.int32, device=self.device)
+        info = (C.c_int64 * 4)()
+        args = (self.ctx, n, _ptr(beg), _ptr(end), _ptr(line_off), int(u0), int(foff.numel()) - 1, _ptr(foff), int(min_shift), int(depth), _ptr(work), info)
+        self._check(self.L.nc_lines_index(*args, None, None, None, None), "nc_lines_index")
+        if info[3]:
+            raise ValueError("lines_index: %s" % "; ".join(w for k, w in enumerate(("the lines' ends do not ascend", "the lines' begins do not ascend",
+                                                                                    "an empty interval, or line offsets that do not fit the members")) if info[3] >> k & 1))
+        n_runs, w0, n_win = int(info[0]), int(info[1]), int(info[2])
+        out = torch.empty(4 * n_runs + 8 * (2 * n_runs + n_win), dtype=torch.uint8, device=self.device)    # one buffer, one copy back
+        v = out[:8 * (2 * n_runs + n_win)].view(torch.int64)
+        rb = out[8 * (2 * n_runs + n_win):].view(torch.int32)
+        self._check(self.L.nc_lines_index(*args, _ptr(rb), _ptr(v[:n_runs]), _ptr(v[n_runs:2 * n_runs]), _ptr(v[2 * n_runs:])), "nc_lines_index")
+        h = out.cpu().numpy()
+        hv = h[:8 * (2 * n_runs + n_win)].view(np.uint64)
+        return dict(run_bin=h[8 * (2 * n_runs + n_win):].view(np.int32).copy(), run_vbeg=hv[:n_runs].copy(), run_vend=hv[n_runs:2 * n_runs].copy(),
+                    w0=w0, win_min=hv[2 * n_runs:].copy())
 
     # ------------------------------------------------------------------ K2-K4
     def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1, int16=None) -> SnpSites:

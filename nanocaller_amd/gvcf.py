@@ -5,6 +5,10 @@ device (csrc/nc_refconf.hip through Engine.refconf_columns / refconf_blocks / re
 parsing, the three integer constants of the model, the header, the splice of a group's variant lines into its block text and the merge of the
 workers' files.  `scores` and `block_line` state the PL rule and the line format in plain Python: the tests compare the device with them.
 
+params['gvcf_writer'] = 'device' (or NC_GVCF_WRITER=device where the key is absent) takes the splice, the compression and
+the index to the device: `group_pieces` writes a group's lines as BGZF pieces (vcf_write.write_piece) to a `PieceFile`, `merge_pieces` concatenates
+the workers' pieces and joins their index summaries.  The default, 'host', is the path above.
+
 The model.  e = params['gvcf_error'] (default 0.1) is the per-read error rate; c_m = round(-10000 log10(1 - e)), c_x = round(-10000 log10 e),
 c_h = round(-10000 log10 0.5).  A column with n pileup entries, ref of them the reference base and alt = n - ref has S00 = ref c_m + alt c_x,
 S01 = n c_h, S11 = ref c_x + alt c_m; other = min(S01, S11) (haploid: S11); it is a no-call when n == 0 or S00 > other, else
@@ -35,6 +39,15 @@ def enabled(params) -> bool:
     if 'gvcf' in params:
         return bool(params['gvcf'])
     return os.environ.get('NC_GVCF') == '1'
+
+
+def writer(params) -> str:
+    """'host' or 'device': params['gvcf_writer'] where the key is present, else NC_GVCF_WRITER, else 'host' (section 22).  Only read when the
+    gVCF is on."""
+    v = params['gvcf_writer'] if 'gvcf_writer' in params else os.environ.get('NC_GVCF_WRITER', 'host')
+    if v not in ('host', 'device'):
+        raise ValueError("gvcf_writer must be 'host' or 'device', got %r" % (v,))
+    return v
 
 
 def constants(error=DEFAULT_ERROR):
@@ -173,3 +186,215 @@ def group_blocks(eng, held, chrom, haploid, spans, record_pos, cfg):
     text, off = eng.refconf_text(blocks, ref_code, tile_pos0, chrom, error=cfg['error'], haploid=haploid)
     start = blocks[:, 0].to('cpu').numpy().astype(np.int64) if blocks.shape[0] else np.zeros(0, np.int64)
     return text, off, start
+
+
+# ------------------------------------------------------------------------------------------------------------ the device writer (section 22)
+def piece_path(params, worker_id):
+    return worker_path(params, worker_id) + '.bgzf'
+
+
+def variant_lines(text):
+    """-> (byte offset of every line int64 [n + 1], len(REF) of every line int64 [n]) of record lines (uint8 array)"""
+    vt = np.asarray(text, np.uint8)
+    vend = np.flatnonzero(vt == 10) + 1
+    tabs = np.flatnonzero(vt == 9)
+    first = np.searchsorted(tabs, np.concatenate([[0], vend[:-1]]))       # every line's first tab: CHROM's
+    if vend.size and (first[-1] + 3 >= tabs.size or np.any(tabs[first + 3] >= vend)):
+        raise ValueError("variant_lines: a line with fewer than five fields")
+    return np.concatenate([[0], vend]).astype(np.int64), (tabs[first + 3] - tabs[first + 2] - 1).astype(np.int64)
+
+
+def chunk_runs(spans):
+    """maximal runs of abutting or overlapping intervals (both ends inclusive) -> [(start, end)], ascending"""
+    out = []
+    for s, e in sorted((int(s), int(e)) for s, e in spans):
+        if out and s <= out[-1][1] + 1:
+            out[-1][1] = max(out[-1][1], e)
+        else:
+            out.append([s, e])
+    return [tuple(x) for x in out]
+
+
+PIECE_ARRAYS = (('run_bin', np.int32), ('run_vbeg', np.uint64), ('run_vend', np.uint64), ('win_min', np.uint64))
+
+
+class PieceFile:
+    """A worker's pieces: the file they are appended to and their summaries, which close() writes to the sidecar <path>.npz.  It is the file
+    object write_piece writes to; with `pool` (a one-thread executor) a write runs there and write() returns once the write BEFORE it is done,
+    which is what write_piece's two staging buffers need."""
+
+    def __init__(self, path, pool=None):
+        self.path, self.pool, self.f, self.offset, self.pieces, self.pending = path, pool, open(path, 'wb'), 0, [], None
+        self.ms, self.merged_bytes = {}, 0                              # group_pieces' stage times and the bytes its merges wrote
+
+    def write(self, buf):
+        if self.pool is None:
+            self.f.write(buf)
+            return
+        self.flush()
+        self.pending = self.pool.submit(self.f.write, buf)
+
+    def flush(self):
+        if self.pending is not None:
+            pending, self.pending = self.pending, None
+            pending.result()
+
+    def add(self, piece, contig, first, last):
+        """file the summary of the piece write_piece has just written: its lines cover the 1-based positions first .. last of contig"""
+        self.flush()
+        self.pieces.append(dict(piece, contig=contig, first=int(first), last=int(last), offset=self.offset, file=self.path))
+        self.offset += int(piece['bytes'])
+
+    def close(self):
+        self.flush()
+        self.f.close()
+        save_pieces(self.path + '.npz', self.pieces)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def save_pieces(path, pieces):
+    """the summaries of a worker's pieces as one .npz: per piece contig, first and last position, file offset, length, lines, first window;
+    the runs and the window minima of all pieces back to back with their bounds"""
+    arrays = dict(contig=np.array([p['contig'] for p in pieces], dtype=str))
+    for k in ('first', 'last', 'offset', 'bytes', 'lines', 'w0'):
+        arrays[k] = np.array([int(p[k]) for p in pieces], np.int64)
+    for which, names in (('run', PIECE_ARRAYS[:3]), ('win', PIECE_ARRAYS[3:])):
+        arrays[which + '_ptr'] = np.concatenate([[0], np.cumsum([np.asarray(p[names[0][0]]).size for p in pieces])]).astype(np.int64)
+        for k, dt in names:
+            arrays[k] = np.concatenate([np.asarray(p[k], dt) for p in pieces]) if pieces else np.zeros(0, dt)
+    with open(path, 'wb') as f:
+        np.savez(f, **arrays)
+
+
+def load_pieces(path, file):
+    """-> the summaries save_pieces wrote, each with 'file' = the file its bytes are in"""
+    with np.load(path) as z:
+        a = {k: z[k] for k in z.files}
+    out = []
+    for i in range(a['first'].size):
+        p = dict(contig=str(a['contig'][i]), file=file, **{k: int(a[k][i]) for k in ('first', 'last', 'offset', 'bytes', 'lines', 'w0')})
+        for which, names in (('run', PIECE_ARRAYS[:3]), ('win', PIECE_ARRAYS[3:])):
+            lo, hi = int(a[which + '_ptr'][i]), int(a[which + '_ptr'][i + 1])
+            for k, _ in names:
+                p[k] = a[k][lo:hi]
+        out.append(p)
+    return out
+
+
+def group_pieces(eng, out, held, chrom, haploid, spans, variant_text, variant_pos, cfg, slab_members=4096):
+    """The device twin of group_blocks + splice: the group's blocks and their text are made on the device as there, the group's variant lines
+    (bytes or uint8 array, one line per position of variant_pos, ascending) are uploaded and merged in between (Engine.lines_merge: a block that
+    starts where a record stands follows it, as splice's searchsorted has it), and one BGZF piece per maximal run of abutting or overlapping
+    chunk intervals is written to `out` (a PieceFile) by vcf_write.write_piece.  -> the pieces' summaries (they are filed in `out` as well)."""
+    import torch
+
+    from . import vcf_write
+    from .bgzf import event_timed
+    words, ref_code, tile_pos0 = held
+    dev = eng.device
+    timed = event_timed(out.ms)                                         # (milliseconds per stage, summed over the groups: tools/bench_gvcf_write.py)
+    pos = np.asarray(variant_pos if variant_pos is not None else [], np.int64).reshape(-1)
+    cuts = np.stack([pos, pos], 1).astype(np.int32) if pos.size else None
+    blocks = timed('blocks', lambda: eng.refconf_blocks(words, tile_pos0, spans, cuts, error=cfg['error'], bands=cfg['bands'], haploid=haploid, device_out=True))
+    text, off = timed('text', lambda: eng.refconf_text(blocks, ref_code, tile_pos0, chrom, error=cfg['error'], haploid=haploid, device_out=True))
+    a = b = None
+    if blocks.shape[0]:
+        beg = blocks[:, 0].to(torch.int64) - 1
+        a = (text, off, beg, beg, blocks[:, 1].to(torch.int64))
+    if pos.size:
+        vt = np.frombuffer(variant_text, np.uint8) if isinstance(variant_text, (bytes, bytearray)) else np.asarray(variant_text, np.uint8)
+        voff, ref_len = variant_lines(vt)
+        if voff.size - 1 != pos.size:
+            raise ValueError("group_pieces: %d variant lines for %d positions" % (voff.size - 1, pos.size))
+        b = tuple(torch.from_numpy(np.array(x)).to(dev) for x in (vt, voff, pos - 1, pos - 1, pos - 1 + ref_len))
+    m_text, m_off, m_beg, m_end, _ = timed('merge', lambda: eng.lines_merge(a, b))
+    out.merged_bytes += int(m_text.numel())
+    n = int(m_beg.numel())
+    if n == 0:
+        return []
+    runs = chunk_runs(spans)
+    edges = torch.tensor([[s - 1, e] for s, e in runs], dtype=torch.int64, device=dev).reshape(-1)
+    at = torch.searchsorted(m_beg, edges)                               # the lines that begin inside each run
+    ends = m_end[(at[1::2] - 1).clamp(min=0)]
+    at, ends = at.cpu().numpy().reshape(-1, 2), ends.cpu().numpy()
+    if int((at[:, 1] - at[:, 0]).sum()) != n or np.any(at[1:, 0] != at[:-1, 1]):
+        raise ValueError("group_pieces: %s: lines outside the group's chunk intervals" % chrom)
+    made = []
+    for (l0, l1), last in zip(at.tolist(), ends.tolist()):
+        if l1 > l0:
+            piece = vcf_write.write_piece(eng, out, m_text, m_off[l0:l1 + 1], m_beg[l0:l1], m_end[l0:l1], slab_members=slab_members)
+            for k, v in piece['ms'].items():
+                out.ms[k] = out.ms.get(k, 0.0) + v
+            out.add(piece, chrom, int(m_beg[l0].item()) + 1, last)
+            made.append(out.pieces[-1])
+    return made
+
+
+class _Span:
+    """`left` bytes of a file object from where it stands, as a file object for shutil.copyfileobj"""
+
+    def __init__(self, f, left):
+        self.f, self.left = f, left
+
+    def read(self, size=-1):
+        if self.left <= 0:
+            return b''
+        got = self.f.read(self.left if size is None or size < 0 else min(size, self.left))
+        self.left -= len(got)
+        return got
+
+
+def merge_pieces(files, out_path, contigs, sample):
+    """The workers' piece files (each with its sidecar <file>.npz) as one position-sorted <out_path> (BGZF) + .csi, without reading a line: the
+    pieces sorted by (contig order, first position) are copied behind the header, which gets members of its own, and the index is their
+    summaries joined (hts_index.csi_from_summaries).  Two pieces of a contig that overlap raise ValueError before anything is written.
+    -> number of records"""
+    import shutil
+
+    from . import vcfio
+    from .bgzf import BGZF_EOF
+    from .hts_index import csi_from_summaries
+    order = {c: i for i, c in enumerate(contigs)}
+    pieces = []
+    for fn in files:
+        if os.path.exists(fn + '.npz'):
+            pieces.extend(p for p in load_pieces(fn + '.npz', fn) if p['lines'])
+    for p in pieces:
+        if p['contig'] not in order:
+            raise ValueError("merge_pieces: %s holds lines of contig %r, which the header does not name" % (p['file'], p['contig']))
+    pieces.sort(key=lambda p: (order[p['contig']], p['first']))
+    name = lambda p: '%s:%d-%d (%s, byte %d)' % (p['contig'], p['first'], p['last'], p['file'], p['offset'])  # noqa: E731
+    for p, q in zip(pieces, pieces[1:]):
+        if p['contig'] == q['contig'] and q['first'] <= p['last']:
+            raise ValueError("merge_pieces: the pieces %s and %s overlap: the file would not be sorted" % (name(p), name(q)))
+    hdr = header(contigs, sample).encode()
+    comp, coff = vcfio.bgzf_compress(hdr)
+    head = comp[:int(coff[-(-len(hdr) // vcfio.BGZF_BLOCK)])]            # the header's members, without the EOF block behind them
+    per_ref = [[] for _ in contigs]
+    handles = {}
+    try:
+        with open(out_path, 'wb') as f:
+            f.write(head)
+            at = int(head.size)
+            for p in pieces:
+                src = handles.get(p['file'])
+                if src is None:
+                    src = handles[p['file']] = open(p['file'], 'rb')
+                src.seek(p['offset'])
+                span = _Span(src, p['bytes'])
+                shutil.copyfileobj(span, f, 1 << 22)
+                if span.left:
+                    raise ValueError("merge_pieces: %s ends inside the piece %s" % (p['file'], name(p)))
+                per_ref[order[p['contig']]].append(dict(p, offset=at))
+                at += p['bytes']
+            f.write(BGZF_EOF)
+    finally:
+        for src in handles.values():
+            src.close()
+    vcfio.bgzf_write(out_path + '.csi', csi_from_summaries(len(contigs), per_ref, aux=vcfio.tabix_aux(contigs)))
+    return sum(p['lines'] for p in pieces)

@@ -78,41 +78,88 @@ def index_bytes(fmt, n_ref, refid, beg, end, unmapped, bins, vbeg, vend, min_shi
     bins = reg2bin(beg, end, min_shift, depth) if bins is None else np.asarray(bins, np.int64)
     bai = fmt == "bai"
     out = [b"BAI\1" + struct.pack("<i", n_ref)] if bai else [b"CSI\1", struct.pack("<3i", min_shift, depth, len(aux)), aux, struct.pack("<i", n_ref)]
-    meta_bin = ((1 << (depth * 3 + 3)) - 1) // 7 + 1
     # [a, b) of every reference's records in the (sorted) record list; the unplaced ones lie behind them
     edges = np.searchsorted(np.where(refid < 0, n_ref, refid), np.arange(n_ref + 1))
     for r in range(n_ref):
         a, b = int(edges[r]), int(edges[r + 1])
-        if a == b:
-            out.append(struct.pack("<ii", 0, 0) if bai else struct.pack("<i", 0))
-            continue
-        ub, first, n_ch, cb, ce = bin_chunks(bins[a:b], vbeg[a:b], vend[a:b])
-        lin = linear_index(beg[a:b], end[a:b], vbeg[a:b], min_shift)
-        n_win = lin.size
-        if bai:
-            idx = np.maximum.accumulate(np.where(lin != _BIG, np.arange(n_win), -1))
-            lin_out = np.where(idx >= 0, lin[np.maximum(idx, 0)], np.uint64(0))
-        else:
-            idx = np.where(lin != _BIG, np.arange(n_win), n_win)
-            idx = np.minimum.accumulate(idx[::-1])[::-1]
-            filled = np.concatenate([lin, [np.uint64(0)]])[idx]
-            wdx = bin_first_window(ub, depth)
-            loff = np.where(wdx < n_win, filled[np.minimum(wdx, n_win - 1)], np.uint64(0))
-        chunks = np.empty(2 * cb.size, "<u8")
-        chunks[0::2], chunks[1::2] = cb, ce
-        blob = [struct.pack("<i", ub.size + bool(pseudo_bin))]
-        for k in range(ub.size):
-            s, n = int(first[k]), int(n_ch[k])
-            blob.append(struct.pack("<Ii", int(ub[k]), n) if bai else struct.pack("<IQi", int(ub[k]), int(loff[k]), n))
-            blob.append(chunks[2 * s:2 * (s + n)].tobytes())
-        if pseudo_bin:
-            n_un = int(np.count_nonzero(unmapped[a:b]))
-            blob.append(struct.pack("<Ii", meta_bin, 2) if bai else struct.pack("<IQi", meta_bin, 0, 2))
-            blob.append(struct.pack("<QQQQ", int(vbeg[a:b].min()), int(vend[a:b].max()), b - a - n_un, n_un))
-        if bai:
-            blob.append(struct.pack("<i", n_win) + lin_out.astype("<u8").tobytes())
-        out.append(b"".join(blob))
+        summ = None if a == b else reference_summary(beg[a:b], end[a:b], unmapped[a:b], bins[a:b], vbeg[a:b], vend[a:b], min_shift)
+        out.append(summary_bytes(fmt, summ, depth, pseudo_bin))
     out.append(struct.pack("<Q", int(refid.size - edges[n_ref])))
+    return b"".join(out)
+
+
+def reference_summary(beg, end, unmapped, bins, vbeg, vend, min_shift=14):
+    """first half of index_bytes, one reference's records -> what its index stores: dict(bins ascending, first = the first chunk of each,
+    n_chunks, chunk_beg, chunk_end, lin = the linear minima per 2^min_shift window from window 0 on, mapped, unmapped, vmin, vmax)"""
+    ub, first, n_ch, cb, ce = bin_chunks(bins, vbeg, vend)
+    n_un = int(np.count_nonzero(unmapped))
+    return dict(bins=ub, first=first, n_chunks=n_ch, chunk_beg=cb, chunk_end=ce, lin=linear_index(beg, end, vbeg, min_shift),
+                mapped=int(beg.size) - n_un, unmapped=n_un, vmin=int(vbeg.min()), vmax=int(vend.max()))
+
+
+def summary_bytes(fmt, summ, depth=5, pseudo_bin=True) -> bytes:
+    """second half of index_bytes: one reference's section of a .bai or .csi from its summary (None: a reference without records)"""
+    bai = fmt == "bai"
+    if summ is None:
+        return struct.pack("<ii", 0, 0) if bai else struct.pack("<i", 0)
+    meta_bin = ((1 << (depth * 3 + 3)) - 1) // 7 + 1
+    ub, first, n_ch, cb, ce, lin = (summ[k] for k in ("bins", "first", "n_chunks", "chunk_beg", "chunk_end", "lin"))
+    n_win = lin.size
+    if bai:
+        idx = np.maximum.accumulate(np.where(lin != _BIG, np.arange(n_win), -1))
+        lin_out = np.where(idx >= 0, lin[np.maximum(idx, 0)], np.uint64(0))
+    else:
+        idx = np.where(lin != _BIG, np.arange(n_win), n_win)
+        idx = np.minimum.accumulate(idx[::-1])[::-1]
+        filled = np.concatenate([lin, [np.uint64(0)]])[idx]
+        wdx = bin_first_window(ub, depth)
+        loff = np.where(wdx < n_win, filled[np.minimum(wdx, n_win - 1)], np.uint64(0))
+    chunks = np.empty(2 * cb.size, "<u8")
+    chunks[0::2], chunks[1::2] = cb, ce
+    blob = [struct.pack("<i", ub.size + bool(pseudo_bin))]
+    for k in range(ub.size):
+        s, n = int(first[k]), int(n_ch[k])
+        blob.append(struct.pack("<Ii", int(ub[k]), n) if bai else struct.pack("<IQi", int(ub[k]), int(loff[k]), n))
+        blob.append(chunks[2 * s:2 * (s + n)].tobytes())
+    if pseudo_bin:
+        blob.append(struct.pack("<Ii", meta_bin, 2) if bai else struct.pack("<IQi", meta_bin, 0, 2))
+        blob.append(struct.pack("<QQQQ", summ["vmin"], summ["vmax"], summ["mapped"], summ["unmapped"]))
+    if bai:
+        blob.append(struct.pack("<i", n_win) + lin_out.astype("<u8").tobytes())
+    return b"".join(blob)
+
+
+def join_piece_summaries(pieces, min_shift=14):
+    """One reference's summary (reference_summary's form) from the summaries of the BGZF pieces that hold its records, in file order.  A piece:
+    dict(offset = where it starts in the file, lines, run_bin, run_vbeg, run_vend = its maximal runs of consecutive lines of one bin in file
+    order, w0, win_min = its window minima from window w0 on), virtual offsets relative to the piece (Engine.lines_index).  The piece's file
+    offset << 16 is added; bin_chunks then joins, per bin, the runs whose offsets meet: inside a piece none do (a run is maximal), across a piece
+    border the last run of one piece and the first of the next when they share the bin and the pieces abut; shared windows take the minimum."""
+    rb, vb, ve = [], [], []
+    n_win = max(int(p["w0"]) + int(np.asarray(p["win_min"]).size) for p in pieces)
+    lin = np.full(n_win, _BIG, np.uint64)
+    for p in pieces:
+        base = np.uint64(int(p["offset"]) << 16)
+        rb.append(np.asarray(p["run_bin"], np.int64))
+        vb.append(np.asarray(p["run_vbeg"], np.uint64) + base)
+        ve.append(np.asarray(p["run_vend"], np.uint64) + base)
+        wm = np.asarray(p["win_min"], np.uint64)
+        w0 = int(p["w0"])
+        lin[w0:w0 + wm.size] = np.minimum(lin[w0:w0 + wm.size], np.where(wm == _BIG, _BIG, wm + base))
+    rb, vb, ve = np.concatenate(rb), np.concatenate(vb), np.concatenate(ve)
+    ub, first, n_ch, cb, ce = bin_chunks(rb, vb, ve)
+    return dict(bins=ub, first=first, n_chunks=n_ch, chunk_beg=cb, chunk_end=ce, lin=lin, mapped=sum(int(p["lines"]) for p in pieces), unmapped=0,
+                vmin=int(vb.min()), vmax=int(ve.max()))
+
+
+def csi_from_summaries(n_ref, pieces_of_ref, min_shift=14, depth=5, aux=b"", pseudo_bin=True) -> bytes:
+    """the uncompressed .csi of a file made of BGZF pieces, without its records: pieces_of_ref[r] = the summaries of reference r's pieces in
+    file order (join_piece_summaries; none: a reference without records).  Byte for byte what index_bytes writes from the records."""
+    out = [b"CSI\1", struct.pack("<3i", min_shift, depth, len(aux)), aux, struct.pack("<i", n_ref)]
+    for r in range(n_ref):
+        ps = [p for p in pieces_of_ref[r] if int(p["lines"])]
+        out.append(summary_bytes("csi", join_piece_summaries(ps, min_shift) if ps else None, depth, pseudo_bin))
+    out.append(struct.pack("<Q", 0))
     return b"".join(out)
 
 

@@ -166,7 +166,7 @@ VCF_HEADER = (                                                      # snpCaller.
 
 # keys of the `params` dict this module reads (all of them are in the dict NanoCaller:28-35 builds)
 # (opt-in keys of this project that the reference's dict does not have are read with .get and are not listed: 'genotype_sites',
-# 'genotype_only', 'neighbor_sites', 'neighbor_only', 'haploid_snp_model', 'gvcf', 'gvcf_error', 'gvcf_gq_bands'; tests/test_boundary.py holds this set
+# 'genotype_only', 'neighbor_sites', 'neighbor_only', 'haploid_snp_model', 'gvcf', 'gvcf_error', 'gvcf_gq_bands', 'gvcf_writer'; tests/test_boundary.py holds this set
 # to the reference's keys)
 PARAM_KEYS = frozenset(['chunks_list', 'regions_list', 'sam_path', 'fasta_path', 'mincov', 'maxcov', 'min_allele_freq', 'min_nbr_sites',
                         'threshold', 'snp_model', 'vcf_path', 'prefix', 'sample', 'seq', 'supplementary', 'exclude_bed',
@@ -445,7 +445,8 @@ class _Records:
     def __init__(self, f, pool, counter_Q, gvcf_f=None):
         self.f, self.pool, self.counter_Q, self.scratch, self.pending, self.gvcf_f = f, pool, counter_Q, None, None, gvcf_f
 
-    def emit(self, chrom, ploidy, r, grp, blocks=None):
+    def emit(self, chrom, ploidy, r, grp, blocks=None, keep_text=False):
+        """keep_text (the gVCF's device writer): -> the group's record lines as bytes; caller() merges them into the group's blocks on the device"""
         f = self.f
         text = b''
         if r['n']:
@@ -465,14 +466,16 @@ class _Records:
             self.gvcf_f.flush()
         for _ in grp:
             self.counter_Q.put(1)
+        if keep_text:
+            return text.tobytes() if r['n'] else b''                 # (a copy: the next group's lines overwrite the scratch)
 
     def wait(self):
         if self.pending is not None:
-            self.pending.result()                                    # keeps the records in group order; re-raises errors
+            return self.pending.result()                             # keeps the records in group order; re-raises errors
 
-    def submit(self, chrom, ploidy, r, grp, blocks=None):
+    def submit(self, chrom, ploidy, r, grp, blocks=None, keep_text=False):
         self.wait()
-        self.pending = self.pool.submit(self.emit, chrom, ploidy, r, grp, blocks)
+        self.pending = self.pool.submit(self.emit, chrom, ploidy, r, grp, blocks, keep_text)
 
 
 def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
@@ -506,12 +509,23 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
     from contextlib import ExitStack
     from . import gvcf
     gvcf_cfg = gvcf.settings(params) if gvcf.enabled(params) else None          # (opt-in: <prefix>.<worker>.snps.g.vcf beside the worker's VCF)
+    gvcf_dev = gvcf_cfg is not None and gvcf.writer(params) == 'device'          # (section 22: <prefix>.<worker>.snps.g.vcf.bgzf + .npz instead)
     with open(curr_vcf_path, 'wb') as f, ThreadPoolExecutor(max_workers=1) as pool, ExitStack() as stack:
-        gvcf_f = stack.enter_context(open(gvcf.worker_path(params, worker_id), 'wb')) if gvcf_cfg else None
+        gvcf_f = stack.enter_context(open(gvcf.worker_path(params, worker_id), 'wb')) if gvcf_cfg and not gvcf_dev else None
+        # the device writer's file writes run on the records thread, between two groups' records
+        pieces = stack.enter_context(gvcf.PieceFile(gvcf.piece_path(params, worker_id), pool)) if gvcf_dev else None
+        held_group = []                                              # the group whose records are being written: its pieces follow them
         records = _Records(f, pool, counter_Q, gvcf_f)
         ingest = _Ingest(params, keys, groups, device) if piped and keys else None
         in_flight = []                                               # groups whose kernels are queued and whose results have not been collected
         unrecorded = {}                                              # contig -> listed positions (params['genotype_sites']) inside its chunks that got no record
+
+        def write_pieces():
+            if held_group:
+                held, chrom, ploidy, grp, pos = held_group.pop()
+                text = records.wait()
+                gvcf.group_pieces(get_engine(device), pieces, held, chrom, ploidy != 'diploid', [(c['start'], c['end']) for c in grp], text, pos, gvcf_cfg)
+                pieces.flush()
 
         def collect():
             chrom, ploidy, call, grp, gi = in_flight.pop(0)
@@ -519,11 +533,17 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
             if r.get('genotype_listed'):
                 unrecorded[chrom] = unrecorded.get(chrom, 0) + r['genotype_listed'] - r['genotype_emitted']
             held, blocks = r.pop('gvcf', None), None
-            if gvcf_cfg is not None and held is not None:
+            if gvcf_dev:
+                # the blocks, the merge with the group's lines and the compression run on the device once the records thread has formatted the
+                # lines: the group before this one is due now, this one when the next is collected
+                write_pieces()
+                if held is not None:
+                    held_group.append((held, chrom, ploidy, grp, r['pos'] if r['n'] else None))
+            elif gvcf_cfg is not None and held is not None:
                 # blocks and their text on the device, cut at the positions of the lines this group gets (PASS or not)
                 blocks = gvcf.group_blocks(get_engine(device), held, chrom, ploidy != 'diploid', [(c['start'], c['end']) for c in grp],
                                            r['pos'] if r['n'] else None, gvcf_cfg)
-            records.submit(chrom, ploidy, r, grp, blocks)
+            records.submit(chrom, ploidy, r, grp, blocks, keep_text=gvcf_dev and held is not None)
             if last_use[chrom] == gi:
                 # a genome is walked contig by contig: drop the decoded alignments and the HBM pack of the one just finished (on an
                 # ingest thread when there is one: unmapping ~100 MB takes 8 ms this thread would not be launching kernels)
@@ -548,6 +568,7 @@ def caller(params, chunks_Q, counter_Q, snp_files, device=0, worker_id=1):
         while in_flight:
             collect()
         records.wait()
+        write_pieces()
         if not params.get('suppress_progress'):
             for chrom_, n_ in unrecorded.items():                    # (below mincov, a masked / non-AGTC / excluded reference base, no tensor)
                 print('%s: %s: %d listed sites got no record (not eligible for a pileup).' % (str(datetime.datetime.now()), chrom_, n_), flush=True)
@@ -577,6 +598,8 @@ def call_manager(params, devices=None):
     from .engine import local_device
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if (dist.is_available() and dist.is_initialized()) else (0, 1)
+    if gvcf.enabled(params):
+        gvcf.writer(params)                                           # (an unknown writer is refused before any work)
     if world > 1:                                                     # next to its GPU before anything page-locks memory or starts threads
         from .numa import bind_rank
         bind_rank(local_device(devices, rank))
@@ -629,7 +652,10 @@ def call_manager(params, devices=None):
                                     np.array([len(k[4].encode()) for k in recs], np.int64))   # + <path>.csi (tabix -p vcf --csi)
     if gvcf.enabled(params):
         # <prefix>.snps.g.vcf.gz + .csi: every rank's blocks and variant lines (a block never spans two ranks' chunk runs)
-        gvcf.merge_worker_files([gvcf.worker_path(params, r + 1) for r in range(world)],
-                                os.path.join(params['vcf_path'], '%s.snps.g.vcf.gz' % params['prefix']), contigs, params['sample'])
+        g_path = os.path.join(params['vcf_path'], '%s.snps.g.vcf.gz' % params['prefix'])
+        if gvcf.writer(params) == 'device':                          # compressed pieces, concatenated (section 22)
+            gvcf.merge_pieces([gvcf.piece_path(params, r + 1) for r in range(world)], g_path, contigs, params['sample'])
+        else:
+            gvcf.merge_worker_files([gvcf.worker_path(params, r + 1) for r in range(world)], g_path, contigs, params['sample'])
     shard.barrier()
     return pass_path

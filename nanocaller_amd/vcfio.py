@@ -64,12 +64,16 @@ def virtual_offsets(block_coff, uoff):
     return bgzf.virtual_offsets(uoff, block_coff)
 
 
+def tabix_aux(names):
+    """the tabix auxiliary block of a VCF's CSI: format VCF (2), columns 1 / 2 / 0, meta '#', skip 0, the contig names"""
+    nm = b"".join(n.encode() + b"\0" for n in names)
+    return struct.pack("<7i", 2, 1, 2, 0, ord("#"), 0, len(nm)) + nm
+
+
 def csi_bytes(names, tid, beg0, end0, voff_beg, voff_end, min_shift=14, depth=5):
     """Uncompressed CSI index of records sorted by (tid, beg0): 0-based half-open [beg0, end0), virtual offsets of each
-    record's first byte and of the byte after it.  tabix aux: format VCF (2), columns 1 / 2 / 0, meta '#', skip 0."""
-    nm = b"".join(n.encode() + b"\0" for n in names)
-    aux = struct.pack("<7i", 2, 1, 2, 0, ord("#"), 0, len(nm)) + nm
-    return index_bytes("csi", len(names), tid, beg0, end0, np.zeros(len(tid), bool), None, voff_beg, voff_end, min_shift, depth, aux=aux)
+    record's first byte and of the byte after it, with the tabix auxiliary block (tabix_aux)."""
+    return index_bytes("csi", len(names), tid, beg0, end0, np.zeros(len(tid), bool), None, voff_beg, voff_end, min_shift, depth, aux=tabix_aux(names))
 
 
 def write_vcf_gz_with_csi(path, header, lines_bytes, contigs, tid, pos1, ref_len, line_len):
