@@ -382,8 +382,9 @@ int nc_snp_scan_fetch_async(nc_ctx *ctx, void *copy_stream, int32_t *nbr_pos, in
  * the last nc_snp_scan on this context: one wavefront per site picks <= 20+20 neighbour sites, gathers the
  * codes of the site's reads at those columns and writes the (5,41,5) tensor.
  * Neighbour sites are limited to the owning chunk's scan window [max(1,start-50000), end+50000] (quirk E9).
- * Above maxcov the reference draws an unseeded random.sample (:215-216); this library keeps the first
- * maxcov reads in coordinate order (documented policy; parity is defined for depth <= maxcov).
+ * Above maxcov the reference draws an unseeded random.sample (:215-216).  By default this library keeps the first
+ * maxcov reads in coordinate order (reproducible, but the reads that start furthest left); after nc_set_downsample(ctx, 1,
+ * seed) it draws the seeded uniform sample described there.  Parity with the reference is defined for depth <= maxcov.
  * Outputs (dev, caller-allocated): x f32 [n_sites][5][41][5]; ref_code i32 [n_sites]; fwd_dp, rev_dp
  * i32 [n_sites][4] (AGTC counts over all reads by strand, :210-213); site_depth i32 [n_sites] (|S| after the
  * maxcov cut, :263).  Sites failing `len(cols) < min_nbr_sites` (:244) get valid[s]=0 and a zero tensor.
@@ -682,7 +683,8 @@ int nc_slices_free(nc_slices *s);
  * of `window_after` query bases from query_position_or_next (:331), the split into hap0 / hap1 / all reads by HP tag -- or,
  * where imp_idx[a] = k >= 0, by the imputed read collections imp_reads[imp_off[2k] .. imp_off[2k+1]) and
  * [imp_off[2k+1] .. imp_off[2k+2]) (read indices; :310-318) --, at most `maxcov` reads per set (the first in pileup order;
- * the reference samples at random, unseeded, :19-20), at least 2 / 2 / mincov reads (:48, :345; haploid: one set of >= mincov).
+ * the reference samples at random, unseeded, :19-20; this host-assembled route has no uniform sample: nc_set_downsample is
+ * read by the device pipeline, nc_indel_sites_plan), at least 2 / 2 / mincov reads (:48, :345; haploid: one set of >= mincov).
  * The result holds the flat arrays nc_star_msa_tensor takes (sets_per_anchor consecutive sets per kept anchor). */
 typedef struct nc_pass2 nc_pass2;
 typedef struct {
@@ -1201,6 +1203,18 @@ int nc_lines_merge(nc_ctx *ctx, int64_t na, const uint8_t *d_a_text, const int64
 int nc_lines_index(nc_ctx *ctx, int64_t n, const int64_t *d_beg, const int64_t *d_end, const int64_t *d_line_off, int64_t u0,
                    int32_t n_members, const int64_t *d_foff, int32_t min_shift, int32_t depth, int32_t *d_work, int64_t *info_host,
                    int32_t *d_run_bin, uint64_t *d_run_vbeg, uint64_t *d_run_vend, uint64_t *d_win_min);
+
+/* ---- Which reads a pileup deeper than maxcov keeps (csrc/nc_sample.h; ABI 11: an added export).  mode 0 (the default): the
+ * first maxcov entries in pileup order.  mode 1: a uniform sample without replacement that is a function of (seed, column, set, entry ordinal) alone.
+ * With mix32(p, s) the mixer of nc_snp_scan_set_sampling, for the pileup at the 1-based column v, the set id s (0: the SNP pileup and the indel
+ * caller's `all` set, haploid included; 1: the HP 1 set; 2: the HP 2 set) and n > maxcov entries counted in pack (= file) order,
+ *     base = mix32(v, seed ^ C[s]),  C = {0x00000000, 0x68E31DA4, 0xB5297A4D};      key(j) = mix32(j, base),  0 <= j < n
+ * the sample is the maxcov entries of the smallest keys, kept in pileup order (for a fixed base the keys of distinct j differ).  Everything that is
+ * not the sample stays what it is: fwd_dp / rev_dp over all reads, site_depth = min(n, maxcov), the indel sets' mincov tests, an indel site's phase
+ * set from the pileup's first HP 1 read.  The mode is held in the context and read by the next nc_snp_featurize and nc_indel_sites_plan calls;
+ * anything but 0 or 1 is NC_ERR_ARG.  With mode 1 those two return NC_ERR_UNSUPPORTED -- they never fall back to the first-maxcov cut -- when a
+ * shared-names table is set (nc_snp_set_mates, nc_indel_set_mates) and, for the plan, with impute_indel_phase. */
+int nc_set_downsample(nc_ctx *ctx, int32_t mode, uint32_t seed);
 
 #ifdef __cplusplus
 }

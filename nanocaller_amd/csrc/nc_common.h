@@ -83,6 +83,9 @@ struct nc_ctx {
     bool sample_on = false;
     uint32_t sample_seed = 0;
     uint32_t sample_keep[6] = {0, 0, 0, 0, 0, 0};
+    // what the featurisers and the indel plan do above maxcov (nc_set_downsample): 0 the first maxcov entries, 1 a seeded uniform sample
+    int32_t downsample = 0;
+    uint32_t downsample_seed = 0;
     // indel columns to genotype (nc_indel_set_sites): borrowed device pointers, read by the next nc_indel_sites_plan calls
     int32_t n_isites = 0;
     const int32_t *isite_pos = nullptr;

@@ -221,6 +221,15 @@ int nc_set_tensor_format(nc_ctx *ctx, int fmt)
     return NC_OK;
 }
 
+int nc_set_downsample(nc_ctx *ctx, int32_t mode, uint32_t seed)
+{
+    if (!ctx) return NC_ERR_ARG;
+    if (mode != 0 && mode != 1) return nc_fail(ctx, NC_ERR_ARG, "nc_set_downsample: mode %d is neither 0 (the first maxcov entries) nor 1 (uniform)", mode);
+    ctx->downsample = mode;
+    ctx->downsample_seed = mode ? seed : 0u;
+    return NC_OK;
+}
+
 int nc_enable_timing(nc_ctx *ctx, int on)
 {
     if (!ctx) return NC_ERR_ARG;

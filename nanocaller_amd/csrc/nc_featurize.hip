@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "nc_common.h"
+#include "nc_sample.h"
 
 namespace {
 
@@ -88,6 +89,7 @@ struct FeatArgs {
     const int64_t *mate_key;
     const int4 *mate_rec;
     int32_t n_mates;
+    uint32_t seed;                 // (the SAMPLED forms) nc_set_downsample's seed
 };
 
 // The reference's pileup dicts are keyed by read NAME (generate_SNP_pileups.py:175,185): where several alignments of one name cover a column the
@@ -119,7 +121,9 @@ __device__ __forceinline__ int named_code(const FeatArgs &a, int64_t key, int32_
 // I16: the tensors leave as int16 (product path).  Then nothing is assembled in LDS: lane L < 41 takes tensor column L, fetches
 // the counters of the lane that walked that column (ds_bpermute) and writes its five rows' 10 bytes straight to global memory
 // (41 lanes x 10 B = one contiguous 410-byte row per store pair) -- no zero fill, no workgroup barrier, no LDS round trip.
-template <int CAP, bool I16>
+// SAMPLED (nc_set_downsample, mode 1): above maxcov the sampled reads are the seeded uniform sample of nc_sample.h instead of the first maxcov.  An
+// entry's membership needs the pileup's depth n, so where the tile holds more than maxcov entries at all a counting pass over them comes first.
+template <int CAP, bool I16, bool SAMPLED>
 __global__ __launch_bounds__(256) void k_featurize(FeatArgs a)
 {
     __shared__ __attribute__((aligned(16))) float sm[I16 ? 1 : 4][I16 ? 4 : NC_SNP_TENSOR + 3];
@@ -207,6 +211,26 @@ __global__ __launch_bounds__(256) void k_featurize(FeatArgs a)
         cnt_t cnt[4] = {0, 0, 0, 0};
         int n_all = 0;
         int fw[4] = {0, 0, 0, 0}, rv[4] = {0, 0, 0, 0};
+        uint32_t sbase = 0, sthr = 0;
+        bool deep = false;                                      // (SAMPLED) the pileup is deeper than maxcov: an entry is sampled when its key <= sthr
+        if constexpr (SAMPLED) {
+            if (ok && e1 - e0 > a.maxcov) {
+                int n = 0;
+                for (int eb = e0; eb < e1; eb += 64) {
+                    bool cov = false;
+                    if (eb + lane < e1) {
+                        const nc_tile_entry ent = a.tile_ent[eb + lane];
+                        cov = ent.start <= v && v < ent.end;
+                    }
+                    n += __popcll(__ballot(cov));
+                }
+                if (n > a.maxcov) {
+                    deep = true;
+                    sbase = nc_sample_base(v, a.seed, 0);
+                    sthr = nc_sample_threshold(sbase, n, a.maxcov);
+                }
+            }
+        }
         for (int eb = e0; eb < e1; eb += 64) {
             const int e = eb + lane;
             bool cov = false;
@@ -237,10 +261,17 @@ __global__ __launch_bounds__(256) void k_featurize(FeatArgs a)
                 fw[b] += __popcll(f);
                 rv[b] += __popcll(mb[b] & ~f);
             }
+            if constexpr (SAMPLED) {
+                const int j = n_all + __popcll(m & ((1ull << lane) - 1ull));      // the entry's ordinal in the pileup
+                n_all += __popcll(m);
+                if (!ok) continue;
+                if (deep) m = __ballot(cov && mix32(j, sbase) <= sthr);           // deeper than maxcov: the maxcov entries of the smallest keys
+            } else {
             const int room = a.maxcov - n_all;                  // sampled reads still to take (wave-uniform)
             n_all += __popcll(m);
             if (!ok || room <= 0) continue;
             while (__popcll(m) > room) m &= ~(1ull << (63 - __builtin_clzll(m)));   // deeper than maxcov: the first maxcov in coordinate order
+            }
             // Reads are walked grouped by centre base k, so the histogram row is a compile-time register; reads deleted
             // at the centre (code 4) count nowhere and are skipped.
 #pragma unroll
@@ -393,7 +424,9 @@ __global__ __launch_bounds__(256) void k_featurize(FeatArgs a)
 // LDS: 22,432 bytes a workgroup (52 VGPRs): 7 waves per SIMD, as before.
 // MATES: the pack holds alignments that share read names (entries with bit 3 of base_flag; nc_snp_set_mates): such an entry is left out of a
 // column's pileup when a later alignment of its name covers the column, and its row reads every column through named_code.
-template <bool MATES>
+// SAMPLED: as in k_featurize (never together with MATES: nc_snp_featurize refuses that).  The select's histograms (nc_sample_threshold: 1 KB a wave)
+// are static LDS of every sampled instantiation: 26,528 bytes a workgroup here, so 6 waves per SIMD where the plain form holds 7.
+template <bool MATES, bool SAMPLED>
 __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
 {
     __shared__ int32_t nlist[4][64];
@@ -478,6 +511,27 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
     const bool ok = ncols >= a.min_nbr_sites;
     int n_all = 0, nsel = 0;
     int fw[4] = {0, 0, 0, 0}, rv[4] = {0, 0, 0, 0};
+    uint32_t sbase = 0, sthr = 0;
+    bool deep = false;                                            // (SAMPLED) the pileup is deeper than maxcov: an entry is sampled when its key <= sthr
+    if constexpr (SAMPLED) {
+        if (ok && e1 - e0 > a.maxcov) {
+            int n = 0;
+            for (int eb = e0; eb < e1; eb += 64) {
+                bool cov = false;
+                if (eb + lane < e1) {
+                    nc_tile_entry ent = pf_ent;
+                    if (eb != e0) ent = a.tile_ent[eb + lane];
+                    cov = ent.start <= v && v < ent.end;
+                }
+                n += __popcll(__ballot(cov));
+            }
+            if (n > a.maxcov) {
+                deep = true;
+                sbase = nc_sample_base(v, a.seed, 0);
+                sthr = nc_sample_threshold(sbase, n, a.maxcov);
+            }
+        }
+    }
     for (int eb = e0; eb < e1; eb += 64) {
         const int e = eb + lane;
         bool cov = false;
@@ -508,10 +562,17 @@ __global__ __launch_bounds__(256) void k_featurize_pairs(FeatArgs a)
             fw[b] += __popcll(f);
             rv[b] += __popcll(mb & ~f);
         }
+        if constexpr (SAMPLED) {
+            const int j = n_all + __popcll(m & ((1ull << lane) - 1ull));          // the entry's ordinal in the pileup
+            n_all += __popcll(m);
+            if (!ok) continue;
+            if (deep) m = __ballot(cov && mix32(j, sbase) <= sthr);               // deeper than maxcov: the maxcov entries of the smallest keys
+        } else {
         const int room = a.maxcov - n_all;
         n_all += __popcll(m);
         if (!ok || room <= 0) continue;
         while (__popcll(m) > room) m &= ~(1ull << (63 - __builtin_clzll(m)));   // deeper than maxcov: the first maxcov in coordinate order
+        }
         const bool sel = ((m >> lane) & 1ull) && code < 4;                     // (a read deleted at the centre counts nowhere)
         const unsigned long long ms = __ballot(sel);
         if (sel) {
@@ -746,6 +807,10 @@ int nc_snp_featurize(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_co
     a.mate_key = (const int64_t *)ctx->mate_key;
     a.mate_rec = (const int4 *)ctx->mate_rec;
     a.n_mates = ctx->n_mates;
+    a.seed = ctx->downsample_seed;
+    const bool sampled = ctx->downsample == 1;
+    if (sampled && a.n_mates > 0)
+        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_snp_featurize: the uniform sample above maxcov (nc_set_downsample) on alignments that share read names (nc_snp_set_mates)");
     const char *fp = getenv("NC_FEAT_PAIRS");
     const bool pairs = maxcov < MAXCOV_SMALL && a.x_i16 && !(fp && atoi(fp) == 0);
     if (a.n_mates > 0 && !pairs)
@@ -757,13 +822,18 @@ int nc_snp_featurize(nc_ctx *ctx, const nc_readpack *pack, const uint8_t *ref_co
     if (maxcov < MAXCOV_SMALL) {                            // 8-bit counter fields: at most 255 sampled reads
         // int16 tensors (the product path): lanes as (read, column) pairs (k_featurize_pairs); NC_FEAT_PAIRS=0: the scalar-driven read walk
         // (read per call: A/B checks)
-        if (pairs && a.n_mates > 0) hipLaunchKernelGGL(k_featurize_pairs<true>, grid, dim3(256), 0, ctx->stream, a);
-        else if (pairs) hipLaunchKernelGGL(k_featurize_pairs<false>, grid, dim3(256), 0, ctx->stream, a);
-        else if (a.x_i16) hipLaunchKernelGGL((k_featurize<MAXCOV_SMALL, true>), grid, dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_featurize<MAXCOV_SMALL, false>), grid, dim3(256), 0, ctx->stream, a);
+        if (pairs && a.n_mates > 0) hipLaunchKernelGGL((k_featurize_pairs<true, false>), grid, dim3(256), 0, ctx->stream, a);
+        else if (pairs && sampled) hipLaunchKernelGGL((k_featurize_pairs<false, true>), grid, dim3(256), 0, ctx->stream, a);
+        else if (pairs) hipLaunchKernelGGL((k_featurize_pairs<false, false>), grid, dim3(256), 0, ctx->stream, a);
+        else if (a.x_i16 && sampled) hipLaunchKernelGGL((k_featurize<MAXCOV_SMALL, true, true>), grid, dim3(256), 0, ctx->stream, a);
+        else if (a.x_i16) hipLaunchKernelGGL((k_featurize<MAXCOV_SMALL, true, false>), grid, dim3(256), 0, ctx->stream, a);
+        else if (sampled) hipLaunchKernelGGL((k_featurize<MAXCOV_SMALL, false, true>), grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_featurize<MAXCOV_SMALL, false, false>), grid, dim3(256), 0, ctx->stream, a);
     } else {
-        if (a.x_i16) hipLaunchKernelGGL((k_featurize<MAXCOV_CAP, true>), grid, dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_featurize<MAXCOV_CAP, false>), grid, dim3(256), 0, ctx->stream, a);
+        if (a.x_i16 && sampled) hipLaunchKernelGGL((k_featurize<MAXCOV_CAP, true, true>), grid, dim3(256), 0, ctx->stream, a);
+        else if (a.x_i16) hipLaunchKernelGGL((k_featurize<MAXCOV_CAP, true, false>), grid, dim3(256), 0, ctx->stream, a);
+        else if (sampled) hipLaunchKernelGGL((k_featurize<MAXCOV_CAP, false, true>), grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_featurize<MAXCOV_CAP, false, false>), grid, dim3(256), 0, ctx->stream, a);
     }
     NC_HIP(ctx, hipGetLastError());
     tm.stop();

@@ -78,6 +78,7 @@ struct SetArgs {
     ImpArgs imp;                       // (k_sets<.., true, ..>) the grouping of an imputed anchor's source column
     int32_t *err;
     IndelMates mt;                     // (k_sets<.., true>) alignments that share read names (nc_indel_set_mates); n = 0: none
+    uint32_t seed;                     // (k_sets<.., SAMPLED>) nc_set_downsample's seed
 };
 
 // a given list of indel columns (nc_indel_set_sites) against one group of chunks and its col_type (k_listed)
@@ -191,7 +192,7 @@ void nc_pipe_launch_pick_listed(hipStream_t st, int n_chunks, const PipeChunk *p
                                 int32_t *seg_src, int32_t *cnt, int32_t *err);
 void nc_pipe_launch_flatten(hipStream_t st, int n_chunks, const PipeChunk *pc, const int32_t *seg_pos, const int8_t *seg_type, const int32_t *cnt,
                             const int32_t *off, int32_t *anc_pos, int8_t *anc_type, int32_t *anc_chunk);
-void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impute);           // k_sets<fill, impute, sa.mt.n > 0>
+void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impute, bool sampled);   // k_sets<fill, impute, sa.mt.n > 0, sampled>
 // exclusive scans in two launches; `part` holds the partial sums (SC_PARTS of them: a longer array is refused).  out[n] = the total, except _pos
 int nc_pipe_scan_i32(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int32_t *out);
 int nc_pipe_scan_twb(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int64_t *out, int32_t *total_mbox);      // of tw_blocks(in[i]); the total also as a row mailbox

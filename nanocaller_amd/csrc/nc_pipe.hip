@@ -85,6 +85,12 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     const IndelMates mates = {ctx->imate_key, ctx->imate_rec, ctx->n_imates};
     if (mates.n > 0 && impute)
         return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_indel_sites_plan: impute_indel_phase on a contig whose kept alignments share read names");
+    // the uniform sample above maxcov (nc_set_downsample): k_sets has it in its plain form only; never served by the first-maxcov cut instead
+    const bool sampled = ctx->downsample == 1;
+    if (sampled && mates.n > 0)
+        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_indel_sites_plan: the uniform sample above maxcov (nc_set_downsample) on a contig whose kept alignments share read names");
+    if (sampled && impute)
+        return nc_fail(ctx, NC_ERR_UNSUPPORTED, "nc_indel_sites_plan: the uniform sample above maxcov (nc_set_downsample) with impute_indel_phase");
     nc_indel_events ev;
     ev.n_reads = reads->n_reads; ev.ev_off = reads->ev_off; ev.ev_pos = reads->ev_pos; ev.ev_len = reads->ev_len; ev.read_hap = reads->read_hap;
     NC_TRY(nc_indel_check(ctx, pack, &ev, prm, "nc_indel_sites_plan"));
@@ -239,7 +245,8 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
     sa.kept = (int32_t *)s->kept.p; sa.nuniq = (int32_t *)s->nuniq.p;
     sa.imp = imp; sa.imp.ent_read = sa.ent_read; sa.err = err;
     sa.mt = mates;
-    nc_pipe_launch_sets(ctx->stream, sa, false, impute);
+    sa.seed = ctx->downsample_seed;
+    nc_pipe_launch_sets(ctx->stream, sa, false, impute, sampled);
     NC_TRY(nc_pipe_scan_i32(ctx, ctx->stream, s->part_a, (const int32_t *)s->kept.p, na, (int32_t *)s->site_of.p));
     NC_TRY(nc_pipe_scan_i32(ctx, ctx->stream, s->part_a, (const int32_t *)s->nuniq.p, na, (int32_t *)s->al_of.p));
     NC_HIP(ctx, hipGetLastError());
@@ -275,7 +282,7 @@ extern "C" int nc_indel_sites_plan(nc_ctx *ctx, const nc_readpack *pack, const u
         NC_TRY(nc_ensure(ctx, s->al_ev, (size_t)std::max(nal, 1) * 8));
         sa.al_ev = (int2 *)s->al_ev.p;
     }
-    nc_pipe_launch_sets(ctx->stream, sa, true, impute);
+    nc_pipe_launch_sets(ctx->stream, sa, true, impute, sampled);
     if (listed) {
         NC_TRY(nc_ensure(ctx, s->site_src, NS * 4));
         nc_pipe_launch_src_sites(ctx->stream, n_chunks, (const PipeChunk *)s->pc.p, (const int32_t *)s->seg_src.p, (const int32_t *)s->cnt.p,

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "nc_pipe.h"
+#include "nc_sample.h"
 
 namespace {
 // dct['impute_indel_phase'] on the device pipeline (generate_indel_pileups.py:278-304; round 6).  K7 marks the columns that meet the rule's column-level
@@ -408,7 +409,10 @@ __global__ __launch_bounds__(256) void k_flatten(const PipeChunk *__restrict__ p
 // (:322-338): where several alignments of a name cover the anchor, the name is one entry at the rank of the first of them (a dict keeps the order of
 // first insertion) with the window of the last (`d_tot[qname] = dt` overwrites); its haplotype is the name's (hap0 when records of the name carry
 // HP 1 and HP 2: `if ... elif`), and the site's phase is phase_dict[name].  Every other entry takes the code of the plain form.
-template <bool FILL, bool IMP, bool MATES>
+// SAMPLED (nc_set_downsample, mode 1; never with IMP or MATES: the plan refuses those): a set deeper than maxcov holds the seeded uniform sample of
+// nc_sample.h instead of its first maxcov entries.  Membership needs the sets' sizes, so where the tile holds more than maxcov entries at all a counting
+// pass comes first, in the count launch and in the fill launch alike (the two must agree entry by entry).
+template <bool FILL, bool IMP, bool MATES, bool SAMPLED>
 __global__ __launch_bounds__(256) void k_sets(SetArgs p)
 {
     __shared__ ImpLds imp_lds[IMP ? 4 : 1];
@@ -446,6 +450,26 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
     if (ok && v >= p.tile_pos0 && t < p.n_tiles) {
         const int e0 = p.tile_off[t], e1 = p.tile_off[t + 1];
         const uint64_t lt = (1ull << lane) - 1;
+        uint32_t sb_all = 0, sb_1 = 0, sb_2 = 0, st_all = 0, st_1 = 0, st_2 = 0;
+        bool deep_all = false, deep_1 = false, deep_2 = false;                   // (SAMPLED) the set is deeper than maxcov: an entry is a member when its key <= st_*
+        if constexpr (SAMPLED) {
+            if (e1 - e0 > p.maxcov) {
+                int c_all = 0, c_1 = 0, c_2 = 0;
+                for (int eb = e0; eb < e1; eb += 64) {
+                    nc_tile_entry ent;
+                    ent.start = 0; ent.end = 0; ent.base_flag = 0;
+                    if (eb + lane < e1) ent = p.tile_ent[eb + lane];
+                    const bool cov = eb + lane < e1 && ent.start <= v && v < ent.end;
+                    const int hp = (int)((ent.base_flag >> 1) & 3);
+                    c_all += __popcll(__ballot(cov));
+                    c_1 += __popcll(__ballot(cov && hp == 1));
+                    c_2 += __popcll(__ballot(cov && hp == 2));
+                }
+                if (c_all > p.maxcov) { deep_all = true; sb_all = nc_sample_base(v, p.seed, 0); st_all = nc_sample_threshold(sb_all, c_all, p.maxcov); }
+                if (!p.haploid && c_1 > p.maxcov) { deep_1 = true; sb_1 = nc_sample_base(v, p.seed, 1); st_1 = nc_sample_threshold(sb_1, c_1, p.maxcov); }
+                if (!p.haploid && c_2 > p.maxcov) { deep_2 = true; sb_2 = nc_sample_base(v, p.seed, 2); st_2 = nc_sample_threshold(sb_2, c_2, p.maxcov); }
+            }
+        }
         for (int eb = e0; eb < e1; eb += 64) {
             const int e = eb + lane;
             nc_tile_entry ent;
@@ -490,6 +514,14 @@ __global__ __launch_bounds__(256) void k_sets(SetArgs p)
             const uint64_t m_all = __ballot(cov), m_1 = __ballot(cov && hp == 1), m_2 = __ballot(cov && hp == 2);
             const int my_all = n_all + __popcll(m_all & lt), my_1 = n_1 + __popcll(m_1 & lt), my_2 = n_2 + __popcll(m_2 & lt);
             int member = 0;
+            if constexpr (SAMPLED) {
+                if (cov) {
+                    const bool in_all = deep_all ? mix32(my_all, sb_all) <= st_all : true;
+                    if (p.haploid) member = in_all ? 1 : 0;
+                    else member = ((hp == 1 && (deep_1 ? mix32(my_1, sb_1) <= st_1 : true)) ? 1 : 0) | ((hp == 2 && (deep_2 ? mix32(my_2, sb_2) <= st_2 : true)) ? 2 : 0) |
+                                  (in_all ? 4 : 0);
+                }
+            } else
             if (cov) {
                 if (p.haploid) member = my_all < p.maxcov ? 1 : 0;
                 else member = ((hp == 1 && my_1 < p.maxcov) ? 1 : 0) | ((hp == 2 && my_2 < p.maxcov) ? 2 : 0) | (my_all < p.maxcov ? 4 : 0);
@@ -582,16 +614,19 @@ void nc_pipe_launch_flatten(hipStream_t st, int n_chunks, const PipeChunk *pc, c
 {
     hipLaunchKernelGGL(k_flatten, dim3(n_chunks), dim3(256), 0, st, pc, seg_pos, seg_type, cnt, off, anc_pos, anc_type, anc_chunk);
 }
-void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impute)
+void nc_pipe_launch_sets(hipStream_t st, const SetArgs &sa, bool fill, bool impute, bool sampled)
 {
     const dim3 grid((sa.n_anchor + 3) / 4);
-    if (sa.mt.n > 0 && !impute) {                                     // (shared names with impute_indel_phase: refused by the plan)
-        if (fill) hipLaunchKernelGGL((k_sets<true, false, true>), grid, dim3(256), 0, st, sa);
-        else hipLaunchKernelGGL((k_sets<false, false, true>), grid, dim3(256), 0, st, sa);
-    } else if (fill && impute) hipLaunchKernelGGL((k_sets<true, true, false>), grid, dim3(256), 0, st, sa);
-    else if (fill) hipLaunchKernelGGL((k_sets<true, false, false>), grid, dim3(256), 0, st, sa);
-    else if (impute) hipLaunchKernelGGL((k_sets<false, true, false>), grid, dim3(256), 0, st, sa);
-    else hipLaunchKernelGGL((k_sets<false, false, false>), grid, dim3(256), 0, st, sa);
+    if (sampled) {                                                    // (with shared names or impute_indel_phase: refused by the plan)
+        if (fill) hipLaunchKernelGGL((k_sets<true, false, false, true>), grid, dim3(256), 0, st, sa);
+        else hipLaunchKernelGGL((k_sets<false, false, false, true>), grid, dim3(256), 0, st, sa);
+    } else if (sa.mt.n > 0 && !impute) {                              // (shared names with impute_indel_phase: refused by the plan)
+        if (fill) hipLaunchKernelGGL((k_sets<true, false, true, false>), grid, dim3(256), 0, st, sa);
+        else hipLaunchKernelGGL((k_sets<false, false, true, false>), grid, dim3(256), 0, st, sa);
+    } else if (fill && impute) hipLaunchKernelGGL((k_sets<true, true, false, false>), grid, dim3(256), 0, st, sa);
+    else if (fill) hipLaunchKernelGGL((k_sets<true, false, false, false>), grid, dim3(256), 0, st, sa);
+    else if (impute) hipLaunchKernelGGL((k_sets<false, true, false, false>), grid, dim3(256), 0, st, sa);
+    else hipLaunchKernelGGL((k_sets<false, false, false, false>), grid, dim3(256), 0, st, sa);
 }
 int nc_pipe_scan_i32(nc_ctx *ctx, hipStream_t st, DevBuf &part, const int32_t *in, int32_t n, int32_t *out)
 {

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "nc_common.h"
+#include "nc_sample.h"     // mix32: the 32-bit mixer of background sampling
 
 namespace {
 
@@ -31,16 +32,6 @@ struct ScanX {
     uint32_t seed;
     uint32_t keep[6];              // per allele-frequency bin: a column is kept when mix(p, seed) < keep[bin]; 0 = never
 };
-
-// the 32-bit mixer of background sampling: a function of the 1-based position and the seed alone
-__device__ __forceinline__ uint32_t mix32(int32_t p, uint32_t seed)
-{
-    uint32_t x = ((uint32_t)p * 0x9E3779B1u) ^ seed;
-    x ^= x >> 16; x *= 0x85EBCA6Bu;
-    x ^= x >> 13; x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
 
 // SITES: a list of positions to genotype is set (nc_snp_scan_set_sites): site_bits holds one bit per column of the pack's tile grid (bit g = column
 // tile_pos0 + g, k_site_bits), a lane reads the 16 bits of its 16 positions as one aligned 16-bit load, and a listed column that passes every other

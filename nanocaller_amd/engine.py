@@ -174,6 +174,27 @@ class Engine:
         self._check(self.L.nc_set_tensor_format(self.ctx, 1 if int16 else 0), "nc_set_tensor_format")
         self.x_int16 = bool(int16)
 
+    def set_downsample(self, mode='first', seed=812):
+        """Which reads a pileup deeper than maxcov keeps in the next snp_featurize / indel_sites_device calls (nc_set_downsample): 'first' (or 0,
+        the default: the first maxcov in pileup order) or 'uniform' (or 1: the seeded uniform sample of nanocaller_amd.downsample)."""
+        from .downsample import MODES
+        m = MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise ValueError("set_downsample: mode is 'first' or 'uniform', not %r" % (mode,))
+        self._check(self.L.nc_set_downsample(self.ctx, int(m), int(seed) & 0xffffffff), "nc_set_downsample")
+
+    @contextmanager
+    def downsampling(self, downsample):
+        """`downsample` = None (nothing is set) or (mode, seed): set for the calls inside, and cleared afterwards whatever their outcome"""
+        if downsample is None:
+            yield
+            return
+        try:
+            self.set_downsample(*downsample)
+            yield
+        finally:
+            self.L.nc_set_downsample(self.ctx, 0, 0)
+
     @contextmanager
     def _snp_state(self, int16=None, exact_fp32=None, range_flags=None):
         """The context's tensor format, CNN precision (None: as they stand) and range watch (nc_cnn_range_watch; None: none) for ONE library
@@ -465,8 +486,10 @@ class Engine:
                     w0=w0, win_min=hv[2 * n_runs:].copy())
 
     # ------------------------------------------------------------------ K2-K4
-    def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1, int16=None) -> SnpSites:
-        """int16: sites.x as int16 (True) or as the reference's float32 (False); None: the engine's default (set_tensor_format).
+    def snp_featurize(self, dp: DevicePack, sites: SnpSites, *, seq, maxcov, min_nbr_sites=1, int16=None, downsample=None) -> SnpSites:
+        """downsample: None, or (mode, seed) for this call (set_downsample; downsample.resolve(params) gives it): with 'uniform' a pileup deeper
+        than maxcov keeps a seeded uniform sample, and a pack with shared read names is refused (NC_ERR_UNSUPPORTED).
+        int16: sites.x as int16 (True) or as the reference's float32 (False); None: the engine's default (set_tensor_format).
         min_nbr_sites: the reference's test of :244, which counts the site's own column; for sites of a scan in neighbour only mode
         (sites.nbr_only) it counts the listed neighbours alone, so the kernel is asked for one column more."""
         if sites.nbr_only:
@@ -491,7 +514,7 @@ class Engine:
         if dp.mates is not None:                                     # alignments that share read names: the featuriser keys them by name
             self._check(self.L.nc_snp_set_mates(self.ctx, int(dp.mates[0].numel()), _ptr(dp.mates[0]), _ptr(dp.mates[1])), "nc_snp_set_mates")
         try:
-            with self._snp_state(int16=i16):
+            with self._snp_state(int16=i16), self.downsampling(downsample):
                 self._check(self.L.nc_snp_featurize(self.ctx, C.byref(pc), _ptr(dp.ref_code), dp.tile_pos0, dp.ref_code.numel(),
                                                     _lib.SEQ_MODES[seq], int(maxcov), int(min_nbr_sites), _ptr(sites.x),
                                                     _ptr(sites.ref_code), _ptr(sites.fwd_dp), _ptr(sites.rev_dp), _ptr(sites.depth),

@@ -265,7 +265,9 @@ def get_snp_testing_candidates(dct, region, device=0):
     empty = ([], [], [], [], [], 0, [], [])
     if sites.n_sites == 0:
         return empty
-    eng.snp_featurize(dp_, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"])
+    # dct['downsample'] / dct['downsample_seed'] (downsample.py): above maxcov the first maxcov reads, or a seeded uniform sample
+    from .downsample import for_pack
+    eng.snp_featurize(dp_, sites, seq=dct["seq"], maxcov=dct["maxcov"], min_nbr_sites=dct["min_nbr_sites"], downsample=for_pack(dct, dp_.mates, chrom))
     valid = sites.valid.cpu().numpy().astype(bool)
     if not valid.any():
         return empty

@@ -311,8 +311,9 @@ _SYM = {"A": 0, "G": 1, "T": 2, "C": 3, "-": 4}
 
 def msa(seq_list, ref, v_pos, mincov, maxcov, aligner=None, device=0):
     """generate_indel_pileups.py:12-73 -> (flag, indel_flag, final_mat float64 (5,128,2), cns, ref_seq).  Down-sampling
-    (deterministic: the first `maxcov` reads in pileup order -- the reference draws an unseeded random.sample, :19-20, so its
-    result above maxcov is not reproducible; same policy as the SNP path), name sort, alignment by `aligner(names, seqs, ref)`,
+    (the first `maxcov` reads in pileup order -- the reference draws an unseeded random.sample, :19-20, so its result above maxcov is not
+    reproducible.  This per-set route has no other choice: dct['downsample'] = 'uniform' is served by the device indel pipeline, and the functions
+    that reach msa() raise for it), name sort, alignment by `aligner(names, seqs, ref)`,
     the histogram / consensus / tensor half on the GPU (nc_indel_tensor)."""
     sample = sorted(list(seq_list.keys())[:maxcov])
     if aligner == "device":
@@ -391,8 +392,8 @@ def get_indel_testing_candidates(dct, chunk, aligner=None, device=0):
 
 
 def _sample_set(seq_list, mincov, maxcov):
-    """the part of msa() before the aligner (:13-23): down-sample to maxcov (the first maxcov reads in pileup order: a
-    deterministic stand-in for the reference's unseeded random.sample), sort the names;
+    """the part of msa() before the aligner (:13-23): down-sample to maxcov (the first maxcov reads in pileup order, where the reference draws
+    an unseeded random.sample; the seeded uniform sample of dct['downsample'] = 'uniform' exists on the device pipeline only), sort the names;
     -> (names, seqs) or None when fewer than mincov reads remain"""
     sample = sorted(list(seq_list.keys())[:maxcov])
     if len(sample) < mincov:
@@ -547,7 +548,11 @@ def plan_routes(dct, chunks, haploid, route=None, mask=None, device=0):
 def _no_list_on_host(dct, chunks):
     """dct['genotype_indel_sites'] is served by the device pipeline only (nc_indel_set_sites): a part on the host-assembled route raises, it does
     not ignore the list"""
+    from .downsample import refuse_uniform
     from .genotype_sites import indel_list_given
+    # dct['downsample'] = 'uniform' likewise: these routes cut at the first maxcov reads and must not stand in for the sample
+    refuse_uniform(dct, "the host-assembled or the per-chunk indel route (no BAM path, nested chunks, route='host', a capacity limit of the device "
+                        "pipeline, or an external aligner: MUSCLE on PATH / aligner=): the device indel pipeline draws the sample")
     if indel_list_given(dct):
         raise ValueError("genotype_indel_sites: the list of indel sites is served by the device indel pipeline only; these chunks take the "
                          "host-assembled or the per-chunk route (no BAM path, nested chunks, route='host', a capacity limit of the device pipeline, "
@@ -618,6 +623,11 @@ def indel_sites_for_chunks(dct, chunks, device, haploid, fetch=True):
     # that combination keeps the refusal
     by_name = haploid or not dct.get("impute_indel_phase")
     eng, dp, reads_c, ctg, excl, mates = indel_pack_for(dct, chunks, device, by_name=by_name)
+    # dct['downsample'] / dct['downsample_seed'] (NC_DOWNSAMPLE / NC_DOWNSAMPLE_SEED): which reads a set deeper than maxcov keeps
+    from .downsample import for_pack
+    down = for_pack(dct, mates, chunks[0]["chrom"])
+    if down is not None and dct.get("impute_indel_phase") and not haploid:
+        raise ValueError("downsample='uniform' is not available with impute_indel_phase")
     # dct['genotype_indel_sites']: the columns listed for this contig become candidates under the scan's depth test (None: no list, nothing changes)
     from .genotype_sites import indel_sites_for
     sites, sites_long, sites_only = indel_sites_for(dct, chunks[0]["chrom"])
@@ -626,7 +636,7 @@ def indel_sites_for_chunks(dct, chunks, device, haploid, fetch=True):
     r = indel_sites_device(eng, dp, reads_c, len(ctg["fasta"]), spans, mincov=dct["mincov"],
                            maxcov=dct["maxcov"], win_size=dct["win_size"], small_win_size=dct["small_win_size"], ins_t=dct["ins_t"], del_t=dct["del_t"],
                            window_after=window_after_of(dct), haploid=haploid, excl=excl, fetch=fetch, impute=bool(dct.get("impute_indel_phase")),
-                           mates=mates, **kw)
+                           mates=mates, downsample=down, **kw)
     if sites is not None:
         inside = np.zeros(sites.size, bool)
         for a, b in spans:

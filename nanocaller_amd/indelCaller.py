@@ -23,7 +23,7 @@ from .weights import get_haploid_indel_model, get_indel_model  # noqa: F401  (sa
 
 # keys of the `params` dict this module and the indel featurisers read (all of them are in the dict NanoCaller:45-53 builds)
 # (opt-in keys of this project that the reference's dict does not have are read with .get and are not listed here: 'genotype_indel_sites',
-# 'genotype_indel_only', 'haploid_indel_model' -- 'haploid' or an .ncw of kind KIND_INDEL_HAP, weights.get_haploid_indel_model)
+# 'genotype_indel_only', 'downsample' / 'downsample_seed' (downsample.py: which reads a set deeper than maxcov keeps), 'haploid_indel_model' -- 'haploid' or an .ncw of kind KIND_INDEL_HAP, weights.get_haploid_indel_model)
 PARAM_KEYS = frozenset(['chunks_list', 'mode', 'snp_vcf', 'regions_list', 'sam_path', 'fasta_path', 'mincov', 'maxcov', 'indel_model',
                         'vcf_path', 'prefix', 'sample', 'seq', 'del_t', 'ins_t', 'impute_indel_phase', 'supplementary', 'exclude_bed',
                         'win_size', 'small_win_size', 'enable_whatshap', 'suppress_progress', 'phase_qual_score', 'verbose'])
@@ -174,6 +174,11 @@ def indel_run(params, indel_dict, job_Q, counter_Q, indel_files_list, device=0, 
     if indel_list_given(params) and (not native or rules != "native"):
         raise ValueError("genotype_indel_sites: the list of indel sites is served by the device indel pipeline with the native rules only "
                          "(this run: %s)" % ("an external aligner, the per-chunk route" if not native else "rules=%r" % rules))
+    # params['downsample'] = 'uniform' (the seeded uniform sample above maxcov) likewise: drawn by the device pipeline, never ignored
+    from .downsample import refuse_uniform, resolve
+    resolve(params)
+    if not native or rules != "native":
+        refuse_uniform(params, "an external aligner (the per-chunk route)" if not native else "rules=%r" % rules)
     curr_vcf_path = os.path.join(params['intermediate_indel_files_dir'], '%s.%d.indel.vcf' % (params['prefix'], worker_id))
     indel_files_list.append(curr_vcf_path)
     model_path = get_indel_model(params['indel_model'])

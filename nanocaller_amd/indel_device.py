@@ -88,8 +88,11 @@ def device_indel_reads(ctg, flag, dp, device):
 
 
 def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, win_size, small_win_size, ins_t, del_t, window_after,
-                       haploid=False, excl=None, fetch=True, impute=False, mates=None, scoring=None, sites=None, sites_long=None, sites_only=False):
-    """nc_indel_sites_plan + _run (+ _fetch) for a list of (start, end) chunks of one contig -> dict: n, x (device float32
+                       haploid=False, excl=None, fetch=True, impute=False, mates=None, scoring=None, sites=None, sites_long=None, sites_only=False,
+                       downsample=None):
+    """downsample: None, or (mode, seed) for this plan (Engine.set_downsample): with 'uniform' a read set deeper than maxcov is a seeded uniform
+    sample; a shared-names table or impute is then refused (NC_ERR_UNSUPPORTED).
+    nc_indel_sites_plan + _run (+ _fetch) for a list of (start, end) chunks of one contig -> dict: n, x (device float32
     [n, sets * 5, 128, 2]: the CNN input), and with fetch: pos / chunk / type / phase int32 [n], ref_len / alt_len int32 [n, sets],
     alt (uint8 codes, the ALT prefixes back to back in (site, set) order).  mates: indel_mate_table's (key, rec) when kept alignments share read
     names.  scoring: the star alignment's (gap open, gap extend, match, mismatch), default _lib.STAR_SCORING; nc_indel_sites_scoring refuses values
@@ -121,18 +124,19 @@ def indel_sites_device(eng, dp, reads_c, chrom_len, chunks, *, mincov, maxcov, w
     # the pointers of the table and of the list, so both are cleared again once the plan's and the run's launches are enqueued, whatever their
     # outcome -- that of the set calls included
     try:
-        check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,
-                                   C.c_void_p(mates[1].data_ptr()) if mates else None), "nc_indel_set_mates")
-        if listed:
-            ns = int(t_pos.numel())
-            check(L.nc_indel_set_sites(eng.ctx, ns, C.c_void_p(t_pos.data_ptr()) if ns else None,
-                                       C.c_void_p(t_long.data_ptr()) if (ns and t_long is not None) else None, 1 if sites_only else 0), "nc_indel_set_sites")
-        check(L.nc_indel_sites_plan(eng.ctx, C.byref(pc), C.c_void_p(dp.ref_code.data_ptr()), dp.tile_pos0, dp.ref_code.numel(), int(chrom_len),
-                                    C.byref(reads_c), C.c_void_p(excl.data_ptr()) if excl is not None else None, len(chunks), _lib.npp(starts),
-                                    _lib.npp(ends), C.byref(prm), int(window_after), int(maxcov), C.byref(n), C.byref(na)), "nc_indel_sites_plan")
-        N = n.value
-        x = torch.empty((N, S * 5, 128, 2), dtype=torch.float32, device=eng.device)
-        check(L.nc_indel_sites_run(eng.ctx, C.c_void_p(x.data_ptr())), "nc_indel_sites_run")
+        with eng.downsampling(downsample):
+            check(L.nc_indel_set_mates(eng.ctx, int(mates[0].numel()) if mates else 0, C.c_void_p(mates[0].data_ptr()) if mates else None,
+                                       C.c_void_p(mates[1].data_ptr()) if mates else None), "nc_indel_set_mates")
+            if listed:
+                ns = int(t_pos.numel())
+                check(L.nc_indel_set_sites(eng.ctx, ns, C.c_void_p(t_pos.data_ptr()) if ns else None,
+                                           C.c_void_p(t_long.data_ptr()) if (ns and t_long is not None) else None, 1 if sites_only else 0), "nc_indel_set_sites")
+            check(L.nc_indel_sites_plan(eng.ctx, C.byref(pc), C.c_void_p(dp.ref_code.data_ptr()), dp.tile_pos0, dp.ref_code.numel(), int(chrom_len),
+                                        C.byref(reads_c), C.c_void_p(excl.data_ptr()) if excl is not None else None, len(chunks), _lib.npp(starts),
+                                        _lib.npp(ends), C.byref(prm), int(window_after), int(maxcov), C.byref(n), C.byref(na)), "nc_indel_sites_plan")
+            N = n.value
+            x = torch.empty((N, S * 5, 128, 2), dtype=torch.float32, device=eng.device)
+            check(L.nc_indel_sites_run(eng.ctx, C.c_void_p(x.data_ptr())), "nc_indel_sites_run")
     finally:
         if mates:
             L.nc_indel_set_mates(eng.ctx, 0, None, None)

@@ -204,6 +204,9 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     neighbour sites whatever their allele frequency, beside the frequency rule or instead of it.
     params['haploid_snp_model'] (optional; else NC_HAPLOID_SNP_MODEL): 'haploid' or an .ncw of kind KIND_SNP_HAP for haploid chunks; a file brings
     its own train_coverage for the coverage scale (weights.get_haploid_SNP_model; a missing file or another kind raises).
+    params['downsample'] / params['downsample_seed'] (optional; else NC_DOWNSAMPLE / NC_DOWNSAMPLE_SEED; downsample.py): 'first' (the default) or
+    'uniform' -- which reads a pileup deeper than maxcov keeps: the first maxcov in pileup order, or a seeded uniform sample (seed 812 unless given).
+    Any other value raises ValueError, and so does 'uniform' on a contig whose kept alignments share read names.
     params['gvcf'] (optional; else NC_GVCF=1; gvcf.py): the result then carries 'gvcf', the per-column counts of the group's pack on the device
     (Engine.refconf_columns), from which caller() makes the reference-confidence blocks once the group's records are known.
     defer=True -> PendingCall: returns once the group's work is handed over; the caller starts the next group and collects result() afterwards.
@@ -214,6 +217,8 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     chrom = chunks[0]['chrom']
     ploidy = chunks[0]['ploidy']
     assert all(c['chrom'] == chrom and c['ploidy'] == ploidy for c in chunks)
+    from .downsample import for_pack, resolve
+    resolve(params)                                                  # (a bad value raises before any work)
     eng = get_engine(device)
     eng.use_torch_stream()
     if ploidy == 'diploid':
@@ -233,6 +238,7 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
         dpk = device_pack_for(params, chrom, device, span=contig_span(params['sam_path'], chrom, chunks))
     # Results drain on a second stream while the GPU keeps computing: the candidate arrays right after the scan, the
     # featuriser's per-site arrays during the CNN, and every CNN batch's probabilities while the next batch runs.
+    down = for_pack(params, dpk.mates, chrom)
     from .genotype_sites import count_listed, neighbor_sites_for, sites_for
     listed, only = sites_for(params, chrom)
     nbr_listed, nbr_only = neighbor_sites_for(params, chrom)
@@ -253,7 +259,7 @@ def call_chunks(params, chunks, device=0, dpk=None, defer=False, pipeline=None):
     # the tensors stay on the device: int16 between featuriser and CNN (exact, half the HBM traffic) unless the exact-fp32
     # trunk, which reads the reference's float32 layout, has been selected
     exact = eng.exact_fp32
-    eng.snp_featurize(dpk, sites, seq=params['seq'], maxcov=params['maxcov'], min_nbr_sites=params['min_nbr_sites'], int16=not exact)
+    eng.snp_featurize(dpk, sites, seq=params['seq'], maxcov=params['maxcov'], min_nbr_sites=params['min_nbr_sites'], int16=not exact, downsample=down)
     # default 1 never filters (:244), unless the neighbours come from a list alone (it then counts them, not the site's own column)
     all_valid = bool(sites.valid.all().item()) if params['min_nbr_sites'] > 1 or sites.nbr_only else True
     per_site = bool(params.get('disable_coverage_normalization'))
